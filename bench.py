@@ -23,8 +23,19 @@ all-gather of each bucket's last gradient.
 
 Rank 0 prints ONE JSON line (contract in the task statement), extended with
 `roofline` (dominant kernel: gtop_eval_wave_kernel, HBM-bound, algorithmic bytes
-of SURVEY.md §8d) and `cpu_baseline` (the oracle's C restatement timed on this
-box's host cores; N=1 only).
+of SURVEY.md §8d, from the timed region's own device clock).
+
+A plain run does only what that line's headline needs: set up, warm up, time
+the K steps, print.  `--full` adds everything else the bench measures or
+checks: the parity gate against the oracle, the launch-time probe behind the
+region, the collective's kernels-only region (N > 1), `extras` (the other
+BASELINE.json workloads and the batched optimizer) and `cpu_baseline` (the
+oracle's C restatement timed on this box's host cores); the last two N=1 only.
+
+`--dump-outputs DIR` writes what the timed path computed in its last step —
+`cost.npy` (one per trajectory) and `grad.npy` (trajectories x free variables),
+in the run's dtype — so that two builds can be compared output for output; the
+inputs depend on the arguments alone (fixed seeds).
 
 Environment knobs for rehearsals on a one-GPU box (never set by the driver):
   GTOP_BENCH_FORCE_DIST=1    initialise the process group (and run the
@@ -167,7 +178,40 @@ def parse():
                     help="keep the generator's random batch order (default: Morton-ordered for L2 locality)")
     ap.add_argument("--waves", type=int, default=0, help="wavefronts per workgroup (0 = auto, 1: there is one)")
     ap.add_argument("--spl", type=int, default=0, help="samples per lane (0 = auto, 3 or 6)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run the checks and figures beyond the headline: parity gate, launch-time probe, "
+                         "kernels-only region (N > 1), extras and cpu_baseline (N = 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (cost.npy, grad.npy) into DIR")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES, seed=0):
+    """Write each (name, numpy array) as out_dir/<name>.npy in float32 / float64 (the array's own width).  The arrays
+    share their leading (trajectory) axis; when together they exceed `limit` bytes, the same fixed, seeded, sorted
+    sample of rows is taken from every one of them.  Returns the row indices written (None: all of them)."""
+    import numpy as np
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32 if v.dtype == np.float32 else np.float64)
+              for k, v in arrays.items()}
+    rows = None
+    total = sum(a.nbytes for a in arrays.values())
+    if total > limit:
+        n = next(iter(arrays.values())).shape[0]
+        keep = max(1, int(n * limit // total))
+        rows = np.sort(np.random.default_rng(seed).choice(n, size=keep, replace=False))
+        arrays = {k: a[rows] for k, a in arrays.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), a)
+    return rows
 
 
 def launch_ranks(args):
@@ -296,10 +340,14 @@ def main():
         G -= 1
     nbuckets = args.steps // G
 
-    # ---- parity gate (rank 0): HIP vs oracle on a subsample of this rank's shard ----
+    # ---- parity gate (rank 0, --full): HIP vs oracle on a subsample of this rank's shard.  A plain run launches the
+    #      whole batch once instead, untimed and outside any graph capture, as the gate's own launch does ----
     parity = None
     osdf = None
-    if rank == 0:
+    if not args.full:
+        ctx.eval_device(x, Df, T)
+        torch.cuda.synchronize()
+    elif rank == 0:
         from oracle import oracle
         osdf = oracle_field(oracle, mp, ctx)
         parity = parity_check(ctx, oracle, osdf, x, Df, T, (batch.T[lo:hi], batch.Df[lo:hi], batch.x[lo:hi]),
@@ -517,6 +565,12 @@ def main():
             e2, g2 = timed_region(run_bucket)
             if rank == 0:
                 log(f"region repeat {k}: host {e2 * 1e6:.1f} us, device span {g2 * 1e6:.1f} us (first: {elapsed * 1e6:.1f} / {gpu_elapsed * 1e6:.1f})")
+    # what the timed path delivered in its last step (bucket nbuckets-1, step G-1), copied out before anything else runs
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        last_b = nbuckets - 1
+        dumped = {"cost": pipe.all_costs(last_b)[:, G - 1, :].reshape(-1).cpu().numpy(),
+                  "grad": pipe.all_grads(last_b).reshape(-1, n).cpu().numpy()}
     kern_ms_host = elapsed * 1e3 / args.steps
     kern_ms_gpu = gpu_elapsed * 1e3 / args.steps
     timed_src = (f"device wall clock ({clock_hz / 1e6:.0f} MHz) stamped by a one-lane kernel in front of the first and behind "
@@ -525,48 +579,54 @@ def main():
 
     # what the collective costs: the same K steps through the same buckets WITHOUT their all-gather, timed the same way
     kernels_only = None
-    if collective and kernel_graphs is not None:
+    if collective and kernel_graphs is not None and args.full:
         def run_kernels_only(b):
             kernel_graphs[b % len(kernel_graphs)].replay()
         kernels_only = timed_region(run_kernels_only)
 
     # Cross-check of the kernel's launch time: a probe of 1 000 launches of the same kernel, graph-replayed 50 at a
     # time, HIP events on the same stream, right after the timed region (no collective).  The roofline's `frac` is
-    # computed from the timed region's device-clock figure; the probe, the host clock's figure and the rocprofv3
-    # average of the same command committed under profiles/ go into the line beside it.
-    GR, reps = 50, 20
-    scratch = torch.zeros(GR, hi - lo, dtype=tdtype, device=dev)
+    # computed from the timed region's device-clock figure; the probe (--full), the host clock's figure and the
+    # rocprofv3 average of the same command committed under profiles/ go into the line beside it.
+    def launch_probe():
+        GR, reps = 50, 20
+        scratch = torch.zeros(GR, hi - lo, dtype=tdtype, device=dev)
 
-    def run_probe():
-        for s_ in range(GR):
-            ctx.eval_device(x, Df, T, scratch[s_], pipe.grad_ring[0])
-    probe = run_probe
-    probe_mode = "eager"
-    if graphs is not None:
-        try:
-            gph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(gph, capture_error_mode="thread_local"):
-                run_probe()
-            gph.replay()
-            probe = gph.replay
-            probe_mode = "hipgraph"
-        except Exception:
+        def run_probe():
+            for s_ in range(GR):
+                ctx.eval_device(x, Df, T, scratch[s_], pipe.grad_ring[0])
+        probe = run_probe
+        probe_mode = "eager"
+        if graphs is not None:
+            try:
+                gph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(gph, capture_error_mode="thread_local"):
+                    run_probe()
+                gph.replay()
+                probe = gph.replay
+                probe_mode = "hipgraph"
+            except Exception:
+                torch.cuda.synchronize()
+        t_w = time.perf_counter()
+        while time.perf_counter() - t_w < 0.010:      # (the clocks are up already; this covers the probe graph's upload)
+            for r in range(reps):
+                probe()
             torch.cuda.synchronize()
-    t_w = time.perf_counter()
-    while time.perf_counter() - t_w < 0.010:      # (the clocks are up already; this covers the probe graph's upload)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record(stream)
         for r in range(reps):
             probe()
+        e1.record(stream)
         torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    e0.record(stream)
-    for r in range(reps):
-        probe()
-    e1.record(stream)
-    torch.cuda.synchronize()
-    probe_ms = e0.elapsed_time(e1) / (reps * GR)
-    probe_src = (f"HIP events around {reps * GR} launches of the same kernel ({probe_mode}, {GR} per graph) right after "
-                 f"the timed region")
+        probe_ms = e0.elapsed_time(e1) / (reps * GR)
+        probe_src = (f"HIP events around {reps * GR} launches of the same kernel ({probe_mode}, {GR} per graph) right after "
+                     f"the timed region")
+        return probe_ms, probe_src
+
+    probe_ms, probe_src = None, "not measured (the launch-time probe runs with --full)"
+    if args.full:
+        probe_ms, probe_src = launch_probe()
 
     by_rank = None
     if collective:
@@ -579,6 +639,7 @@ def main():
         by_rank = {"host_s": allr[:, 0].tolist(), "gpu_s": allr[:, 1].tolist(),
                    "kernels_only_host_s": allr[:, 2].tolist(), "kernels_only_gpu_s": allr[:, 3].tolist()}
         elapsed = float(allr[:, 0].max())          # the job's time: the slowest rank's
+    if collective and args.full:
         # every rank must now hold every rank's costs (and gradients) of the last bucket
         last = pipe.all_costs(nbuckets - 1)
         assert torch.equal(last[rank], pipe.cost_ring[(nbuckets - 1) & 1])
@@ -604,6 +665,9 @@ def main():
 
         def gbs(ms):
             return launch_bytes / (ms * 1e-3) / 1e9 if ms else None
+
+        def frac(ms):
+            return gbs(ms) / HBM_PEAK_GBS if ms else None
         achieved = gbs(kern_ms_gpu)                            # GB/s per launch on this rank, from the timed region's device clock
         meas = measured_traffic(wkey)
         rocprof_us = meas.get("rocprof_avg_us")
@@ -655,15 +719,15 @@ def main():
                 # 2 000-step one); rocprofv3's figure is its instrumented dispatch interval, which for a 4 us kernel
                 # is not the kernel (an EMPTY 1 024-workgroup kernel reads 4.4 us there: DESIGN.md 5.1).
                 "avg_launch_us": kern_ms_gpu * 1e3,
-                "launch_us": {"timed_region_gpu": kern_ms_gpu * 1e3, "probe": probe_ms * 1e3,
+                "launch_us": {"timed_region_gpu": kern_ms_gpu * 1e3, "probe": probe_ms * 1e3 if probe_ms else None,
                               "timed_region_host": kern_ms_host * 1e3, "rocprof": rocprof_us},
-                "frac_by_source": {"timed_region_gpu": gbs(kern_ms_gpu) / HBM_PEAK_GBS,
-                                   "probe": gbs(probe_ms) / HBM_PEAK_GBS,
-                                   "timed_region_host": gbs(kern_ms_host) / HBM_PEAK_GBS,
-                                   "rocprof": (gbs(rocprof_us * 1e-3) / HBM_PEAK_GBS) if rocprof_us else None},
+                "frac_by_source": {"timed_region_gpu": frac(kern_ms_gpu),
+                                   "probe": frac(probe_ms),
+                                   "timed_region_host": frac(kern_ms_host),
+                                   "rocprof": frac(rocprof_us * 1e-3) if rocprof_us else None},
                 "launch_us_sources": {"timed_region_gpu": timed_src, "probe": probe_src, "timed_region_host": host_src,
                                       "rocprof": meas.get("rocprof_source")},
-                "gpu_vs_probe": kern_ms_gpu / probe_ms,
+                "gpu_vs_probe": kern_ms_gpu / probe_ms if probe_ms else None,
                 "launch_time_source": timed_src,
             },
             # what really bounds the kernel: instruction issue (the 200^3 field is cache resident)
@@ -693,17 +757,21 @@ def main():
             }
         if rehearsal:
             out["rehearsal"] = True
-        if world == 1 and not args.no_extras:
+        if world == 1 and args.full and not args.no_extras:
             from oracle import oracle
             try:   # untimed additions must never cost the main line
                 out["extras"] = extras(args, ctx, batch, mp, osdf, oracle, x, Df, T, tdtype, dev)
             except Exception as e:
                 out["extras"] = {"error": repr(e)}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(args, batch, osdf)
             except Exception as e:
                 out["cpu_baseline"] = {"error": repr(e)}
+        if dumped is not None:
+            rows = dump_outputs(args.dump_outputs, dumped)
+            log(f"outputs of the last timed step written to {args.dump_outputs}"
+                + (f" (a seeded sample of {len(rows)} rows)" if rows is not None else ""))
         print(json.dumps(out), flush=True)
 
     if collective:

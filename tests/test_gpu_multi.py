@@ -31,7 +31,7 @@ def _bench(args, env_extra, timeout=600):
 @pytest.mark.timeout(900)
 def test_bench_rank_path_with_rccl_at_world_size_one():
     r = _bench(["--gpus", "1", "--steps", "40", "--warmup", "7", "--bucket", "10", "--gather-grads",
-                "--no-extras", "--no-cpu-baseline"], {"GTOP_BENCH_FORCE_DIST": "1"})
+                "--full", "--no-extras", "--no-cpu-baseline"], {"GTOP_BENCH_FORCE_DIST": "1"})
     assert r["rehearsal"] is True and r["n_gpus"] == 1
     assert r["steps"] == 40 and r["warmup"] == 7           # --warmup honoured exactly
     assert r["config"]["launch"] == "hipgraph" and r["config"]["steps_per_bucket"] == 10
@@ -52,7 +52,7 @@ def test_bench_rank_path_with_rccl_at_world_size_one():
 def test_bench_rank_path_with_host_side_gathers():
     # the fallback when RCCL cannot be captured: graphs of kernels, one async all-gather call per bucket
     r = _bench(["--gpus", "1", "--steps", "40", "--warmup", "7", "--bucket", "10", "--gather-grads",
-                "--no-extras", "--no-cpu-baseline"],
+                "--full", "--no-extras", "--no-cpu-baseline"],
                {"GTOP_BENCH_FORCE_DIST": "1", "GTOP_BENCH_CAPTURE_GATHER": "0", "GTOP_BENCH_GATHER": "library"})
     assert r["config"]["launch"] == "hipgraph" and r["config"]["gather"].startswith("host call per bucket")
     assert r["parity"]["ok"] and r["value"] > 1e4
@@ -64,7 +64,7 @@ def test_bench_short_collective_run_and_its_buckets():
     runs in line behind its bucket's kernels, so the run is ONE bucket — one exposed gather, not two (bench.py has the
     measurements of the overlapping alternatives); with host-side asynchronous gathers, which do run beside the next
     bucket's kernels, it is split in two."""
-    args = ["--gpus", "1", "--steps", "20", "--warmup", "5", "--no-extras", "--no-cpu-baseline"]
+    args = ["--gpus", "1", "--steps", "20", "--warmup", "5", "--full", "--no-extras", "--no-cpu-baseline"]
     r = _bench(args, {"GTOP_BENCH_FORCE_DIST": "1", "GTOP_BENCH_GATHER": "library"})      # RCCL's all-gather, captured
     assert r["config"]["steps_per_bucket"] == 20 and r["config"]["buckets"] == 1 and r["steps"] == 20
     assert r["config"]["gather"] == "captured in each bucket's hipGraph" and r["collective"]["collective_exposed_us"] is not None
@@ -79,7 +79,7 @@ def test_bench_short_collective_run_and_its_buckets():
 def test_gpus_1_is_the_single_path_however_it_is_started():
     """`--gpus 1` must be byte for byte the path BENCH measures — no process group, no collective, every step in one
     graph, the device-clock stamps — whether the driver starts bench.py directly or under torchrun."""
-    args = ["--gpus", "1", "--steps", "20", "--warmup", "5", "--no-extras", "--no-cpu-baseline"]
+    args = ["--gpus", "1", "--steps", "20", "--warmup", "5", "--full", "--no-extras", "--no-cpu-baseline"]
     direct = _bench(args, {})
     env = dict(os.environ)
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
@@ -103,7 +103,7 @@ def test_gpus_1_is_the_single_path_however_it_is_started():
 
 @pytest.mark.timeout(900)
 def test_bench_self_launches_two_ranks_on_one_card():
-    r = _bench(["--gpus", "2", "--steps", "20", "--warmup", "5", "--batch", "512", "--gather-grads"],
+    r = _bench(["--gpus", "2", "--steps", "20", "--warmup", "5", "--batch", "512", "--gather-grads", "--full"],
                {"GTOP_BENCH_BACKEND": "gloo", "GTOP_BENCH_SHARE_DEVICE": "1"})
     assert r["rehearsal"] is True and r["n_gpus"] == 2 and r["scaling"] == "weak"
     assert r["config"]["global_batch"] == 1024 and r["config"]["batch_per_gpu"] == 512
@@ -123,7 +123,7 @@ def test_bench_self_launches_two_ranks_on_one_card():
 def test_a_rank_that_cannot_map_its_peers_sends_every_rank_to_the_library_gather():
     """The safety net of the push path: rank 1 fails to map rank 0's buffers (forced); BOTH ranks must then drop the
     mappings they hold and gather through the process group — the run completes, says which path it took and why."""
-    r = _bench(["--gpus", "2", "--steps", "20", "--warmup", "5", "--batch", "512"],
+    r = _bench(["--gpus", "2", "--steps", "20", "--warmup", "5", "--batch", "512", "--full"],
                {"GTOP_BENCH_BACKEND": "gloo", "GTOP_BENCH_SHARE_DEVICE": "1", "GTOP_PUSH_FORCE_FAIL": "1"})
     col = r["collective"]
     assert col["gather_impl"] == "library" and "rank 1" in col["push_note"] and "GTOP_PUSH_FORCE_FAIL" in col["push_note"]
