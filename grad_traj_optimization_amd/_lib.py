@@ -125,6 +125,9 @@ def load_library():
         "gtop_update_sdf_map_window": (C.c_int, [vp, dp, dp, dp, C.c_int]),
         "gtop_update_sdf_map_window_device": (C.c_int, [vp, dp, dp, vp, C.c_int, vp]),
         "gtop_set_field_precisions": (C.c_int, [vp, C.c_int]),
+        "gtop_set_field_sign": (C.c_int, [vp, C.c_int, C.c_double]),
+        "gtop_get_field_sign": (C.c_int, [vp, ip, dp]),
+        "gtop_group_set_field_sign": (C.c_int, [vp, C.c_int, C.c_double]),
         "gtop_device_clock_stamp": (C.c_int, [vp, vp, vp]),
         "gtop_push_rows": (C.c_int, [vp, vp, C.c_size_t, C.POINTER(C.c_void_p), C.c_int, vp, vp]),
         "gtop_shared_alloc": (C.c_int, [vp, C.c_size_t, C.POINTER(C.c_void_p), C.c_char_p]),
@@ -355,6 +358,18 @@ class GtopContext:
     def set_field_precisions(self, keep_fp32=True):
         """False: keep fp64 corner records only (the capturable map updates then skip the fp32 pass; fp32 evaluations fail)."""
         self._chk(self._L.gtop_set_field_precisions(self._h, 1 if keep_fp32 else 0))
+
+    def set_field_sign(self, signed=True, max_depth=0.0):
+        """Signed (True) or unsigned (False, the default) distance field from the next whole-map build on: negative
+        inside obstacles, max(-max_depth, res - distance to the nearest free voxel); max_depth 0 means 10000
+        (include/gtop.h, gtop_set_field_sign)."""
+        self._chk(self._L.gtop_set_field_sign(self._h, 1 if signed else 0, float(max_depth)))
+
+    def field_sign(self):
+        """(signed, max_depth) of the resident field."""
+        mode, depth = C.c_int(), C.c_double()
+        self._chk(self._L.gtop_get_field_sign(self._h, C.byref(mode), C.byref(depth)))
+        return bool(mode.value), depth.value
 
     def push_rows(self, src, dst_ptrs, nbytes=None, stream=None, clock_minmax=None):
         """ONE kernel copies `src` (a contiguous CUDA tensor, or its first nbytes) to every device address in dst_ptrs
@@ -677,6 +692,10 @@ class GtopGroup:
         d.update(kw)
         p = GtopParams(**d)
         self._chk(self._L.gtop_group_set_params(self._h, C.byref(p)))
+
+    def set_field_sign(self, signed=True, max_depth=0.0):
+        """GtopContext.set_field_sign on every member."""
+        self._chk(self._L.gtop_group_set_field_sign(self._h, 1 if signed else 0, float(max_depth)))
 
     def init_sdf_map(self, map_size, origin, resolution):
         self._chk(self._L.gtop_group_init_sdf_map(self._h, _p(_f64(map_size)), _p(_f64(origin)), float(resolution)))

@@ -19,7 +19,8 @@
 #include "gtop_guard.h"
 #include "gtop_kernels.h"
 
-#define GTOP_ABI_VERSION 2   // round 4: gtop_update_sdf_map_window*, gtop_set_field_precisions, gtop_device_clock_*, gtop_group_gather_note, GTOP_ERR_INTERNAL
+#define GTOP_ABI_VERSION 3   // 3: gtop_set_field_sign, gtop_get_field_sign, gtop_group_set_field_sign
+                             // 2: gtop_update_sdf_map_window*, gtop_set_field_precisions, gtop_device_clock_*, gtop_group_gather_note, GTOP_ERR_INTERNAL
 
 struct gtop_ctx {
   int device = 0;
@@ -51,6 +52,9 @@ struct gtop_ctx {
   bool rec32_stale = false;          // ... or must be rebuilt from sdf64 before the next fp32 use
   bool fp32_in_use = false;
   bool fp32_wanted = true;           // gtop_set_field_precisions: 0 = fp64 records only (fp32 evaluations refused)
+  // gtop_set_field_sign: the sign of the NEXT whole-map build (sign_next, depth_next) and of the resident field
+  int sign_next = 0, sign_field = 0;
+  double depth_next = 0.0, depth_field = 0.0;   // max_depth as given (0 = 10000)
 
   // ESDF construction workspace
   uint8_t *occ = nullptr;
@@ -290,6 +294,15 @@ int launch_eval(gtop_ctx *c, const R *sdf, int B, int m, const void *d_x, const 
   return GTOP_OK;
 }
 
+// the resident field takes the sign in force (a whole-map build, gtop_init_sdf_map, an upload)
+void take_field_sign(gtop_ctx *c) {
+  c->sign_field = c->sign_next;
+  c->depth_field = c->depth_next;
+}
+
+// what a signed build clamps occupied voxels to: max_depth, 0 meaning the reference's 10000
+double field_depth(double max_depth) { return max_depth == 0.0 ? 10000.0 : max_depth; }
+
 int check_eval_state(gtop_ctx *c) {
   if (!c->have_params) return fail(c, GTOP_ERR_STATE, "gtop_set_params has not been called");
   if (!c->have_grid) return fail(c, GTOP_ERR_STATE, "no distance field set");
@@ -373,6 +386,7 @@ int gtop_set_sdf(gtop_ctx *c, const double *dist_host, int nx, int ny, int nz,
   const size_t nvox = (size_t)nx * ny * nz;
   if ((rc = own_sdf_buffers(c, nvox))) { c->have_grid = false; return rc; }
   HIPCHK(c, hipMemcpyAsync(c->sdf64, dist_host, nvox * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  take_field_sign(c);   // (the library cannot tell what the values mean: the mode in force names them)
   if ((rc = build_records_on_stream(c, c->stream, c->fp32_in_use))) return rc;   // the upload transform
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return GTOP_OK;
@@ -388,6 +402,7 @@ int gtop_set_sdf_device(gtop_ctx *c, int dtype, const void *dist_dev, int nx, in
   if (rc) return rc;
   release_sdf(c);
   if ((rc = ensure_records(c))) { c->have_grid = false; return rc; }
+  take_field_sign(c);
   // The buffer is borrowed as the boundary copy (gtop_get_sdf and the coarse voxel query read it in place); the
   // corner records the lookups read are derived from it HERE — a caller that rewrites the buffer calls again.
   if (dtype == GTOP_F64) {
@@ -416,6 +431,7 @@ int gtop_init_sdf_map(gtop_ctx *c, const double map_size[3], const double origin
   if ((rc = ensure(c, &c->occ, &c->cap_occ, nvox))) return rc;
   // sdf_map.cpp:22-23: distance 10000, occupancy 0
   HIPCHK(c, gtop_launch_esdf_reset(c->occ, c->sdf64, nvox, c->stream));
+  take_field_sign(c);   // a whole-map build: the all-free field is the same in both modes
   if ((rc = build_records_on_stream(c, c->stream, c->fp32_in_use))) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return GTOP_OK;
@@ -437,7 +453,12 @@ static int update_sdf_map_on_stream(gtop_ctx *c, const double *d_pts, int npts, 
   // writes every voxel (10000 where the line holds no obstacle, as the reset would have left it)
   HIPCHK(c, gtop_launch_esdf_reset(c->occ, nullptr, nvox, s));
   HIPCHK(c, gtop_launch_esdf_mark(g, d_pts, npts, c->occ, s));         // setOccupancy
-  HIPCHK(c, gtop_launch_esdf_build(g, c->occ, c->tmp1, c->tmp2, c->rows, c->sdf64, nullptr, s));   // updateESDF3d
+  if (c->sign_next)   // the signed field (gtop_set_field_sign): a second transform fills the occupied voxels
+    HIPCHK(c, gtop_launch_esdf_build_signed(g, c->occ, c->tmp1, c->tmp2, c->rows, c->sdf64, nullptr,
+                                            field_depth(c->depth_next), s));
+  else
+    HIPCHK(c, gtop_launch_esdf_build(g, c->occ, c->tmp1, c->tmp2, c->rows, c->sdf64, nullptr, s));   // updateESDF3d
+  take_field_sign(c);
   // the corner records behind it, on the same stream (device-side: holds for graph replays too); the fp32 ones now
   // when they are wanted now, otherwise at the first fp32 evaluation (host-synchronous caller only, see gtop_ctx)
   return build_records_on_stream(c, s, convert_now || c->fp32_in_use);
@@ -489,6 +510,11 @@ static int update_window_on_stream(gtop_ctx *c, const double min_pos[3], const d
                                    int npts, hipStream_t s, bool convert_now) {
   const GtopGrid &g = c->grid;
   const size_t nvox = (size_t)g.nx * g.ny * g.nz;
+  // a window is built in the resident field's sign: one changed since needs a whole-map build first (never a field
+  // that is signed in some boxes only)
+  if (c->sign_next != c->sign_field || (c->sign_next && c->depth_next != c->depth_field))
+    return fail(c, GTOP_ERR_STATE, "update window: whole-map update needed after changing the field sign "
+                                   "(gtop_update_sdf_map*, gtop_init_sdf_map or gtop_set_sdf*)");
   int lo[3], hi[3];
   window_ids(g, min_pos, max_pos, lo, hi);
   int rc;
@@ -527,10 +553,18 @@ static int update_window_on_stream(gtop_ctx *c, const double min_pos[3], const d
     // need no reset: the scatter below rewrites every voxel of it
     (void)wx; (void)wy; (void)wz;
     HIPCHK(c, gtop_launch_esdf_window_reset_mark_compact(g, lo, hi, d_pts, npts, c->occ, c->win_occ, s));
-    HIPCHK(c, gtop_launch_esdf_build(sub, c->win_occ, c->tmp1, c->tmp2, c->rows, c->win_dist, nullptr, s));
+    if (c->sign_field)
+      HIPCHK(c, gtop_launch_esdf_build_signed(sub, c->win_occ, c->tmp1, c->tmp2, c->rows, c->win_dist, nullptr,
+                                              field_depth(c->depth_field), s));
+    else
+      HIPCHK(c, gtop_launch_esdf_build(sub, c->win_occ, c->tmp1, c->tmp2, c->rows, c->win_dist, nullptr, s));
     HIPCHK(c, gtop_launch_esdf_window_scatter(g, lo, hi, c->win_dist, c->sdf64, s));
   } else {
-    HIPCHK(c, gtop_launch_esdf_window_build(g, lo, hi, c->occ, c->tmp1, c->tmp2, c->sdf64, s));
+    if (c->sign_field)
+      HIPCHK(c, gtop_launch_esdf_window_build_signed(g, lo, hi, c->occ, c->tmp1, c->tmp2, c->sdf64,
+                                                     field_depth(c->depth_field), s));
+    else
+      HIPCHK(c, gtop_launch_esdf_window_build(g, lo, hi, c->occ, c->tmp1, c->tmp2, c->sdf64, s));
   }
   // Only the records that hold a voxel of the window change.  fp32 records that are current stay current (their window
   // is rebuilt in the same pass); stale ones cannot be made current by a window: they are rebuilt whole where this
@@ -569,6 +603,24 @@ int gtop_update_sdf_map_window_device(gtop_ctx *c, const double min_pos[3], cons
   return update_window_on_stream(c, min_pos, max_pos, static_cast<const double *>(d_pts), npts,
                                  static_cast<hipStream_t>(hip_stream), /*convert_now=*/true);
 } GTOP_CATCH_STATUS(c)
+
+int gtop_set_field_sign(gtop_ctx *c, int signed_mode, double max_depth) try {
+  if (!c) return GTOP_ERR_INVALID;
+  if (signed_mode != 0 && signed_mode != 1)
+    return fail(c, GTOP_ERR_INVALID, "field sign: signed_mode must be 0 (unsigned) or 1 (signed)");
+  if (!std::isfinite(max_depth) || max_depth < 0.0)
+    return fail(c, GTOP_ERR_INVALID, "field sign: max_depth must be finite and >= 0 (0 = 10000)");
+  c->sign_next = signed_mode;
+  c->depth_next = max_depth;
+  return GTOP_OK;
+} GTOP_CATCH_STATUS(c)
+
+int gtop_get_field_sign(const gtop_ctx *c, int *signed_mode, double *max_depth) {
+  if (!c) return GTOP_ERR_INVALID;
+  if (signed_mode) *signed_mode = c->sign_field;
+  if (max_depth) *max_depth = c->depth_field;
+  return GTOP_OK;
+}
 
 int gtop_get_sdf(gtop_ctx *c, double *dist_host, int grid_out[3]) try {
   if (!c) return GTOP_ERR_INVALID;

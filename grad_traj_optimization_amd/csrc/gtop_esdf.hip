@@ -87,9 +87,16 @@ esdf_mark_kernel(const GtopGrid g, const double *__restrict__ pts, int npts,
 // z sweep (sdf_map.cpp:311-326): one wavefront per (x,y) column.
 constexpr int kMaxChunks = 64;   // columns up to 4096 voxels
 
-__global__ void __launch_bounds__(256)
-esdf_z_kernel(const GtopGrid g, const uint8_t *__restrict__ occ, int *__restrict__ out, uint16_t *__restrict__ out16,
-              uint8_t *__restrict__ colany, int *__restrict__ n_empty_slabs) {
+// The seeds of a transform: the occupied voxels (the distance field), or — FREE, the signed field's second transform —
+// every voxel that is not occupied.  A template parameter: the predicate is fixed per instantiation, and the unsigned
+// kernels compile to what they were.
+template <bool FREE>
+__device__ __forceinline__ bool esdf_seed(uint8_t o) { return FREE ? o != 1 : o == 1; }
+
+template <bool FREE>
+__device__ __forceinline__ void esdf_z_body(const GtopGrid &g, const uint8_t *__restrict__ occ, int *__restrict__ out,
+                                            uint16_t *__restrict__ out16, uint8_t *__restrict__ colany,
+                                            int *__restrict__ n_empty_slabs) {
   if (blockIdx.x == 0 && threadIdx.x == 0) *n_empty_slabs = 0;   // counted by the y sweep / esdf_rows_kernel, read by the x sweep
   __shared__ unsigned long long masks[4][kMaxChunks];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -100,7 +107,7 @@ esdf_z_kernel(const GtopGrid g, const uint8_t *__restrict__ occ, int *__restrict
     unsigned long long any = 0ull;
     for (int k = 0; k < nchunk; ++k) {
       const int z = k * 64 + lane;
-      const bool o = (z < nz) && (c[z] == 1);
+      const bool o = (z < nz) && esdf_seed<FREE>(c[z]);
       const unsigned long long mk = __ballot(o);
       if (lane == 0) masks[w][k] = mk;
       any |= mk;
@@ -137,13 +144,27 @@ esdf_z_kernel(const GtopGrid g, const uint8_t *__restrict__ occ, int *__restrict
   }
 }
 
+__global__ void __launch_bounds__(256)
+esdf_z_kernel(const GtopGrid g, const uint8_t *__restrict__ occ, int *__restrict__ out, uint16_t *__restrict__ out16,
+              uint8_t *__restrict__ colany, int *__restrict__ n_empty_slabs) {
+  esdf_z_body<false>(g, occ, out, out16, colany, n_empty_slabs);
+}
+
+// the signed field's interior transform: seeds are the free voxels
+__global__ void __launch_bounds__(256)
+esdf_z_free_kernel(const GtopGrid g, const uint8_t *__restrict__ occ, int *__restrict__ out, uint16_t *__restrict__ out16,
+                   uint8_t *__restrict__ colany, int *__restrict__ n_empty_slabs) {
+  esdf_z_body<true>(g, occ, out, out16, colany, n_empty_slabs);
+}
+
 // The same for columns of up to 512 voxels (NCH <= 8 chunks of 64): the ballots stay in scalar registers, what the
 // other chunks contribute to a chunk (their highest occupied voxel below it, their lowest above it) is scalar
 // arithmetic done once per column, and a lane only searches its own chunk's mask (21 -> 18 us at 200^3).  What is
 // left is instruction issue — 160 VALU + 81 SALU per column, 39 columns per SIMD — not latency: four columns per
 // trip with all their loads issued first made it slower (20.6 us); storing the distance as a byte instead of its
 // square as an int made this sweep 2 us faster and the y sweep 2.4 us slower.
-template <int NCH>
+// FREE: the signed field's interior transform (seeds are the free voxels; esdf_seed)
+template <int NCH, bool FREE = false>
 __global__ void __launch_bounds__(256)
 esdf_z_small_kernel(const GtopGrid g, const uint8_t *__restrict__ occ, int *__restrict__ out, uint16_t *__restrict__ out16,
                     uint8_t *__restrict__ colany, int *__restrict__ n_empty_slabs) {
@@ -160,7 +181,7 @@ esdf_z_small_kernel(const GtopGrid g, const uint8_t *__restrict__ occ, int *__re
 #pragma unroll
     for (int k = 0; k < NCH; ++k) {
       const int z = k * 64 + lane;
-      mk[k] = __ballot((z < nz) && (c[z] == 1));
+      mk[k] = __ballot((z < nz) && esdf_seed<FREE>(c[z]));
       any |= mk[k];
       hi[k] = mk[k] ? k * 64 + 63 - __clzll((long long)mk[k]) : -kFar;
       lo[k] = mk[k] ? k * 64 + (__ffsll((long long)mk[k]) - 1) : kFar;
@@ -694,11 +715,22 @@ __device__ __forceinline__ int esdf_empty_run(const EsdfSlabRuns *sr, int n, int
   return __builtin_amdgcn_readfirstlane(min(runl, runr));
 }
 
+// The signed field's interior store (SIGNED instantiations of the x sweeps): the squared distance n to the nearest
+// FREE voxel becomes max(-D, res - res*sqrt(n)) at the occupied voxels — two roundings and a max, as numpy evaluates it
+// (the product and the difference are separate statements: -ffp-contract=on fuses within one expression only) — and
+// -D where the box holds no free voxel; every other voxel keeps the value of the first transform.
+__device__ __forceinline__ double esdf_interior(double res, double neg_depth, double root) {
+  const double r = res * root;
+  const double v = res - r;
+  return v > neg_depth ? v : neg_depth;
+}
+
 // the scan of one lane's block: V voxels from `first` (slab 0) times the kXB slabs from q0
-template <int V>
+template <int V, bool SIGNED = false>
 __device__ __forceinline__ void esdf_x_scan_block(const GtopGrid &g, const int *__restrict__ fin, double *__restrict__ dist,
                                                   float *__restrict__ dist32, const int first, const int q0,
-                                                  const EsdfSlabRuns *sr, const uint16_t *__restrict__ f16 = nullptr) {
+                                                  const EsdfSlabRuns *sr, const uint16_t *__restrict__ f16 = nullptr,
+                                                  const uint8_t *__restrict__ occ = nullptr, double neg_depth = 0.0) {
   constexpr int kScanBatch = 4;   // steps per round trip
   // f16 set (the packed x sweep's exact fallback, V = 4): the packed y sweep stores its int32 output only where the
   // 16-bit copy is saturated (whole wavefronts of it), so a row is read from the 16-bit copy — exact wherever it is
@@ -801,6 +833,14 @@ __device__ __forceinline__ void esdf_x_scan_block(const GtopGrid &g, const int *
     if (q0 + e >= n) break;
 #pragma unroll
     for (int v = 0; v < V; ++v) {
+      if constexpr (SIGNED) {
+        if (occ[row[e] + v] != 1) continue;   // a free voxel: the first transform's value stands
+        double dv = neg_depth;
+        if (best[e].v[v] < kInf) dv = esdf_interior(g.res, neg_depth, sqrt((double)best[e].v[v]));
+        dist[row[e] + v] = dv;
+        if (dist32) dist32[row[e] + v] = (float)dv;
+        continue;
+      }
       double dv = 10000.0;
       if (best[e].v[v] < kInf) {
         const double r = g.res * sqrt((double)best[e].v[v]);
@@ -863,6 +903,19 @@ esdf_x_kernel(const GtopGrid g, const int *__restrict__ fin, double *__restrict_
 #endif
 }
 
+// the signed field's interior pass: the same scan over the transform whose seeds are the free voxels, stored at the
+// occupied voxels only (esdf_interior)
+template <int V>
+__global__ void __launch_bounds__(256)
+esdf_x_signed_kernel(const GtopGrid g, const int *__restrict__ fin, double *__restrict__ dist, float *__restrict__ dist32,
+                     const int *__restrict__ cnt, const uint8_t *__restrict__ occ, double neg_depth) {
+  __shared__ EsdfSlabRuns s_runs;
+  const EsdfSlabRuns *sr = esdf_stage_slab_runs(&s_runs, cnt, g.nx) ? &s_runs : nullptr;
+  int fl, q0;
+  if (!esdf_x_lane(g.ny * g.nz / V, &fl, &q0)) return;
+  esdf_x_scan_block<V, true>(g, fin, dist, dist32, fl * V, q0, sr, nullptr, occ, neg_depth);
+}
+
 // The x sweep on packed 16-bit values.  Squared distances below 2^16 (255 voxels: 51 m at the reference's 0.2 m)
 // fit 16 bits, and the min-plus step on two voxels is then ONE v_pk_add_u16 (saturating) + ONE v_pk_min_u16 —
 // a third of the 32-bit form's instructions per candidate — and a 16-byte load brings 8 voxels.  The y sweep
@@ -903,12 +956,11 @@ __device__ __forceinline__ double esdf_sqrt_u16(int n) {
 #endif
 constexpr int kX16Block = GTOP_ESDF_X16_BLOCK;
 
-__global__ void __launch_bounds__(kX16Block)
-#ifdef GTOP_ESDF_X16_WPE
-__attribute__((amdgpu_waves_per_eu(GTOP_ESDF_X16_WPE)))
-#endif
-esdf_x16_kernel(const GtopGrid g, const uint16_t *__restrict__ f16, const int *__restrict__ fin,
-                double *__restrict__ dist, float *__restrict__ dist32, const int *__restrict__ cnt) {
+template <bool SIGNED>
+__device__ __forceinline__ void esdf_x16_body(const GtopGrid &g, const uint16_t *__restrict__ f16, const int *__restrict__ fin,
+                                              double *__restrict__ dist, float *__restrict__ dist32,
+                                              const int *__restrict__ cnt, const uint8_t *__restrict__ occ,
+                                              const double neg_depth) {
   __shared__ EsdfSlabRuns s_runs;
   const EsdfSlabRuns *sr = esdf_stage_slab_runs(&s_runs, cnt, g.nx) ? &s_runs : nullptr;
   constexpr int kScanBatch = GTOP_ESDF_X16_BATCH;
@@ -1006,8 +1058,8 @@ esdf_x16_kernel(const GtopGrid g, const uint16_t *__restrict__ f16, const int *_
     worst = worst_of();
   }
   if (__any(worst == 0xFFFF)) {   // (wave-uniform) a minimum at or past 2^16 - 1: the exact 32-bit scan instead
-    esdf_x_scan_block<4>(g, fin, dist, dist32, first, q0, sr, f16);
-    esdf_x_scan_block<4>(g, fin, dist, dist32, first + 4, q0, sr, f16);
+    esdf_x_scan_block<4, SIGNED>(g, fin, dist, dist32, first, q0, sr, f16, occ, neg_depth);
+    esdf_x_scan_block<4, SIGNED>(g, fin, dist, dist32, first + 4, q0, sr, f16, occ, neg_depth);
     return;
   }
 #ifdef GTOP_ESDF_STAMPS
@@ -1036,6 +1088,18 @@ esdf_x16_kernel(const GtopGrid g, const uint16_t *__restrict__ f16, const int *_
       const int v = 128 * k + 2 * ln;                            // voxel pair (v, v + 1) of the wavefront's chunk
       if (wave_base + v >= nyz) continue;                        // past the end of the plane (last chunk only)
       const int nn[2] = {(int)(pk & 0xFFFFu), (int)(pk >> 16)};
+      if constexpr (SIGNED) {   // the occupied voxels of the pair only (esdf_interior); every value here is finite
+        const uchar2 o = *reinterpret_cast<const uchar2 *>(occ + rowbase + v);
+        if (o.x == 1) {
+          dist[rowbase + v] = esdf_interior(g.res, neg_depth, esdf_sqrt_u16(nn[0]));
+          if (dist32) dist32[rowbase + v] = (float)dist[rowbase + v];
+        }
+        if (o.y == 1) {
+          dist[rowbase + v + 1] = esdf_interior(g.res, neg_depth, esdf_sqrt_u16(nn[1]));
+          if (dist32) dist32[rowbase + v + 1] = (float)dist[rowbase + v + 1];
+        }
+        continue;
+      }
       double2 dv;
       {
         const double r0 = g.res * esdf_sqrt_u16(nn[0]), r1 = g.res * esdf_sqrt_u16(nn[1]);
@@ -1049,6 +1113,23 @@ esdf_x16_kernel(const GtopGrid g, const uint16_t *__restrict__ f16, const int *_
 #ifdef GTOP_ESDF_STAMPS
   if (!getenv_stamp_y) esdf_stamp(t0, steps_done);
 #endif
+}
+
+__global__ void __launch_bounds__(kX16Block)
+#ifdef GTOP_ESDF_X16_WPE
+__attribute__((amdgpu_waves_per_eu(GTOP_ESDF_X16_WPE)))
+#endif
+esdf_x16_kernel(const GtopGrid g, const uint16_t *__restrict__ f16, const int *__restrict__ fin,
+                double *__restrict__ dist, float *__restrict__ dist32, const int *__restrict__ cnt) {
+  esdf_x16_body<false>(g, f16, fin, dist, dist32, cnt, nullptr, 0.0);
+}
+
+// the signed field's interior pass (see esdf_x_signed_kernel)
+__global__ void __launch_bounds__(kX16Block)
+esdf_x16_signed_kernel(const GtopGrid g, const uint16_t *__restrict__ f16, const int *__restrict__ fin,
+                       double *__restrict__ dist, float *__restrict__ dist32, const int *__restrict__ cnt,
+                       const uint8_t *__restrict__ occ, double neg_depth) {
+  esdf_x16_body<true>(g, f16, fin, dist, dist32, cnt, occ, neg_depth);
 }
 
 }  // namespace
@@ -1083,8 +1164,12 @@ size_t gtop_esdf_rows_ints(const GtopGrid &g) {
   return ((2 * ncol + (size_t)g.nx + 1 + (ncol + 3) / 4 + 3) & ~(size_t)3) + 2 * (((nvox + 1) / 2 + 3) & ~(size_t)3);   // (cnt: nx + 1)
 }
 
-hipError_t gtop_launch_esdf_build(const GtopGrid &g, const uint8_t *occ, int *tmp1, int *tmp2, int *rows,
-                                  double *dist, float *dist32, hipStream_t stream) {
+// One exact transform and its store.  FREE = false: seeds are the occupied voxels, every voxel gets
+// min(res*sqrt(n), 10000).  FREE = true (the signed field's second transform): seeds are the free voxels, and only the
+// occupied voxels are stored, as esdf_interior.  The y sweeps run unchanged on either.
+template <bool FREE>
+static hipError_t esdf_build_pass(const GtopGrid &g, const uint8_t *occ, int *tmp1, int *tmp2, int *rows, double *dist,
+                                  float *dist32, double neg_depth, hipStream_t stream) {
   const size_t ncol = (size_t)g.nx * g.ny;
   int *cols = rows, *rank = rows + ncol, *cnt = rows + 2 * ncol;
   uint8_t *colany = reinterpret_cast<uint8_t *>(rows + 2 * ncol + g.nx + 1);   // cnt[nx] = number of empty slabs
@@ -1104,17 +1189,19 @@ hipError_t gtop_launch_esdf_build(const GtopGrid &g, const uint8_t *occ, int *tm
   const bool y16k = GTOP_ESDF_Y16 && GTOP_ESDF_X16 && GTOP_ESDF_VEC == 4 && g.nz % 8 == 0;
   uint16_t *z16 = y16k ? z16_buf : (uint16_t *)nullptr;
   const unsigned zblocks = (unsigned)((ncol + 3) / 4 < 65536 ? (ncol + 3) / 4 : 65536);
+#define ZS(NCH) (esdf_z_small_kernel<NCH, FREE>)
   switch ((g.nz + 63) >> 6) {
-    case 1: hipLaunchKernelGGL(esdf_z_small_kernel<1>, dim3(zblocks), dim3(256), 0, stream, g, occ, tmp1, z16, colany, cnt + g.nx); break;
-    case 2: hipLaunchKernelGGL(esdf_z_small_kernel<2>, dim3(zblocks), dim3(256), 0, stream, g, occ, tmp1, z16, colany, cnt + g.nx); break;
-    case 3: hipLaunchKernelGGL(esdf_z_small_kernel<3>, dim3(zblocks), dim3(256), 0, stream, g, occ, tmp1, z16, colany, cnt + g.nx); break;
-    case 4: hipLaunchKernelGGL(esdf_z_small_kernel<4>, dim3(zblocks), dim3(256), 0, stream, g, occ, tmp1, z16, colany, cnt + g.nx); break;
-    case 5: hipLaunchKernelGGL(esdf_z_small_kernel<5>, dim3(zblocks), dim3(256), 0, stream, g, occ, tmp1, z16, colany, cnt + g.nx); break;
-    case 6: hipLaunchKernelGGL(esdf_z_small_kernel<6>, dim3(zblocks), dim3(256), 0, stream, g, occ, tmp1, z16, colany, cnt + g.nx); break;
-    case 7: hipLaunchKernelGGL(esdf_z_small_kernel<7>, dim3(zblocks), dim3(256), 0, stream, g, occ, tmp1, z16, colany, cnt + g.nx); break;
-    case 8: hipLaunchKernelGGL(esdf_z_small_kernel<8>, dim3(zblocks), dim3(256), 0, stream, g, occ, tmp1, z16, colany, cnt + g.nx); break;
-    default: hipLaunchKernelGGL(esdf_z_kernel, dim3(zblocks), dim3(256), 0, stream, g, occ, tmp1, z16, colany, cnt + g.nx);
+    case 1: hipLaunchKernelGGL(ZS(1), dim3(zblocks), dim3(256), 0, stream, g, occ, tmp1, z16, colany, cnt + g.nx); break;
+    case 2: hipLaunchKernelGGL(ZS(2), dim3(zblocks), dim3(256), 0, stream, g, occ, tmp1, z16, colany, cnt + g.nx); break;
+    case 3: hipLaunchKernelGGL(ZS(3), dim3(zblocks), dim3(256), 0, stream, g, occ, tmp1, z16, colany, cnt + g.nx); break;
+    case 4: hipLaunchKernelGGL(ZS(4), dim3(zblocks), dim3(256), 0, stream, g, occ, tmp1, z16, colany, cnt + g.nx); break;
+    case 5: hipLaunchKernelGGL(ZS(5), dim3(zblocks), dim3(256), 0, stream, g, occ, tmp1, z16, colany, cnt + g.nx); break;
+    case 6: hipLaunchKernelGGL(ZS(6), dim3(zblocks), dim3(256), 0, stream, g, occ, tmp1, z16, colany, cnt + g.nx); break;
+    case 7: hipLaunchKernelGGL(ZS(7), dim3(zblocks), dim3(256), 0, stream, g, occ, tmp1, z16, colany, cnt + g.nx); break;
+    case 8: hipLaunchKernelGGL(ZS(8), dim3(zblocks), dim3(256), 0, stream, g, occ, tmp1, z16, colany, cnt + g.nx); break;
+    default: hipLaunchKernelGGL((FREE ? esdf_z_free_kernel : esdf_z_kernel), dim3(zblocks), dim3(256), 0, stream, g, occ, tmp1, z16, colany, cnt + g.nx);
   }
+#undef ZS
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
 #ifndef GTOP_ESDF_YLOCAL
@@ -1163,6 +1250,19 @@ hipError_t gtop_launch_esdf_build(const GtopGrid &g, const uint8_t *occ, int *tm
 #undef GTOP_Y_LAUNCH
   e = hipGetLastError();
   if (e != hipSuccess) return e;
+  if constexpr (FREE) {
+    if (x16) {
+      hipLaunchKernelGGL(esdf_x16_signed_kernel, dim3(x_blocks(nyz >> 3, kX16Block)), dim3(kX16Block), 0, stream, g,
+                         (const uint16_t *)f16, (const int *)tmp2, dist, dist32, (const int *)cnt, occ, neg_depth);
+    } else if (V == 4)
+      hipLaunchKernelGGL(esdf_x_signed_kernel<4>, dim3(xblocks), dim3(256), 0, stream, g, (const int *)tmp2, dist, dist32,
+                         (const int *)cnt, occ, neg_depth);
+    else
+      hipLaunchKernelGGL(esdf_x_signed_kernel<1>, dim3(xblocks), dim3(256), 0, stream, g, (const int *)tmp2, dist, dist32,
+                         (const int *)cnt, occ, neg_depth);
+    return hipGetLastError();
+  }
+  (void)neg_depth;
   if (x16) {
     hipLaunchKernelGGL(esdf_x16_kernel, dim3(x_blocks(nyz >> 3, kX16Block)), dim3(kX16Block), 0, stream, g, (const uint16_t *)f16,
                        (const int *)tmp2, dist, dist32, (const int *)cnt);
@@ -1173,4 +1273,18 @@ hipError_t gtop_launch_esdf_build(const GtopGrid &g, const uint8_t *occ, int *tm
     hipLaunchKernelGGL(esdf_x_kernel<1>, dim3(xblocks), dim3(256), 0, stream, g, (const int *)tmp2, dist, dist32,
                        (const int *)cnt);
   return hipGetLastError();
+}
+
+hipError_t gtop_launch_esdf_build(const GtopGrid &g, const uint8_t *occ, int *tmp1, int *tmp2, int *rows,
+                                  double *dist, float *dist32, hipStream_t stream) {
+  return esdf_build_pass<false>(g, occ, tmp1, tmp2, rows, dist, dist32, 0.0, stream);
+}
+
+// The signed field: the distance field as above, then the transform whose seeds are the free voxels over the same
+// workspaces (the stream orders the passes), which overwrites the occupied voxels.
+hipError_t gtop_launch_esdf_build_signed(const GtopGrid &g, const uint8_t *occ, int *tmp1, int *tmp2, int *rows,
+                                         double *dist, float *dist32, double max_depth, hipStream_t stream) {
+  const hipError_t e = esdf_build_pass<false>(g, occ, tmp1, tmp2, rows, dist, dist32, 0.0, stream);
+  if (e != hipSuccess) return e;
+  return esdf_build_pass<true>(g, occ, tmp1, tmp2, rows, dist, dist32, -max_depth, stream);
 }

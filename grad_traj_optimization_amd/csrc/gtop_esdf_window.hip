@@ -54,9 +54,11 @@ window_reset_kernel(const GtopGrid g, const Window w, uint8_t *__restrict__ occ,
   dist[idx] = 10000.0;
 }
 
-// z sweep (:311-326) over z in [lo2, hi2]: squared distance to the nearest occupied voxel of the column segment
-__global__ void __launch_bounds__(256)
-window_z_kernel(const GtopGrid g, const Window w, const uint8_t *__restrict__ occ, int *__restrict__ out) {
+// z sweep (:311-326) over z in [lo2, hi2]: squared distance to the nearest occupied voxel of the column segment —
+// or, FREE (the signed field's interior transform), to the nearest voxel that is not occupied
+template <bool FREE>
+__device__ __forceinline__ void window_z_body(const GtopGrid &g, const Window &w, const uint8_t *__restrict__ occ,
+                                              int *__restrict__ out) {
   int x, y, z;
   size_t idx;
   if (!window_voxel(g, w, x, y, z, idx)) return;
@@ -64,12 +66,23 @@ window_z_kernel(const GtopGrid g, const Window w, const uint8_t *__restrict__ oc
   for (int d = 0;; ++d) {
     const bool below = z - d >= w.lo[2], above = z + d <= w.hi[2];
     if (!below && !above) break;
-    if ((below && occ[idx - d] == 1) || (above && occ[idx + d] == 1)) {
+    if (FREE ? ((below && occ[idx - d] != 1) || (above && occ[idx + d] != 1))
+             : ((below && occ[idx - d] == 1) || (above && occ[idx + d] == 1))) {
       best = d * d;
       break;
     }
   }
   out[idx] = best;
+}
+
+__global__ void __launch_bounds__(256)
+window_z_kernel(const GtopGrid g, const Window w, const uint8_t *__restrict__ occ, int *__restrict__ out) {
+  window_z_body<false>(g, w, occ, out);
+}
+
+__global__ void __launch_bounds__(256)
+window_z_free_kernel(const GtopGrid g, const Window w, const uint8_t *__restrict__ occ, int *__restrict__ out) {
+  window_z_body<true>(g, w, occ, out);
 }
 
 // y sweep (:328-345, STRIDE = nz, AXIS = 1) and x sweep (:347-363, STRIDE = ny nz, AXIS = 0; FINAL: res*sqrt, min with
@@ -109,6 +122,26 @@ window_scan_kernel(const GtopGrid g, const Window w, const int *__restrict__ in,
   } else {
     out[idx] = best;
   }
+}
+
+// The signed field's interior store (as gtop_esdf.hip's esdf_interior): at the window's occupied voxels, the squared
+// distance n to the nearest free voxel of the window becomes max(-D, res - res*sqrt(n)), two roundings and a max; -D
+// where the window holds no free voxel.  Free voxels keep the distance field's value.
+__global__ void __launch_bounds__(256)
+window_signed_store_kernel(const GtopGrid g, const Window w, const uint8_t *__restrict__ occ, const int *__restrict__ in,
+                           double *__restrict__ dist, double neg_depth) {
+  int x, y, z;
+  size_t idx;
+  if (!window_voxel(g, w, x, y, z, idx)) return;
+  if (occ[idx] != 1) return;
+  const int n = in[idx];
+  double dv = neg_depth;
+  if (n < kInf) {
+    const double r = g.res * sqrt((double)n);
+    const double v = g.res - r;
+    dv = v > neg_depth ? v : neg_depth;
+  }
+  dist[idx] = dv;
 }
 
 // The window's occupancy as a compact grid of its own, and the compact grid's distances back into the window: a
@@ -196,5 +229,22 @@ hipError_t gtop_launch_esdf_window_build(const GtopGrid &g, const int lo[3], con
   hipLaunchKernelGGL(window_z_kernel, grid, block, 0, stream, g, w, occ, tmp1);
   hipLaunchKernelGGL((window_scan_kernel<1, false>), grid, block, 0, stream, g, w, (const int *)tmp1, tmp2, dist);
   hipLaunchKernelGGL((window_scan_kernel<0, true>), grid, block, 0, stream, g, w, (const int *)tmp2, (int *)nullptr, dist);
+  return hipGetLastError();
+}
+
+// The signed field over the window: the distance field as above, then the transform whose seeds are the window's free
+// voxels (z, y and x sweeps; the x sweep keeps the squared distances) and the interior store at its occupied voxels.
+hipError_t gtop_launch_esdf_window_build_signed(const GtopGrid &g, const int lo[3], const int hi[3], const uint8_t *occ,
+                                                int *tmp1, int *tmp2, double *dist, double max_depth, hipStream_t stream) {
+  if (hi[0] < lo[0] || hi[1] < lo[1] || hi[2] < lo[2]) return hipSuccess;
+  hipError_t e = gtop_launch_esdf_window_build(g, lo, hi, occ, tmp1, tmp2, dist, stream);
+  if (e != hipSuccess) return e;
+  Window w{{lo[0], lo[1], lo[2]}, {hi[0], hi[1], hi[2]}};
+  const long long n = (long long)(hi[0] - lo[0] + 1) * (hi[1] - lo[1] + 1) * (hi[2] - lo[2] + 1);
+  const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+  hipLaunchKernelGGL(window_z_free_kernel, grid, block, 0, stream, g, w, occ, tmp1);
+  hipLaunchKernelGGL((window_scan_kernel<1, false>), grid, block, 0, stream, g, w, (const int *)tmp1, tmp2, dist);
+  hipLaunchKernelGGL((window_scan_kernel<0, false>), grid, block, 0, stream, g, w, (const int *)tmp2, tmp1, dist);
+  hipLaunchKernelGGL(window_signed_store_kernel, grid, block, 0, stream, g, w, occ, (const int *)tmp1, dist, -max_depth);
   return hipGetLastError();
 }

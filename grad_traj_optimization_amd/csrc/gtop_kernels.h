@@ -105,6 +105,11 @@ bool gtop_esdf_supported(const GtopGrid &g);
 size_t gtop_esdf_rows_ints(const GtopGrid &g);   // ints of row workspace the builder needs
 hipError_t gtop_launch_esdf_build(const GtopGrid &g, const uint8_t *occ, int *tmp1, int *tmp2, int *rows,
                                   double *dist, float *dist32, hipStream_t stream);
+// The signed field (gtop_set_field_sign): the distance field above at free voxels; at occupied ones
+// max(-max_depth, res - res*sqrt(n)), n the squared voxel distance to the nearest free voxel (-max_depth if none).
+// Two transforms over the same workspaces.
+hipError_t gtop_launch_esdf_build_signed(const GtopGrid &g, const uint8_t *occ, int *tmp1, int *tmp2, int *rows,
+                                         double *dist, float *dist32, double max_depth, hipStream_t stream);
 
 // the local update of compare2.cpp:147-152 (gtop_esdf_window.hip): resetBuffer(min, max) over the inclusive voxel box
 // lo .. hi, and updateESDF3d over the same box (sdf_map.cpp:28-53, :310-368)
@@ -112,6 +117,9 @@ hipError_t gtop_launch_esdf_window_reset(const GtopGrid &g, const int lo[3], con
                                          hipStream_t stream);
 hipError_t gtop_launch_esdf_window_build(const GtopGrid &g, const int lo[3], const int hi[3], const uint8_t *occ, int *tmp1,
                                          int *tmp2, double *dist, hipStream_t stream);
+// the same, signed (gtop_launch_esdf_build_signed over the window taken alone)
+hipError_t gtop_launch_esdf_window_build_signed(const GtopGrid &g, const int lo[3], const int hi[3], const uint8_t *occ,
+                                                int *tmp1, int *tmp2, double *dist, double max_depth, hipStream_t stream);
 // a compact grid's distances (z fastest) into the window
 hipError_t gtop_launch_esdf_window_scatter(const GtopGrid &g, const int lo[3], const int hi[3], const double *sub,
                                            double *dist, hipStream_t stream);

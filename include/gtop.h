@@ -77,7 +77,8 @@ int gtop_destroy(gtop_ctx *ctx);
 const char *gtop_last_error(const gtop_ctx *ctx);
 /* Library/ABI version, for the loader to check (2 since round 4: the windowed map
  * update, gtop_set_field_precisions, gtop_device_clock_*, gtop_group_gather_note,
- * GTOP_ERR_INTERNAL; nothing of version 1 changed meaning). */
+ * GTOP_ERR_INTERNAL; 3: the signed field, gtop_set_field_sign / gtop_get_field_sign /
+ * gtop_group_set_field_sign; nothing of an earlier version changed meaning). */
 int gtop_abi_version(void);
 
 /* ---- configuration -------------------------------------------------- */
@@ -150,6 +151,43 @@ int gtop_update_sdf_map_window_device(gtop_ctx *ctx, const double min_pos[3], co
                                       const void *d_obstacle_pts, int npts, void *hip_stream);
 /* Copy the resident fp64 distance field back to the host (nx*ny*nz doubles). */
 int gtop_get_sdf(gtop_ctx *ctx, double *dist_host, int grid_out[3]);
+
+/* ---- signed field (not in the reference) ----------------------------- */
+/* The field above is unsigned, as the reference's updateESDF3d
+ * (src/sdf_map.cpp:310-368): every occupied voxel holds 0, so inside a thick
+ * obstacle the lookup is a flat 0 with zero gradient and nothing pushes a
+ * trajectory out sideways.  signed_mode = 1 makes the map builds produce a
+ * SIGNED field instead.  With B the voxel box being built (the whole grid for
+ * gtop_update_sdf_map*, the window for gtop_update_sdf_map_window*, taken alone
+ * as always):
+ *   free voxel (occupancy 0)  min(res*sqrt(n+), 10000), as unsigned; n+ = squared
+ *                             voxel distance to the nearest occupied voxel of B
+ *   occupied voxel            max(-D, res - res*sqrt(n-)) in fp64, each step
+ *                             rounded (product, difference, max); n- = squared
+ *                             voxel distance to the nearest FREE voxel of B;
+ *                             -D when B holds no free voxel
+ * D = max_depth, 0 meaning 10000 (the mirror of the reference's cap).  An
+ * occupied voxel with a free face-neighbour gets exactly 0, the unsigned value:
+ * the two fields differ only at occupied voxels without a free 6-neighbour in B,
+ * and the signed one is continuous across the surface (distance + res inside).
+ * Mode 0 (unsigned) is the default; max_depth must be finite and >= 0
+ * (GTOP_ERR_INVALID otherwise).  The setting takes effect at the next WHOLE-MAP
+ * build (gtop_update_sdf_map*, gtop_init_sdf_map — whose all-free field is the
+ * same in both modes — or an upload); it does not rebuild the resident field.
+ * A windowed update while the setting differs from the resident field's
+ * (mode, or depth in signed mode) fails with GTOP_ERR_STATE and changes nothing.
+ * gtop_get_field_sign reports the RESIDENT field's mode and max_depth (as given);
+ * after gtop_set_sdf* that is the mode in force at the upload — the library
+ * cannot tell what uploaded values mean.
+ * Everything that reads the field (evaluations, the optimizer, the EDT queries)
+ * takes negative values as they are.  One limit: the collision penalty
+ * alpha*exp((d0 - d)/r) overflows once (d0 - d)/r passes about 88.7 in fp32
+ * (GTOP_F32 evaluations, gtop_set_optimizer_precision(GTOP_F32)) and about 709
+ * in fp64.  max_depth is the control: keep max_depth <= 80*r - d0 for fp32 use.
+ * With the default D = 10000 a box without any free voxel holds -10000 and the
+ * penalty there is inf even in fp64. */
+int gtop_set_field_sign(gtop_ctx *ctx, int signed_mode, double max_depth);
+int gtop_get_field_sign(const gtop_ctx *ctx, int *signed_mode, double *max_depth);
 
 /* Replaces the problem state setPath/setKinoPath leave in the object
  * (segment_time, Df; L and R follow from segment_time and are formed on the
@@ -292,6 +330,8 @@ const char *gtop_group_gather_backend(const gtop_group *g);
  * librccl.so not found: ..." — a fallback from RCCL to copies is never silent. */
 const char *gtop_group_gather_note(const gtop_group *g);
 int gtop_group_set_params(gtop_group *g, const gtop_params *p);
+/* gtop_set_field_sign on every member */
+int gtop_group_set_field_sign(gtop_group *g, int signed_mode, double max_depth);
 int gtop_group_init_sdf_map(gtop_group *g, const double map_size[3], const double origin[3], double resolution);
 int gtop_group_update_sdf_map(gtop_group *g, const double *pts, int npts);
 int gtop_group_update_sdf_map_window(gtop_group *g, const double min_pos[3], const double max_pos[3], const double *pts,

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Diagnostic: the local map update (gtop_update_sdf_map_window_device: reset + mark + the three sweeps over the box +
 the box's corner records) against the whole-map rebuild (gtop_update_sdf_map_device) on the bench maps.
-usage: tools/window_time.py [grid ...]   (default 200 400)"""
+--signed: the signed field (gtop_set_field_sign) in both.
+usage: tools/window_time.py [--signed] [grid ...]   (default 200 400)"""
 import os
 import sys
 
@@ -25,14 +26,17 @@ def timed(fn, reps=20):
     return e0.elapsed_time(e1) / reps * 1e3
 
 
-for g in [int(a) for a in sys.argv[1:]] or [200, 400]:
+signed = "--signed" in sys.argv
+for g in [int(a) for a in sys.argv[1:] if a != "--signed"] or [200, 400]:
     mp = problem.make_map(g, density=0.02 if g <= 200 else 0.04, seed=0)
     ctx = gtop.GtopContext(0)
+    if signed:
+        ctx.set_field_sign(True)
     ctx.init_sdf_map(mp.map_size, mp.origin, mp.resolution)
     pts = mp.obstacle_points()
     dp = torch.tensor(pts, device="cuda:0")
     full = timed(lambda: ctx.update_sdf_map_device(dp), 10)
-    print(f"grid {g}^3: whole-map rebuild (points resident, both record precisions) {full:.1f} us", flush=True)
+    print(f"grid {g}^3 ({'signed' if signed else 'unsigned'}): whole-map rebuild (points resident, both record precisions) {full:.1f} us", flush=True)
     centre = mp.origin + 0.5 * mp.map_size
     for box in ((10.0, 10.0, 5.0), (20.0, 20.0, 5.0), (20.0, 20.0, 20.0)):     # metres: a sensor's reach
         half = 0.5 * np.array(box)
