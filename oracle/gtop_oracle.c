@@ -367,6 +367,96 @@ double oracle_sdf_query(const oracle_sdf *S, const double pos[3],
   return dist;
 }
 
+/* Rounding-error magnitudes of oracle_sdf_query at the same position (see oracle_cost_grad_mag): *dmag bounds the
+ * value's arithmetic, gmag[k] the gradient's — corner values by magnitude, every difference of two corners as
+ * (|v1| + |v0|) (fp32 fields round the corners themselves), and the weights' own absolute error,
+ * (|pos| + |idx_pos|) / res + 1, times the value's (gradient's) exact sensitivity to that weight.
+ * margins: [0] distance of the cell coordinate (pos - res/2 - origin) / res to an integer (the floor of
+ * sdf_map.cpp:201-204), [1] distance of pos to the in-map bounds (:55-69); both relative to their magnitudes. */
+static void sdf_query_mag(const oracle_sdf *S, const double pos[3], double *dmag, double gmag[3],
+                          double margins[2], double dgdp[3][3]) {
+  for (int k = 0; k < 3; ++k) dgdp[k][0] = dgdp[k][1] = dgdp[k][2] = 0;
+  double mm = INFINITY;
+  for (int i = 0; i < 3; ++i) {
+    double lo = S->min_range[i] + 1e-4, hi = S->max_range[i] - 1e-4;
+    double sc = fabs(pos[i]) + fabs(S->min_range[i]) + fabs(S->max_range[i]) + 1e-4;
+    mm = fmin(mm, fmin(fabs(pos[i] - lo), fabs(pos[i] - hi)) / sc);
+  }
+  margins[1] = mm;
+  if (!sdf_in_map(S, pos)) {
+    *dmag = 1.0;
+    gmag[0] = gmag[1] = gmag[2] = 0.0;
+    margins[0] = INFINITY;
+    return;
+  }
+  double res = S->resolution, rinv = S->resolution_inv;
+  double diff[3], wm[3];
+  int idx[3];
+  double cm = INFINITY;
+  for (int i = 0; i < 3; ++i) {
+    double u = ((pos[i] - 0.5 * res) - S->origin[i]) * rinv;
+    idx[i] = (int)floor(u);
+    cm = fmin(cm, fabs(u - nearbyint(u)) / ((fabs(pos[i]) + fabs(S->origin[i]) + res) * rinv));
+    double ip = (idx[i] + 0.5) * res + S->origin[i];
+    diff[i] = (pos[i] - ip) * rinv;
+    wm[i] = (fabs(pos[i]) + fabs(ip)) * rinv + 1.0;
+  }
+  margins[0] = cm;
+  double v[8]; /* v[x*4 + y*2 + z] */
+  for (int c = 0; c < 8; c++) v[c] = sdf_get_distance(S, idx[0] + (c >> 2), idx[1] + ((c >> 1) & 1), idx[2] + (c & 1));
+  double w[3][2];
+  for (int i = 0; i < 3; ++i) {
+    w[i][0] = fabs(1 - diff[i]);
+    w[i][1] = fabs(diff[i]);
+  }
+  static const int bit[3] = {4, 2, 1};
+  double val = 0, d[3] = {0, 0, 0}, ds[3] = {0, 0, 0}, dd[3][3] = {{0}};
+  for (int c = 0; c < 8; c++) {
+    const int b[3] = {c >> 2, (c >> 1) & 1, c & 1};
+    val += w[0][b[0]] * w[1][b[1]] * w[2][b[2]] * fabs(v[c]);
+    for (int k = 0; k < 3; ++k) {
+      if (b[k]) continue;
+      const int o1 = (k + 1) % 3, o2 = (k + 2) % 3;
+      const double wo = w[o1][b[o1]] * w[o2][b[o2]];
+      d[k] += wo * (fabs(v[c + bit[k]]) + fabs(v[c]));  /* the difference's magnitude */
+      ds[k] += wo * fabs(v[c + bit[k]] - v[c]);         /* the value's sensitivity to weight k */
+      for (int j = 0; j < 3; ++j) {                      /* the k-gradient's sensitivity to weight j */
+        if (j == k || b[j]) continue;
+        const int l = 3 - j - k;
+        dd[k][j] += w[l][b[l]] * fabs((v[c + bit[k] + bit[j]] - v[c + bit[j]]) - (v[c + bit[k]] - v[c]));
+      }
+    }
+  }
+  *dmag = val + wm[0] * ds[0] + wm[1] * ds[1] + wm[2] * ds[2];
+  for (int k = 0; k < 3; ++k) {
+    double e = d[k];
+    for (int j = 0; j < 3; ++j)
+      if (j != k) {
+        e += wm[j] * dd[k][j];
+        dgdp[k][j] = dd[k][j] * rinv * rinv;   /* |d grad_k / d pos_j| */
+      }
+    gmag[k] = e * rinv;
+  }
+}
+
+/* pre-rounding doubles closer than FLIP_TAU * magnitude to a float rounding boundary may round either way in an
+ * implementation whose coefficients round differently (2^9 u64: the sample polynomial's ~25 u plus the 150 u of
+ * the sample times, see tests/test_gpu_entrywise.py) */
+#define FLIP_TAU 0x1p-44
+
+/* distance of a double to the nearest rounding boundary of (float), relative to `mag`.  With `noise` a value whose
+ * float spacing is below 2^-42 mag (a velocity that cancels to nearly nothing) is no decision: either rounding moves
+ * it by less than its own arithmetic's error at any kappa64 >= 2^11, which the magnitudes already carry (they take
+ * such values by their magnitude, not their size). */
+static double float_margin(double pre, double mag, int noise) {
+  float f = (float)pre;
+  if (!isfinite(f) || !(mag > 0)) return INFINITY;
+  double up = nextafterf(f, INFINITY), dn = nextafterf(f, -INFINITY);
+  if (noise && up - (double)f <= 0x1p-42 * mag) return INFINITY;
+  double hi = 0.5 * ((double)f + up), lo = 0.5 * ((double)f + dn);
+  return fmin(fabs(pre - hi), fabs(pre - lo)) / mag;
+}
+
 /* EDTEnvironment::distToBox / minDistToAllBox, src/edt_environment.cpp:26-73.
  * A box is {p0, vel, scale}: its centre at `time` is the constant-velocity
  * prediction p0 + vel*time (ObjPrediction::evaluateConstVel,
@@ -615,11 +705,13 @@ void oracle_esdf_build_window(const oracle_sdf *S, const double *occupancy,
 
 /* grad_traj_optimizer.cpp:281-432 with :253-279, :451-505, :507-551 and
  * sdf_map.cpp:185-242 underneath.  L: 6m×(3m+3), R: (3m+3)², Df: 3×6,
- * x/grad: 3·num_dp axis-major (:182-187, :428-432).  Returns the cost. */
-double oracle_cost_grad(int m, const double *L, const double *R,
-                        const double *Df, const double *T,
-                        const oracle_params *prm, const oracle_sdf *S,
-                        const double *x, double *grad_out) {
+ * x/grad: 3·num_dp axis-major (:182-187, :428-432).  Returns the cost.
+ * With mag != NULL also the rounding-error magnitudes and decision margins of
+ * oracle_cost_grad_mag (gtop_oracle.h). */
+static double cost_grad_impl(int m, const double *L, const double *R,
+                             const double *Df, const double *T,
+                             const oracle_params *prm, const oracle_sdf *S,
+                             const double *x, double *grad_out, double *mag) {
   const int num_df = 6, num_dp = 3 * m - 3, nd = num_df + num_dp, n6 = 6 * m;
   double cost_smooth = 0, cost_colli = 0, cost_vel = 0, cost_acc = 0;
   double *g_smooth = dalloc((size_t)3 * num_dp);
@@ -669,6 +761,47 @@ double oracle_cost_grad(int m, const double *L, const double *R,
     }
   }
 
+  /* magnitudes: |c| = |L||d|; smoothness ws·Σ|c|'Q|c| and 2ws|L|'Q|L||d| (the
+   * coefficient-space form, Q_s of qp_generator.cpp:226-234) */
+  double *cabs = NULL, *gm_s = NULL, *gm_c = NULL, *gm_v = NULL, *gm_a = NULL;
+  double cm_s = 0, cm_c = 0, cm_v = 0, cm_a = 0, fl_c = 0, fl_cd = 0;
+  double *fl_g = NULL, *fl_gd = NULL;
+  double mg_float = INFINITY, mg_cell = INFINITY, mg_map = INFINITY, mg_count = INFINITY;
+  if (mag) {
+    cabs = dalloc((size_t)m * 18);
+    gm_s = dalloc((size_t)3 * num_dp);
+    gm_c = dalloc((size_t)3 * num_dp);
+    gm_v = dalloc((size_t)3 * num_dp);
+    gm_a = dalloc((size_t)3 * num_dp);
+    fl_g = dalloc((size_t)3 * num_dp);
+    fl_gd = dalloc((size_t)3 * num_dp);
+    double *qc = dalloc((size_t)n6);
+    for (int a = 0; a < 3; ++a) {
+      const double *da = d + a * nd;
+      for (int r = 0; r < n6; ++r) {
+        double sm = 0;
+        for (int i = 0; i < nd; ++i) sm += fabs(L[r * nd + i]) * fabs(da[i]);
+        cabs[(r / 6) * 18 + 6 * a + (r % 6)] = sm;
+      }
+      for (int sg = 0; sg < m; ++sg) {
+        const double *cs = cabs + sg * 18 + 6 * a;
+        for (int i = 0; i < 6; ++i) {
+          double q = 0;
+          for (int j = 3; j < 6 && i >= 3; ++j)
+            q += (double)(i * (i - 1) * (i - 2) * j * (j - 1) * (j - 2) / (i + j - 5)) * pow(T[sg], i + j - 5) * cs[j];
+          qc[sg * 6 + i] = q;
+          cm_s += cs[i] * q;
+        }
+      }
+      for (int j = 0; j < num_dp; ++j) {
+        double sm = 0;
+        for (int r = 0; r < n6; ++r) sm += fabs(L[r * nd + 6 + j]) * qc[r];
+        gm_s[a * num_dp + j] = 2 * sm;
+      }
+    }
+    free(qc);
+  }
+
   double *Ldp = dalloc((size_t)6 * num_dp);
   for (int s = 0; s < m; s++) {
     if (fabs(prm->wc) < 1e-4) break; /* :346 */
@@ -677,17 +810,34 @@ double oracle_cost_grad(int m, const double *L, const double *R,
         Ldp[r * num_dp + c] = L[(6 * s + r) * nd + 6 + c];
     double dt = T[s] / 30.0; /* :351 */
     const double *c = coe + s * 18;
-    for (double t = 1e-3; t < T[s]; t += dt) { /* :353 */
+    double t = 1e-3, t_in = 0;
+    for (; t < T[s]; t += dt) { /* :353 */
+      t_in = t;
       /* :451-468, :471-488 — note the float locals */
-      double pos[3], vel[3], acc[3];
+      double pos[3], vel[3], acc[3], pmag[3], vmag[3], amag[3], pflip[3] = {0, 0, 0}, vflip[3] = {0, 0, 0};
       for (int a = 0; a < 3; ++a) {
         const double *q = c + 6 * a;
-        float p = q[0] + q[1] * t + q[2] * pow(t, 2) + q[3] * pow(t, 3) +
-                  q[4] * pow(t, 4) + q[5] * pow(t, 5);
-        float v = q[1] + 2 * q[2] * pow(t, 1) + 3 * q[3] * pow(t, 2) +
-                  4 * q[4] * pow(t, 3) + 5 * q[5] * pow(t, 4);
+        double pd = q[0] + q[1] * t + q[2] * pow(t, 2) + q[3] * pow(t, 3) +
+                    q[4] * pow(t, 4) + q[5] * pow(t, 5);
+        double vd = q[1] + 2 * q[2] * pow(t, 1) + 3 * q[3] * pow(t, 2) +
+                    4 * q[4] * pow(t, 3) + 5 * q[5] * pow(t, 4);
+        float p = pd;
+        float v = vd;
         pos[a] = p;
         vel[a] = v;
+        if (mag) {
+          const double *qa = cabs + s * 18 + 6 * a;
+          pmag[a] = vmag[a] = amag[a] = 0;
+          for (int i = 0; i < 6; ++i) {
+            pmag[a] += qa[i] * pow(t, i);
+            if (i >= 1) vmag[a] += i * qa[i] * pow(t, i - 1);
+            if (i >= 2) amag[a] += i * (i - 1) * qa[i] * pow(t, i - 2);
+          }
+          const double mp_ = float_margin(pd, pmag[a], 0), mv_ = float_margin(vd, vmag[a], 1);
+          mg_float = fmin(mg_float, fmin(mp_, mv_));
+          pflip[a] = mp_ < FLIP_TAU ? (double)nextafterf(p, INFINITY) - (double)p : 0;
+          vflip[a] = mv_ < FLIP_TAU ? (double)nextafterf(fabsf(v), INFINITY) - (double)fabsf(v) : 0;
+        }
       }
       double vel_norm =
           sqrt(vel[0] * vel[0] + vel[1] * vel[1] + vel[2] * vel[2]) + 1e-5;
@@ -707,6 +857,51 @@ double oracle_cost_grad(int m, const double *L, const double *R,
 
       cost_colli += cd * vel_norm * dt; /* :373 */
 
+      double w1m[3] = {0, 0, 0}, w2m[3] = {0, 0, 0};
+      if (mag) {
+        double dm, gm[3], mgs[2], dgdp[3][3];
+        sdf_query_mag(S, pos, &dm, gm, mgs, dgdp);
+        mg_cell = fmin(mg_cell, mgs[0]);
+        mg_map = fmin(mg_map, mgs[1]);
+        /* the exp argument's absolute error, in units of u: (|dist| + |d0|) / r */
+        const double ec = 1 + (dm + fabs(prm->d0)) / fabs(prm->r);
+        cm_c += fabs(cd) * ec * vel_norm * dt;
+        for (int k = 0; k < 3; ++k) {
+          w1m[k] = fabs(gd * cd * vel_norm) * (gm[k] + 2 * fabs(grad[k]) * ec);
+          w2m[k] = fabs(cd) * ec * vmag[k] / vel_norm;   /* the velocity by its magnitude */
+        }
+        /* a coordinate whose float rounding can go either way (pre-rounding double within FLIP_TAU of its
+         * magnitude from a rounding boundary): twice the first-order effect of one float step, absolute */
+        double f1[3] = {0, 0, 0}, f2[3] = {0, 0, 0}, fc = 0;
+        for (int j = 0; j < 3; ++j) {
+          if (pflip[j] > 0) {
+            const double dd = fabs(grad[j]) * pflip[j], rel = dd / fabs(prm->r);
+            fc += fabs(cd) * rel * vel_norm;
+            for (int k = 0; k < 3; ++k) {
+              f1[k] += fabs(gd * cd * vel_norm) * (2 * fabs(grad[k]) * rel + dgdp[k][j] * pflip[j]);
+              f2[k] += fabs(cd) * rel * fabs(vel[k]) / vel_norm;
+            }
+          }
+          if (vflip[j] > 0) {
+            const double dvn = fabs(vel[j]) * vflip[j] / vel_norm;
+            fc += fabs(cd) * dvn;
+            for (int k = 0; k < 3; ++k) {
+              f1[k] += fabs(gd * grad[k] * cd) * dvn;
+              f2[k] += fabs(cd) * (fabs(vel[k]) * dvn / vel_norm + (k == j ? vflip[j] / vel_norm : 0));
+            }
+          }
+        }
+        if (fc > 0) {
+          fl_c += 2 * fc * dt;
+          for (int k = 0; k < 3; ++k)
+            for (int cc = 0; cc < num_dp; ++cc) {
+              double b = 0;
+              for (int i = 0; i < 6; ++i) b += (f1[k] * Tm[i] + f2[k] * TV[i]) * fabs(Ldp[i * num_dp + cc]);
+              fl_g[k * num_dp + cc] += 2 * b * dt;
+            }
+        }
+      }
+
       for (int k = 0; k < 3; k++) { /* :376-381 */
         double s1 = gd * grad[k] * cd * vel_norm;
         double s2 = cd * (vel[k] / vel_norm);
@@ -718,24 +913,57 @@ double oracle_cost_grad(int m, const double *L, const double *R,
           }
           g_colli[k * num_dp + cc] =
               g_colli[k * num_dp + cc] + (a1 + a2) * dt;
+          if (mag) {
+            double b = 0;
+            for (int i = 0; i < 6; ++i)
+              b += (w1m[k] * Tm[i] + w2m[k] * TV[i]) * fabs(Ldp[i * num_dp + cc]);
+            gm_c[k * num_dp + cc] += b * dt;
+          }
         }
       }
 
       /* dynamic-feasibility block, commented out in the reference
        * (:383-407); executed here only when enable_dyn != 0. */
       if (prm->enable_dyn && prm->step == 2) {
-        double cv = 0, ca = 0, gv = 0, ga = 0;
+        double cv = 0, ca = 0, gv = 0, ga = 0, aflip[3] = {0, 0, 0};
         for (int a = 0; a < 3; ++a) { /* :491-505 */
           const double *q = c + 6 * a;
-          float ac = 2 * q[2] + 6 * q[3] * pow(t, 1) + 12 * q[4] * pow(t, 2) +
-                     20 * q[5] * pow(t, 3);
+          double ad = 2 * q[2] + 6 * q[3] * pow(t, 1) + 12 * q[4] * pow(t, 2) +
+                      20 * q[5] * pow(t, 3);
+          float ac = ad;
           acc[a] = ac;
+          if (mag) {
+            const double ma_ = float_margin(ad, amag[a], 1);
+            mg_float = fmin(mg_float, ma_);
+            aflip[a] = ma_ < FLIP_TAU ? (double)nextafterf(fabsf(ac), INFINITY) - (double)fabsf(ac) : 0;
+          }
+        }
+        double ev[3], ea[3];
+        if (mag)
+          for (int k = 0; k < 3; ++k) {
+            ev[k] = 1 + (vmag[k] + fabs(prm->v0)) / fabs(prm->r_v);
+            ea[k] = 1 + (amag[k] + fabs(prm->a0)) / fabs(prm->r_a);
+          }
+        /* the flip allowance through the exponentials: one float step of |v_k| / |a_k| moves the exponent by
+         * step / r, one of any velocity moves vn */
+        double fv[3] = {0, 0, 0}, fa[3] = {0, 0, 0}, dvr = 0;
+        if (mag) {
+          for (int k = 0; k < 3; ++k) {
+            fv[k] = vflip[k] / fabs(prm->r_v);
+            fa[k] = aflip[k] / fabs(prm->r_a);
+            dvr += fabs(vel[k]) * vflip[k] / (vel_norm * vel_norm);
+          }
         }
         for (int k = 0; k < 3; k++) {
           cv = prm->alpha_v * exp((fabs(vel[k]) - prm->v0) / prm->r_v); /* :519 */
           cost_vel += cv * vel_norm * dt;
           ca = prm->alpha_a * exp((fabs(acc[k]) - prm->a0) / prm->r_a); /* :529 */
           cost_acc += ca * vel_norm * dt;
+          if (mag) {
+            cm_v += fabs(cv) * ev[k] * vel_norm * dt;
+            cm_a += fabs(ca) * ea[k] * vel_norm * dt;
+            fl_cd += 2 * (fabs(cv) * (fv[k] + dvr) + fabs(ca) * (fa[k] + dvr)) * vel_norm * dt;
+          }
         }
         for (int k = 0; k < 3; k++) {
           gv = (prm->alpha_v / prm->r_v) *
@@ -755,9 +983,36 @@ double oracle_cost_grad(int m, const double *L, const double *R,
             }
             g_vel[k * num_dp + cc] += (a1 + a2) * dt;
             g_acc[k * num_dp + cc] += (a3 + a4) * dt;
+            if (mag) {
+              /* cv / ca: the last axis's values (the reference's loop variables) */
+              double m1 = fabs(s1) * ev[k], m3 = fabs(s3) * ea[k];
+              double m2 = fabs(cv) * ev[2] * vmag[k] / vel_norm, m4 = fabs(ca) * ea[2] * vmag[k] / vel_norm;
+              double b1 = 0, b2 = 0;
+              for (int i = 0; i < 6; ++i) {
+                double l = fabs(Ldp[i * num_dp + cc]);
+                b1 += (m1 + m2) * TV[i] * l;
+                b2 += (m3 * TVV[i] + m4 * TV[i]) * l;
+              }
+              gm_v[k * num_dp + cc] += b1 * dt;
+              gm_a[k * num_dp + cc] += b2 * dt;
+              if (dvr > 0 || fv[k] > 0 || fa[k] > 0 || fv[2] > 0 || fa[2] > 0 || vflip[k] > 0) {
+                const double e1 = fabs(s1) * (fv[k] + dvr), e3 = fabs(s3) * (fa[k] + dvr);
+                const double e2 = fabs(cv) * (fabs(vel[k]) * (fv[2] + 2 * dvr) + vflip[k]) / vel_norm;
+                const double e4 = fabs(ca) * (fabs(vel[k]) * (fa[2] + 2 * dvr) + vflip[k]) / vel_norm;
+                double b3 = 0;
+                for (int i = 0; i < 6; ++i)
+                  b3 += ((e1 + e2 + e4) * TV[i] + e3 * TVV[i]) * fabs(Ldp[i * num_dp + cc]);
+                fl_gd[k * num_dp + cc] += 2 * b3 * dt;
+              }
+            }
           }
         }
       }
+    }
+    /* the `t < T` test: the last t inside and the first outside the bound */
+    if (mag) {
+      if (t_in > 0) mg_count = fmin(mg_count, fabs(T[s] - t_in) / T[s]);
+      mg_count = fmin(mg_count, fabs(t - T[s]) / T[s]);
     }
   }
 
@@ -773,6 +1028,30 @@ double oracle_cost_grad(int m, const double *L, const double *R,
           (ws * g_smooth[a * num_dp + i] + wc * g_colli[a * num_dp + i] +
            wv * g_vel[a * num_dp + i] + wa * g_acc[a * num_dp + i]) +
           1e-5;
+  if (mag) {
+    const double wsm = fabs(ws), wcm = fabs(wc);
+    mag[0] = wsm * cm_s + wcm * cm_c + cm_v + cm_a + 1e-3;
+    for (int a = 0; a < 3; ++a)
+      for (int i = 0; i < num_dp; ++i)
+        mag[1 + i + num_dp * a] = wsm * gm_s[a * num_dp + i] + wcm * gm_c[a * num_dp + i] +
+                                  gm_v[a * num_dp + i] + gm_a[a * num_dp + i] + 1e-5;
+    double *mg = mag + 1 + 3 * num_dp;
+    mg[0] = mg_float;
+    mg[1] = mg_cell;
+    mg[2] = mg_map;
+    mg[3] = mg_count;
+    double *fl = mg + 4;
+    fl[0] = wcm * fl_c + fl_cd;
+    for (int a = 0; a < 3; ++a)   /* (grad's layout: i + num_dp * a, as the accumulators') */
+      for (int i = 0; i < num_dp; ++i) fl[1 + i + num_dp * a] = wcm * fl_g[a * num_dp + i] + fl_gd[a * num_dp + i];
+    free(fl_g);
+    free(fl_gd);
+    free(cabs);
+    free(gm_s);
+    free(gm_c);
+    free(gm_v);
+    free(gm_a);
+  }
 
   free(g_smooth);
   free(g_colli);
@@ -783,6 +1062,20 @@ double oracle_cost_grad(int m, const double *L, const double *R,
   free(tmp);
   free(Ldp);
   return cost;
+}
+
+double oracle_cost_grad(int m, const double *L, const double *R,
+                        const double *Df, const double *T,
+                        const oracle_params *prm, const oracle_sdf *S,
+                        const double *x, double *grad_out) {
+  return cost_grad_impl(m, L, R, Df, T, prm, S, x, grad_out, NULL);
+}
+
+double oracle_cost_grad_mag(int m, const double *L, const double *R,
+                            const double *Df, const double *T,
+                            const oracle_params *prm, const oracle_sdf *S,
+                            const double *x, double *grad_out, double *mag) {
+  return cost_grad_impl(m, L, R, Df, T, prm, S, x, grad_out, mag);
 }
 
 static double now_s(void) {
@@ -797,10 +1090,10 @@ static double now_s(void) {
  * grad_traj_optimizer.cpp:88-98) is done first and NOT timed; `reps`
  * passes of the callback over all B trajectories are timed.
  * Returns seconds spent in the callbacks (all reps), or <0 on error. */
-double oracle_eval_batch(int B, int m, const double *T, int t_stride,
-                         const double *Df, const oracle_params *prm,
-                         const oracle_sdf *S, const double *x, double *cost,
-                         double *grad, int reps, int nthreads) {
+static double eval_batch_impl(int B, int m, const double *T, int t_stride,
+                              const double *Df, const oracle_params *prm,
+                              const oracle_sdf *S, const double *x, double *cost,
+                              double *grad, double *mag, int reps, int nthreads) {
   int nd = 3 * m + 3, n6 = 6 * m, n = 9 * (m - 1);
   size_t lsz = (size_t)n6 * nd, rsz = (size_t)nd * nd;
   int nprob = t_stride ? B : 1;
@@ -823,15 +1116,30 @@ double oracle_eval_batch(int B, int m, const double *T, int t_stride,
 #endif
     for (int b = 0; b < B; ++b) {
       int p = t_stride ? b : 0;
-      cost[b] = oracle_cost_grad(m, Ls + lsz * p, Rs + rsz * p,
-                                 Df + (size_t)b * 18, T + (size_t)b * t_stride,
-                                 prm, S, x + (size_t)b * n, grad + (size_t)b * n);
+      cost[b] = cost_grad_impl(m, Ls + lsz * p, Rs + rsz * p,
+                               Df + (size_t)b * 18, T + (size_t)b * t_stride,
+                               prm, S, x + (size_t)b * n, grad + (size_t)b * n,
+                               mag ? mag + (size_t)b * (2 * n + 6) : NULL);
     }
   }
   double t1 = now_s();
   free(Ls);
   free(Rs);
   return t1 - t0;
+}
+
+double oracle_eval_batch(int B, int m, const double *T, int t_stride,
+                         const double *Df, const oracle_params *prm,
+                         const oracle_sdf *S, const double *x, double *cost,
+                         double *grad, int reps, int nthreads) {
+  return eval_batch_impl(B, m, T, t_stride, Df, prm, S, x, cost, grad, NULL, reps, nthreads);
+}
+
+double oracle_eval_batch_mag(int B, int m, const double *T, int t_stride,
+                             const double *Df, const oracle_params *prm,
+                             const oracle_sdf *S, const double *x, double *cost,
+                             double *grad, double *mag, int nthreads) {
+  return eval_batch_impl(B, m, T, t_stride, Df, prm, S, x, cost, grad, mag, 1, nthreads);
 }
 
 /* ------------------------------------------------------------------ */

@@ -72,6 +72,30 @@ double oracle_eval_batch(int B, int m, const double *T, int t_stride,
                          const oracle_sdf *S, const double *x, double *cost,
                          double *grad, int reps, int nthreads);
 
+/* oracle_cost_grad plus, in mag[0 .. 2n + 5] (n = 9(m-1)), the callback re-evaluated as an a-priori rounding-error
+ * magnitude — absolute values of the inputs, additions for subtractions, sums of products of magnitudes — and the
+ * narrowest margin of each discrete decision:
+ *   mag[0]        Cmag, mag[1 + k] Gmag[k] (same layout as grad): an implementation that rounds differently but
+ *                 takes the same decisions differs from the exact callback by a small multiple of u * magnitude;
+ *   mag[n + 1]    float rounding of a sample's position / velocity (/ acceleration with the dyn block): distance
+ *                 of the double to the nearest float rounding boundary, relative to its magnitude;
+ *   mag[n + 2]    cell choice (sdf_map.cpp:201-204): distance of the cell coordinate to an integer, relative;
+ *   mag[n + 3]    in-map test (:55-69): distance to min_range + 1e-4 / max_range - 1e-4, relative;
+ *   mag[n + 4]    sample count (grad_traj_optimizer.cpp:353): distance of the last tested t to T, relative to T;
+ *   mag[n + 5]    Cflip, mag[n + 6 + k] Gflip[k]: absolute allowance for the sample positions / velocities whose
+ *                 float rounding can go either way (pre-rounding double within 2^-44 of its magnitude from a
+ *                 rounding boundary) — twice the first-order effect of one float step of each such coordinate.
+ * Margins with no sample to test are +inf. */
+double oracle_cost_grad_mag(int m, const double *L, const double *R,
+                            const double *Df, const double *T,
+                            const oracle_params *prm, const oracle_sdf *S,
+                            const double *x, double *grad_out, double *mag);
+/* the batch driver with mag: B x (2n + 6), one row per trajectory as above */
+double oracle_eval_batch_mag(int B, int m, const double *T, int t_stride,
+                             const double *Df, const oracle_params *prm,
+                             const oracle_sdf *S, const double *x, double *cost,
+                             double *grad, double *mag, int nthreads);
+
 void oracle_traj_stats(int m, const double *coeff, const double *T, double dt_sample, double *out);
 /* PolynomialTraj::getTraj (polynomial_traj.hpp:69-78): returns the number of points, stores the first max_samples */
 int oracle_traj_samples(int m, const double *coeff, const double *T, double dt_sample, int max_samples,

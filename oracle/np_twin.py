@@ -12,6 +12,15 @@ import math
 
 import numpy as np
 
+# the reference's float locals (grad_traj_optimizer.cpp:457-465, :477-485) and its two "+1e-5" constants (:358,
+# :425-432) — module attributes, so that tests can evaluate deliberately wrong variants of the callback
+def to_float(v):
+    return np.float64(np.float32(v))
+
+
+VN_EPS = 1e-5
+GRAD_EPS = 1e-5
+
 
 def segment_time(path, mean_v, init_time):
     """src/grad_traj_optimizer.cpp:73-81 (last segment gets no init_time)."""
@@ -219,10 +228,10 @@ def cost_grad(T, Df, x, sdf, p, gen=None):
                 pv = c[0] + c[1] * t + c[2] * math.pow(t, 2) + c[3] * math.pow(t, 3) + c[4] * math.pow(t, 4) + c[5] * math.pow(t, 5)
                 vv = c[1] + 2 * c[2] * math.pow(t, 1) + 3 * c[3] * math.pow(t, 2) + 4 * c[4] * math.pow(t, 3) + 5 * c[5] * math.pow(t, 4)
                 av = 2 * c[2] + 6 * c[3] * math.pow(t, 1) + 12 * c[4] * math.pow(t, 2) + 20 * c[5] * math.pow(t, 3)
-                pos[a] = np.float64(np.float32(pv))
-                vel[a] = np.float64(np.float32(vv))
-                acc[a] = np.float64(np.float32(av))
-            vn = math.sqrt(vel[0] * vel[0] + vel[1] * vel[1] + vel[2] * vel[2]) + 1e-5   # :358
+                pos[a] = to_float(pv)
+                vel[a] = to_float(vv)
+                acc[a] = to_float(av)
+            vn = math.sqrt(vel[0] * vel[0] + vel[1] * vel[1] + vel[2] * vel[2]) + VN_EPS   # :358
             dist, g = sdf.query(pos)                                        # :363
             e = math.exp(-(dist - p["d0"]) / p["r"])
             cd = p["alpha"] * e                                             # :509
@@ -248,5 +257,5 @@ def cost_grad(T, Df, x, sdf, p, gen=None):
 
     ws = 0.0 if p["step"] == 1 else p["ws"]                                 # :412-415
     cost = ws * cost_smooth + p["wc"] * cost_colli + cost_vel + cost_acc + 1e-3     # :417-418
-    grad = (ws * g_smooth + p["wc"] * g_colli + g_vel + g_acc) + 1e-5       # :425-432
+    grad = (ws * g_smooth + p["wc"] * g_colli + g_vel + g_acc) + GRAD_EPS  # :425-432
     return cost, grad.reshape(-1), dict(coe=coe, nsamples=nsamples, cost_smooth=cost_smooth, cost_colli=cost_colli)

@@ -88,6 +88,12 @@ def lib():
                                         C.POINTER(OracleParams), C.POINTER(OracleSdf),
                                         dp, dp, dp, C.c_int, C.c_int]
         L.oracle_eval_batch.restype = C.c_double
+        L.oracle_cost_grad_mag.argtypes = [C.c_int, dp, dp, dp, dp, C.POINTER(OracleParams),
+                                           C.POINTER(OracleSdf), dp, dp, dp]
+        L.oracle_cost_grad_mag.restype = C.c_double
+        L.oracle_eval_batch_mag.argtypes = [C.c_int, C.c_int, dp, C.c_int, dp, C.POINTER(OracleParams),
+                                            C.POINTER(OracleSdf), dp, dp, dp, dp, C.c_int]
+        L.oracle_eval_batch_mag.restype = C.c_double
         L.oracle_traj_stats.argtypes = [C.c_int, dp, dp, C.c_double, dp]
         L.oracle_traj_stats.restype = None
         L.oracle_traj_samples.argtypes = [C.c_int, dp, dp, C.c_double, C.c_int, dp]
@@ -272,6 +278,36 @@ def eval_batch(T, Df, x, sdf, params, reps=1, nthreads=1):
     if sec < 0:
         raise ValueError("oracle_eval_batch failed")
     return cost, grad, sec
+
+
+MARGINS = ("float rounding", "cell choice", "in-map test", "sample count")
+
+
+def eval_batch_mag(T, Df, x, sdf, params, nthreads=1):
+    """eval_batch plus the rounding-error magnitudes and decision margins of oracle_cost_grad_mag (gtop_oracle.h).
+    Returns cost (B,), grad (B, n), Cmag (B,), Gmag (B, n), margins (B, 4) in the order of MARGINS, and the absolute
+    allowance for sample coordinates whose float rounding can go either way: Cflip (B,), Gflip (B, n)."""
+    x = _f64(x)
+    B, n = x.shape
+    m = n // 9 + 1
+    T = _f64(T)
+    stride = m if T.ndim == 2 else 0
+    Df = _f64(Df).reshape(B, 18)
+    cost = np.zeros(B)
+    grad = np.zeros((B, n))
+    mag = np.zeros((B, 2 * n + 6))
+    sec = lib().oracle_eval_batch_mag(B, m, _p(T), stride, _p(Df), C.byref(params), C.byref(sdf.c), _p(x),
+                                      _p(cost), _p(grad), _p(mag), nthreads)
+    if sec < 0:
+        raise ValueError("oracle_eval_batch_mag failed")
+    return (cost, grad, mag[:, 0].copy(), mag[:, 1:n + 1].copy(), mag[:, n + 1:n + 5].copy(), mag[:, n + 5].copy(),
+            mag[:, n + 6:].copy())
+
+
+def cost_grad_mag(T, Df, x, sdf, params):
+    """cost_grad of one trajectory with its magnitudes: (cost, grad, Cmag, Gmag, margins, Cflip, Gflip)."""
+    out = eval_batch_mag(_f64(T).reshape(-1), _f64(Df).reshape(1, 18), _f64(x).reshape(1, -1), sdf, params)
+    return tuple(a[0] for a in out)
 
 
 _opt_lib = None
