@@ -104,6 +104,10 @@ def load_library():
         "gtop_eval_trajectories_device": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_double, vp, vp]),
         "gtop_trajectory_stats": (C.c_int, [vp, C.c_int, dp, C.c_double, dp, dp]),
         "gtop_set_moving_boxes": (C.c_int, [vp, C.c_int, dp, dp, dp]),
+        "gtop_set_moving_cost": (C.c_int, [vp, C.c_int]),
+        "gtop_get_moving_cost": (C.c_int, [vp, ip]),
+        "gtop_set_start_times": (C.c_int, [vp, C.c_int, dp]),
+        "gtop_set_start_times_device": (C.c_int, [vp, C.c_int, vp]),
         "gtop_edt_query_device": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp]),
         "gtop_edt_query": (C.c_int, [vp, C.c_int, dp, dp, dp, dp]),
         "gtop_edt_coarse_query_device": (C.c_int, [vp, C.c_int, vp, vp, vp, vp]),
@@ -168,7 +172,15 @@ def load_library():
         "gtop_group_optimize_batch_ex": (C.c_int, [vp, C.c_int, dp, dp, dp, C.POINTER(GtopStop), dp, C.POINTER(C.c_int32),
                                                    C.POINTER(C.c_int32)]),
     }
+    # An OLDER build chosen through GTOP_HIP_LIB (A/B timing against a parent commit) lacks the entry points of a later
+    # ABI version: those stay unbound there (calling one raises AttributeError); the in-tree library must have them all.
+    since = {"gtop_set_moving_cost": 4, "gtop_get_moving_cost": 4, "gtop_set_start_times": 4,
+             "gtop_set_start_times_device": 4}
+    L.gtop_abi_version.restype = C.c_int
+    abi = L.gtop_abi_version() if os.environ.get("GTOP_HIP_LIB") else max(since.values())
     for name, (res, args) in sig.items():
+        if since.get(name, 0) > abi:
+            continue
         f = getattr(L, name)
         f.restype = res
         f.argtypes = args
@@ -465,6 +477,41 @@ class GtopContext:
         p0, vel, scale = (_f64(a).reshape(-1, 3) for a in (p0, vel, scale))
         assert p0.shape == vel.shape == scale.shape
         self._chk(self._L.gtop_set_moving_boxes(self._h, p0.shape[0], _p(p0), _p(vel), _p(scale)))
+
+    # -- moving-obstacle cost (include/gtop.h: not in the reference's callback) --
+    MOVING_COST_MAX_BOXES = 32
+
+    def set_moving_cost(self, enable=True):
+        """The collision term of every fp64 evaluation and optimizer run looks its samples up against the static field
+        AND the boxes of set_moving_boxes at the sample's absolute time (start time + segment times + local time).
+        Off by default; on without boxes nothing changes (include/gtop.h, gtop_set_moving_cost)."""
+        self._chk(self._L.gtop_set_moving_cost(self._h, 1 if enable else 0))
+
+    def moving_cost(self):
+        on = C.c_int(0)
+        self._chk(self._L.gtop_get_moving_cost(self._h, C.byref(on)))
+        return bool(on.value)
+
+    def set_start_times(self, t0=None):
+        """The trajectories' start times on the boxes' clock: None = all zero, a scalar = one shared value, else one
+        per trajectory of the batch evaluated; finite and >= 0."""
+        if t0 is None:
+            self._chk(self._L.gtop_set_start_times(self._h, 0, None))
+            return
+        t0 = _f64(np.atleast_1d(t0)).reshape(-1)
+        self._chk(self._L.gtop_set_start_times(self._h, t0.shape[0], _p(t0)))
+
+    def set_start_times_device(self, t0):
+        """The same from a torch fp64 CUDA tensor, BORROWED: every launch reads it (a captured launch reads what it
+        holds at replay), so the caller keeps it alive; None = all zero."""
+        if t0 is None:
+            self._chk(self._L.gtop_set_start_times_device(self._h, 0, None))
+            self._t0_keep = None
+            return
+        import torch
+        assert t0.is_cuda and t0.dtype == torch.float64 and t0.is_contiguous()
+        self._t0_keep = t0
+        self._chk(self._L.gtop_set_start_times_device(self._h, t0.numel(), C.c_void_p(t0.data_ptr())))
 
     def edt_query(self, pos, time):
         """(dist (N,), grad (N, 3)) at pos (N, 3), time (N,); time < 0 = static field only."""

@@ -78,6 +78,24 @@ void GradTrajOptimizer::updateSDFMap(const std::vector<Vec3> &obs) {
   last_status_ = gtop_update_sdf_map(ctx_, obs.empty() ? nullptr : obs[0].data(), (int)obs.size());
 }
 
+void GradTrajOptimizer::setMovingObstacles(const std::vector<Vec3> &p0, const std::vector<Vec3> &vel,
+                                           const std::vector<Vec3> &scale) {
+  if (!ctx_) return;
+  if (p0.size() != vel.size() || p0.size() != scale.size()) {
+    last_status_ = GTOP_ERR_INVALID;
+    return;
+  }
+  const int nbox = (int)p0.size();
+  last_status_ = gtop_set_moving_boxes(ctx_, nbox, nbox ? p0[0].data() : nullptr, nbox ? vel[0].data() : nullptr,
+                                       nbox ? scale[0].data() : nullptr);
+  if (last_status_ == GTOP_OK) last_status_ = gtop_set_moving_cost(ctx_, nbox > 0);
+}
+
+void GradTrajOptimizer::setStartTime(double t0) {
+  if (!ctx_) return;
+  last_status_ = gtop_set_start_times(ctx_, 1, &t0);
+}
+
 // Common tail of setPath / setKinoPath: Df, Dp (getInitialD,
 // src/qp_generator.cpp:407-451), initial coefficients (Px = A^-1 Dx,
 // :334-336 / :134-136), then the problem goes to the device.

@@ -91,6 +91,12 @@ class GradTrajOptimizer {
   // here so that an external NLopt (or a test) can take its address.
   static double costFunc(const std::vector<double> &x, std::vector<double> &grad, void *func_data);
 
+  // The moving-obstacle cost (include/gtop.h, gtop_set_moving_cost; not in the reference's callback): boxes
+  // {p0, vel, scale} — centre p0 + vel t, extent +-scale/2 — and the trajectory's start time on their clock.  A
+  // non-empty list switches the mode on for costFunc and optimizeTrajectory (both roads), an empty one off.
+  void setMovingObstacles(const std::vector<Vec3> &p0, const std::vector<Vec3> &vel, const std::vector<Vec3> &scale);
+  void setStartTime(double t0);
+
   // extras (not in the reference)
   bool ok() const { return ctx_ != nullptr && last_status_ == GTOP_OK; }
   const char *lastError() const;

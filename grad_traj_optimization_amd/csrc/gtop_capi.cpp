@@ -19,7 +19,8 @@
 #include "gtop_guard.h"
 #include "gtop_kernels.h"
 
-#define GTOP_ABI_VERSION 3   // 3: gtop_set_field_sign, gtop_get_field_sign, gtop_group_set_field_sign
+#define GTOP_ABI_VERSION 4   // 4: gtop_set_moving_cost, gtop_get_moving_cost, gtop_set_start_times, gtop_set_start_times_device
+                             // 3: gtop_set_field_sign, gtop_get_field_sign, gtop_group_set_field_sign
                              // 2: gtop_update_sdf_map_window*, gtop_set_field_precisions, gtop_device_clock_*, gtop_group_gather_note, GTOP_ERR_INTERNAL
 
 struct gtop_ctx {
@@ -62,6 +63,16 @@ struct gtop_ctx {
   double *boxes = nullptr;   // moving boxes: p0 | vel | scale, nbox x 3 each
   size_t cap_boxes = 0;
   int nbox = 0;
+  // the moving-obstacle cost (gtop_set_moving_cost): the box list as the evaluation kernels read it — [nbox][9] rows
+  // p0, vel, scale / 2 in a buffer of GTOP_MOVING_COST_MAX_BOXES rows allocated once (its address is what a captured
+  // launch holds) and rewritten by gtop_set_moving_boxes — and the start times on the boxes' clock
+  int moving_cost = 0;
+  double *box_rows = nullptr;
+  bool box_rows_ok = false;        // the list fits and every box is finite with a non-negative extent
+  const double *t0_dev = nullptr;  // count > 0: owned (t0_own) or borrowed
+  double *t0_own = nullptr;
+  size_t cap_t0 = 0;
+  int t0_count = 0;
   double *d_q = nullptr;     // host-API staging of gtop_edt_query: pos | time | dist | grad
   size_t cap_q = 0;
   double *pin = nullptr;     // pinned, device-visible host staging for small host-buffer evaluations: x | cost | grad
@@ -238,6 +249,13 @@ int fp32_records_ready(gtop_ctx *c, hipStream_t s) {
   return GTOP_OK;
 }
 
+static_assert(GTOP_MOVING_COST_MAX_BOXES == GTOP_MOVING_MAX_BOXES, "the public box limit is the kernels' own");
+int ensure_box_rows(gtop_ctx *c) {
+  if (c->box_rows) return GTOP_OK;
+  HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->box_rows), (size_t)GTOP_MOVING_COST_MAX_BOXES * 9 * sizeof(double)));
+  return GTOP_OK;
+}
+
 template <typename R>
 void fill_args(const gtop_ctx *c, GtopKernelArgs<R> &a) {
   const GtopGrid &g = c->grid;
@@ -272,10 +290,55 @@ void fill_args(const gtop_ctx *c, GtopKernelArgs<R> &a) {
   a.step = p.step;
 }
 
+// The moving-obstacle cost is in force: switched on and at least one box set (without boxes the static kernels run).
+bool moving_active(const gtop_ctx *c) { return c->moving_cost != 0 && c->nbox > 0; }
+
+// What a moving-mode launch of B trajectories hands the kernels; the checks every road shares.  problem_B: the batch
+// of gtop_set_problem when the evaluation is of its first B rows (gtop_eval_batch: a per-trajectory list of that
+// length serves them), 0 otherwise.
+int moving_args(gtop_ctx *c, int B, int problem_B, GtopMovingArgs *mov) {
+  if (c->nbox > GTOP_MOVING_COST_MAX_BOXES)
+    return fail(c, GTOP_ERR_INVALID, "moving-obstacle cost: more boxes set than GTOP_MOVING_COST_MAX_BOXES");
+  if (!c->box_rows_ok)
+    return fail(c, GTOP_ERR_INVALID, "moving-obstacle cost: the box list has a non-finite value or a negative extent");
+  if (c->t0_count > 1 && c->t0_count != B && c->t0_count != problem_B)
+    return fail(c, GTOP_ERR_INVALID, "moving-obstacle cost: the number of start times does not match the batch");
+  mov->rows = c->box_rows;
+  mov->nbox = c->nbox;
+  mov->t0 = c->t0_count > 0 ? c->t0_dev : nullptr;
+  mov->t0_stride = c->t0_count > 1 ? 1 : 0;
+  return GTOP_OK;
+}
+
 template <typename R>
 int launch_eval(gtop_ctx *c, const R *sdf, int B, int m, const void *d_x, const void *d_Df,
                 const void *d_T, int t_stride, void *d_cost, void *d_grad, hipStream_t stream,
-                const GtopEvalPlan *optimizer_plan = nullptr) {
+                const GtopEvalPlan *optimizer_plan = nullptr, int problem_B = 0) {
+  if (moving_active(c)) {
+    if constexpr (sizeof(R) == 4) {
+      return fail(c, GTOP_ERR_STATE, "fp32 evaluation with the moving-obstacle cost on and boxes set: the term is fp64 only");
+    } else {
+      GtopMovingArgs mov;
+      int rc = moving_args(c, B, problem_B, &mov);
+      if (rc) return rc;
+      GtopKernelArgs<double> a;
+      fill_args(c, a);
+      a.sdf = sdf;
+      a.x = static_cast<const double *>(d_x);
+      a.Df = static_cast<const double *>(d_Df);
+      a.T = static_cast<const double *>(d_T);
+      a.cost = static_cast<double *>(d_cost);
+      a.grad = static_cast<double *>(d_grad);
+      a.B = B; a.m = m; a.t_stride = t_stride;
+      GtopEvalPlan plan;
+      if (optimizer_plan) plan = *optimizer_plan;
+      else if (!gtop_eval_plan_moving(B, m, c->spl, false, &plan))
+        return fail(c, GTOP_ERR_INVALID, "moving-obstacle cost: no body for this launch geometry / length (samples_per_lane "
+                                         "10 and 30, 3 with more than 6 segments; one wavefront's LDS: 227 segments)");
+      HIPCHK(c, gtop_launch_eval_moving(a, plan, c->prm.enable_dyn != 0, mov, stream));
+      return GTOP_OK;
+    }
+  }
   GtopKernelArgs<R> a;
   fill_args(c, a);
   a.sdf = sdf;
@@ -350,7 +413,7 @@ int gtop_destroy(gtop_ctx *c) try {
   (void)hipSetDevice(c->device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   release_sdf(c);
-  void *bufs[] = {c->win_occ, c->win_dist, c->rec64, c->rec32, c->occ, c->tmp1, c->tmp2, c->rows, c->boxes, c->d_q, c->d_pts,
+  void *bufs[] = {c->win_occ, c->win_dist, c->rec64, c->rec32, c->occ, c->tmp1, c->tmp2, c->rows, c->boxes, c->box_rows, c->t0_own, c->d_q, c->d_pts,
                   c->d_T, c->d_Df, c->d_x, c->d_cost, c->d_grad,
                   c->mma_vec, c->mma_scal, c->mma_int, c->mma_f, c->mma_g, c->mma_lb, c->mma_ub, c->mma_res};
   for (void *p : bufs)
@@ -699,7 +762,7 @@ int gtop_eval_batch(gtop_ctx *c, int B, const double *x, double *cost, double *g
     if (poll)
       for (size_t i = 0; i < nout; ++i) out[i] = c->poll_sentinel;
     if ((rc = launch_eval<double>(c, c->rec64, B, c->m, dpin, c->d_Df, c->d_T, c->t_stride, dpin + bn,
-                                  dpin + bn + B, c->stream)))
+                                  dpin + bn + B, c->stream, nullptr, c->B)))
       return rc;
     bool done = false;
     if (poll) {
@@ -729,7 +792,7 @@ int gtop_eval_batch(gtop_ctx *c, int B, const double *x, double *cost, double *g
   }
   HIPCHK(c, hipMemcpyAsync(c->d_x, x, (size_t)B * n * sizeof(double), hipMemcpyHostToDevice, c->stream));
   if ((rc = launch_eval<double>(c, c->rec64, B, c->m, c->d_x, c->d_Df, c->d_T, c->t_stride, c->d_cost,
-                                c->d_grad, c->stream)))
+                                c->d_grad, c->stream, nullptr, c->B)))
     return rc;
   HIPCHK(c, hipMemcpyAsync(cost, c->d_cost, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(grad, c->d_grad, (size_t)B * n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -780,6 +843,8 @@ int gtop_eval_device(gtop_ctx *c, int dtype, int B, int m, const void *d_x, cons
     if (!c->rec64_ok) return fail(c, GTOP_ERR_STATE, "no fp64 distance field resident");
     return launch_eval<double>(c, c->rec64, B, m, d_x, d_Df, d_T, time_stride, d_cost, d_grad, s);
   } else if (dtype == GTOP_F32) {
+    if (moving_active(c))
+      return fail(c, GTOP_ERR_STATE, "fp32 evaluation with the moving-obstacle cost on and boxes set: the term is fp64 only");
     if ((rc = fp32_records_ready(c, s))) return rc;
     return launch_eval<float>(c, c->rec32, B, m, d_x, d_Df, d_T, time_stride, d_cost, d_grad, s);
   }
@@ -926,8 +991,76 @@ int gtop_set_moving_boxes(gtop_ctx *c, int nbox, const double *p0, const double 
   HIPCHK(c, hipMemcpyAsync(c->boxes, p0, n3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(c->boxes + n3, vel, n3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(c->boxes + 2 * n3, scale, n3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  // the same list as the evaluation kernels read it (the moving-obstacle cost): rows of p0, vel, scale / 2, in a
+  // buffer that never moves.  A list the cost term cannot take (too long, a non-finite value, a negative extent — its
+  // slab distance is written for bmin <= bmax) still serves the queries; an evaluation in moving mode refuses it.
+  c->box_rows_ok = false;
+  if ((rc = ensure_box_rows(c))) return rc;
+  if (nbox <= GTOP_MOVING_COST_MAX_BOXES) {
+    double rows[GTOP_MOVING_COST_MAX_BOXES * 9];
+    bool ok = true;
+    for (int b = 0; b < nbox; ++b)
+      for (int k = 0; k < 3; ++k) {
+        const double p = p0[3 * b + k], v = vel[3 * b + k], sc = scale[3 * b + k];
+        ok = ok && std::isfinite(p) && std::isfinite(v) && std::isfinite(sc) && sc >= 0.0;
+        rows[9 * b + k] = p;
+        rows[9 * b + 3 + k] = v;
+        rows[9 * b + 6 + k] = 0.5 * sc;
+      }
+    HIPCHK(c, hipMemcpyAsync(c->box_rows, rows, (size_t)nbox * 9 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    c->box_rows_ok = ok;
+  }
   HIPCHK(c, hipStreamSynchronize(c->stream));   // the host arrays may go away
   c->nbox = nbox;
+  return GTOP_OK;
+} GTOP_CATCH_STATUS(c)
+
+int gtop_set_moving_cost(gtop_ctx *c, int enable) try {
+  if (!c) return GTOP_ERR_INVALID;
+  HIPCHK(c, hipSetDevice(c->device));
+  int rc;
+  if (enable && (rc = ensure_box_rows(c))) return rc;   // (so that no evaluation ever allocates for it)
+  c->moving_cost = enable != 0;
+  return GTOP_OK;
+} GTOP_CATCH_STATUS(c)
+
+int gtop_get_moving_cost(const gtop_ctx *c, int *enable) {
+  if (!c || !enable) return GTOP_ERR_INVALID;
+  *enable = c->moving_cost;
+  return GTOP_OK;
+}
+
+int gtop_set_start_times(gtop_ctx *c, int count, const double *t0_host) try {
+  if (!c) return GTOP_ERR_INVALID;
+  if (count < 0) return fail(c, GTOP_ERR_INVALID, "set_start_times: count < 0");
+  if (count == 0 || !t0_host) {
+    c->t0_count = 0;
+    c->t0_dev = nullptr;
+    return GTOP_OK;
+  }
+  for (int i = 0; i < count; ++i)
+    if (!(std::isfinite(t0_host[i]) && t0_host[i] >= 0.0))
+      return fail(c, GTOP_ERR_INVALID, "set_start_times: start times must be finite and >= 0");
+  HIPCHK(c, hipSetDevice(c->device));
+  int rc;
+  if ((rc = ensure(c, &c->t0_own, &c->cap_t0, (size_t)count))) return rc;
+  HIPCHK(c, hipMemcpyAsync(c->t0_own, t0_host, (size_t)count * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));   // the host array may go away
+  c->t0_dev = c->t0_own;
+  c->t0_count = count;
+  return GTOP_OK;
+} GTOP_CATCH_STATUS(c)
+
+int gtop_set_start_times_device(gtop_ctx *c, int count, const void *d_t0) try {
+  if (!c) return GTOP_ERR_INVALID;
+  if (count < 0) return fail(c, GTOP_ERR_INVALID, "set_start_times_device: count < 0");
+  if (count == 0 || !d_t0) {
+    c->t0_count = 0;
+    c->t0_dev = nullptr;
+    return GTOP_OK;
+  }
+  c->t0_dev = static_cast<const double *>(d_t0);   // borrowed: read by the launches, never copied
+  c->t0_count = count;
   return GTOP_OK;
 } GTOP_CATCH_STATUS(c)
 
@@ -1001,9 +1134,10 @@ int gtop_edt_coarse_query(gtop_ctx *c, int N, const double *pos, const double *t
 // Batched optimizer: max_evals rounds of {cost/gradient, MMA update} per trajectory on
 // `stream` — one launch for the whole loop (fusion mode 2), one per round (1), or two
 // per round (0); no host synchronisation inside.
-int gtop_optimize_device_ex(gtop_ctx *c, int B, int m, void *d_x, const void *d_Df, const void *d_T,
-                            int time_stride, const void *d_lb, const void *d_ub, const gtop_stop *stop, void *d_minf,
-                            int32_t *d_nevals, int32_t *d_code, void *hip_stream) try {
+// (problem_B: see moving_args — gtop_optimize_batch_ex runs the first B rows of the problem set)
+static int optimize_device_impl(gtop_ctx *c, int B, int m, void *d_x, const void *d_Df, const void *d_T,
+                                int time_stride, const void *d_lb, const void *d_ub, const gtop_stop *stop, void *d_minf,
+                                int32_t *d_nevals, int32_t *d_code, void *hip_stream, int problem_B) try {
   if (!c) return GTOP_ERR_INVALID;
   int rc = check_eval_state(c);
   if (rc) return rc;
@@ -1015,6 +1149,14 @@ int gtop_optimize_device_ex(gtop_ctx *c, int B, int m, void *d_x, const void *d_
   if (B == 0) return GTOP_OK;
   if (!d_x || !d_Df || !d_T || !d_lb || !d_ub) return fail(c, GTOP_ERR_INVALID, "optimize_device: NULL buffer");
   if (!c->rec64_ok) return fail(c, GTOP_ERR_STATE, "no fp64 distance field resident");
+  // the moving-obstacle cost: fp64 evaluations only, and its own checks before anything is allocated or launched
+  const bool moving = moving_active(c);
+  GtopMovingArgs mov{};
+  if (moving) {
+    if (c->opt_dtype == GTOP_F32)
+      return fail(c, GTOP_ERR_STATE, "optimize: fp32 evaluations with the moving-obstacle cost on and boxes set: the term is fp64 only");
+    if ((rc = moving_args(c, B, problem_B, &mov))) return rc;
+  }
   HIPCHK(c, hipSetDevice(c->device));
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   const size_t n = 9 * (size_t)(m - 1), bn = (size_t)B * n;
@@ -1041,10 +1183,11 @@ int gtop_optimize_device_ex(gtop_ctx *c, int B, int m, void *d_x, const void *d_
   const bool f32 = c->opt_dtype == GTOP_F32;   // gtop_set_optimizer_precision: see below
   const size_t eval_elem = f32 ? sizeof(float) : sizeof(double);
   const int opt_spl = (c->spl == 30 || c->spl == 10) ? 0 : c->spl;   // (three lanes / one lane per segment: plain-evaluation geometries)
-  bool planned = gtop_eval_plan(B, m, eval_elem, opt_spl, /*for_optimizer=*/true, &plan);
+  bool planned = moving ? gtop_eval_plan_moving(B, m, opt_spl, /*for_optimizer=*/true, &plan)
+                        : gtop_eval_plan(B, m, eval_elem, opt_spl, /*for_optimizer=*/true, &plan);
   // (two trajectories per wavefront with the velocity / acceleration block compiled in: the fp32 loop would spill —
   // enable_dyn keeps the loop at ten lanes per segment, one trajectory per wavefront)
-  if (planned && plan.nt == 2 && c->prm.enable_dyn != 0) planned = gtop_eval_plan(B, m, eval_elem, 3, true, &plan);
+  if (!moving && planned && plan.nt == 2 && c->prm.enable_dyn != 0) planned = gtop_eval_plan(B, m, eval_elem, 3, true, &plan);
   if (!planned)
     return fail(c, GTOP_ERR_INVALID, "optimize: this many segments cannot be served (ten lanes per segment: up to 6; "
                                      "one wavefront's LDS with the optimizer's state: 118)");
@@ -1078,6 +1221,7 @@ int gtop_optimize_device_ex(gtop_ctx *c, int B, int m, void *d_x, const void *d_
     a32.B = B; a32.m = m; a32.t_stride = time_stride;
   }
   auto launch_loop = [&]() -> hipError_t {
+    if (moving) return gtop_launch_eval_mma_moving(a, st, plan, dyn, mov, s);
     return f32 ? gtop_launch_eval_mma(a32, st, plan, dyn, s) : gtop_launch_eval_mma(a, st, plan, dyn, s);
   };
   // The whole optimisation as ONE launch: the loop initialises the state from d_x itself and writes the results where
@@ -1101,7 +1245,7 @@ int gtop_optimize_device_ex(gtop_ctx *c, int B, int m, void *d_x, const void *d_
       HIPCHK(c, launch_loop());
     } else {
       if ((rc = launch_eval<double>(c, c->rec64, B, m, st.xcur, d_Df, d_T, time_stride, c->mma_f, c->mma_g, s,
-                                    &plan)))   // the geometry the fused modes run: same bits
+                                    &plan, problem_B)))   // the geometry the fused modes run: same bits
         return rc;
       HIPCHK(c, gtop_launch_mma_update(st, B, (int)n, c->mma_f, c->mma_g, s));
     }
@@ -1111,6 +1255,12 @@ int gtop_optimize_device_ex(gtop_ctx *c, int B, int m, void *d_x, const void *d_
   HIPCHK(c, gtop_launch_mma_finish(st, B, d_code, d_nevals, s));
   return GTOP_OK;
 } GTOP_CATCH_STATUS(c)
+
+int gtop_optimize_device_ex(gtop_ctx *c, int B, int m, void *d_x, const void *d_Df, const void *d_T,
+                            int time_stride, const void *d_lb, const void *d_ub, const gtop_stop *stop, void *d_minf,
+                            int32_t *d_nevals, int32_t *d_code, void *hip_stream) {
+  return optimize_device_impl(c, B, m, d_x, d_Df, d_T, time_stride, d_lb, d_ub, stop, d_minf, d_nevals, d_code, hip_stream, 0);
+}
 
 int gtop_optimize_device(gtop_ctx *c, int B, int m, void *d_x, const void *d_Df, const void *d_T,
                          int time_stride, const void *d_lb, const void *d_ub, int max_evals, void *d_minf,
@@ -1135,8 +1285,8 @@ int gtop_optimize_batch_ex(gtop_ctx *c, int B, double *x, const double *lb, cons
   HIPCHK(c, hipMemcpyAsync(c->d_x, x, bn * sizeof(double), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(c->mma_lb, lb, bn * sizeof(double), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(c->mma_ub, ub, bn * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  if ((rc = gtop_optimize_device_ex(c, B, c->m, c->d_x, c->d_Df, c->d_T, c->t_stride, c->mma_lb, c->mma_ub, stop,
-                                    c->d_cost, c->mma_res, c->mma_res + B, c->stream)))
+  if ((rc = optimize_device_impl(c, B, c->m, c->d_x, c->d_Df, c->d_T, c->t_stride, c->mma_lb, c->mma_ub, stop,
+                                 c->d_cost, c->mma_res, c->mma_res + B, c->stream, c->B)))
     return rc;
   HIPCHK(c, hipMemcpyAsync(x, c->d_x, bn * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   if (min_cost)

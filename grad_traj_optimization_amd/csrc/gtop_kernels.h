@@ -76,6 +76,23 @@ bool gtop_eval_plan(int B, int m, size_t elem, int pinned_spl, bool for_optimize
 template <typename R>
 hipError_t gtop_launch_eval(const GtopKernelArgs<R> &args, const GtopEvalPlan &plan, bool dyn, hipStream_t stream);
 
+// ---- the moving-obstacle term (gtop_set_moving_cost): the lookup of every collision sample becomes
+// evaluateEDTWithGrad(pos, tau), the 8 corner values min'ed with the distance to the nearest box at the sample's
+// absolute time (fp64 bodies only) ----
+#define GTOP_MOVING_MAX_BOXES 32   // = GTOP_MOVING_COST_MAX_BOXES of include/gtop.h (checked in gtop_capi.cpp)
+struct GtopMovingArgs {
+  const double *rows;   // [nbox][9]: p0, vel, scale / 2 — wavefront-uniform, read through scalar loads
+  int nbox;             // 1 .. GTOP_MOVING_MAX_BOXES
+  const double *t0;     // start times on the boxes' clock; NULL = all zero
+  int t0_stride;        // 0 = one shared value, 1 = one per trajectory
+};
+// the launch rule restricted to the geometries that have a moving-term body; false: none serves the request
+bool gtop_eval_plan_moving(int B, int m, int pinned_spl, bool for_optimizer, GtopEvalPlan *plan);
+hipError_t gtop_launch_eval_moving(const GtopKernelArgs<double> &args, const GtopEvalPlan &plan, bool dyn,
+                                   const GtopMovingArgs &mov, hipStream_t stream);
+hipError_t gtop_launch_eval_mma_moving(const GtopKernelArgs<double> &args, const GtopMmaState &st, const GtopEvalPlan &plan,
+                                       bool dyn, const GtopMovingArgs &mov, hipStream_t stream);
+
 // `bytes` from src to each of the first n_dsts pointers of `dsts` (device memory of this or of a peer GPU mapped into
 // this process; 16-byte aligned), one kernel: gtop_push.hip
 #define GTOP_PUSH_MAX_DSTS 16

@@ -408,6 +408,81 @@ __device__ __forceinline__ R sdf_blend(const SdfTap<R> &tp, R &gx, R &gy, R &gz)
   return dist;   // (out of the map: the caller overrides value and gradient, sdf_map.cpp:187)
 }
 
+// ---- the moving-obstacle term (MOV bodies; gtop_set_moving_cost) ----
+// Kernel arguments of the MOV bodies, behind their MM argument (GtopMoving).  rows: [nbox][9] = p0, vel, scale / 2 per box
+// (GtopMovingArgs); t0: the trajectories' start times on the boxes' clock, NULL = all zero, stride 0 = one shared value.
+struct GtopMovK {
+  const double *rows, *t0;
+  int nbox, t0_stride;
+};
+
+// EDTEnvironment::evaluateEDTWithGrad's corner rule (src/edt_environment.cpp:26-122) on the 8 loaded corners of one
+// sample: each becomes min(static value, distance from its voxel's centre to the nearest box at time tau), written
+// with the expressions of gtop_edt.hip so that the corner values agree with the query kernel bit for bit.  tau < 0 or a
+// sample outside the map: static only (:91-94; the caller overrides an outside sample anyway).
+// The box rows are wavefront-uniform: scalar loads, every row value an SGPR operand; the loop over boxes stays rolled.
+// Per axis and corner offset the distance to the slab [bmin, bmax] — 0 inside, else the distance to the nearer face
+// (distToBox, :36-40) — is max(bmin - pt, pt - bmax, 0): the same bits as the reference's fmin(|pt - bmin|, |pt - bmax|)
+// for a box of non-negative extent (rounding is monotone, negation exact), which gtop_set_moving_boxes checks on the
+// host before an evaluation may use the list.
+// The skip of gtop_edt.hip (a box whose nearest corner distance does not undercut the largest of the 8 values changes
+// none of them) is taken on the squared distance against vmax^2 widened by 4 ulp: it lets through every box the
+// square-root test lets through (sqrt rounds within half an ulp), so the result is the same bit for bit, and a far
+// box costs no square root.
+__device__ __forceinline__ double mov_skip_bound(double vmax) {
+  // (vmax^2 underflows below 1e-154: such a value — never a voxel distance — lets every box through)
+  return vmax < 1e-140 ? (vmax > 0.0 ? __builtin_huge_val() : 0.0) : (vmax * vmax) * 1.000000000000001;
+}
+__device__ __forceinline__ void mov_min_boxes(SdfTap<double> &tp, const GtopKernelArgs<double> &a, const IndexBox &box,
+                                              const double (&p)[3], double tau, const GtopMovK &mk, bool in_map) {
+  const bool live = in_map & (tau >= 0.0);
+  double pt[3][2];   // centres of the corner voxels, gtop_edt.hip's expression
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const int idx = (int)floor(((p[k] - box.half) - box.org[k]) * box.rinv);   // sdf_issue's base index
+#pragma unroll
+    for (int o = 0; o < 2; ++o) pt[k][o] = (idx + o + 0.5) * a.res + a.origin[k];
+  }
+  double vmax = 0.0;
+#pragma unroll
+  for (int q = 0; q < 8; ++q) vmax = fmax(vmax, tp.v[q]);
+  double bound = mov_skip_bound(vmax);
+  // (the constant address space: memory no kernel writes while this one runs, so a uniform address is a scalar load
+  // whatever the compiler can or cannot prove about the stores of this kernel)
+  typedef const double __attribute__((address_space(4))) *ConstRows;
+  const ConstRows rows = (ConstRows)(uintptr_t)mk.rows;
+#pragma unroll 1
+  for (int b = 0; b < mk.nbox; ++b) {
+    const ConstRows r = rows + 9 * b;
+    double d1[3][2];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const double c = r[k] + r[3 + k] * tau;   // obj_predictor.h:57-66
+      const double bmax = c + r[6 + k], bmin = c - r[6 + k];
+#pragma unroll
+      for (int o = 0; o < 2; ++o) d1[k][o] = fmax(fmax(bmin - pt[k][o], pt[k][o] - bmax), 0.0);
+    }
+    const double near2 = fmin(d1[0][0], d1[0][1]) * fmin(d1[0][0], d1[0][1]) +
+                         fmin(d1[1][0], d1[1][1]) * fmin(d1[1][0], d1[1][1]) +
+                         fmin(d1[2][0], d1[2][1]) * fmin(d1[2][0], d1[2][1]);
+    if (live & (near2 < bound)) {
+      vmax = 0.0;
+#pragma unroll
+      for (int x = 0; x < 2; ++x)
+#pragma unroll
+        for (int y = 0; y < 2; ++y)
+#pragma unroll
+          for (int z = 0; z < 2; ++z) {
+            const double d2 = sqrt(d1[0][x] * d1[0][x] + d1[1][y] * d1[1][y] + d1[2][z] * d1[2][z]);   // dist.norm()
+            double &v = tp.v[4 * z + 2 * x + y];
+            v = d2 < v ? d2 : v;
+            vmax = fmax(vmax, v);
+          }
+      bound = mov_skip_bound(vmax);
+    }
+  }
+}
+
 // sum of N consecutive values as a balanced tree (depth log2 N instead of an
 // N-long dependent chain)
 template <typename R, int N>
@@ -671,6 +746,16 @@ __device__ __forceinline__ C gtop_jerk_term(const C (&q)[3][6], C T, C wj, const
 // reject, asymptotes, stop rules, next trial point), evaluate again; cost and gradient never leave the chip.  One
 // wavefront owns the trajectory, so the loop needs no barrier at all.  MM = GtopNoMma: a plain evaluation.
 struct GtopNoMma {};
+// MOV, the moving-obstacle term (gtop_set_moving_cost): a compile-time flag of the kernel carried by MM — the MOV
+// bodies take GtopMoving<GtopNoMma> / GtopMoving<GtopMmaState>, the plain or the optimizer argument with the box list
+// and the start times behind it — so that the static bodies keep their template arguments, their kernel arguments and
+// their names.  Like DYN it lives in the sample loop and is routed to a one-sample-at-a-time body.
+template <typename Base> struct GtopMoving : Base {
+  GtopMovK mk;
+};
+template <typename MM> constexpr bool kIsMov = false;
+template <typename Base> constexpr bool kIsMov<GtopMoving<Base>> = true;
+template <typename MM> constexpr bool kIsMma = std::is_base_of<GtopMmaState, MM>::value;
 // DYN compiles in the velocity / acceleration penalties the reference has commented out
 // (src/grad_traj_optimizer.cpp:383-407, formulas :517-535; they sit inside the collision sample loop, so DYN needs
 // COLLI; the launcher picks DYN only for enable_dyn at step 2, as the block's own `step == 2` test would).
@@ -683,9 +768,11 @@ struct GtopNoMma {};
 // the extra penalty terms need the room).
 // (64-bit field indices — fields past 4 GiB — spill the 168-VGPR fp64 bodies at six samples per lane: two-wavefront budget)
 // (the same for the fp64 body that walks more than 12 segments in chunks: 19 spilled registers at 168)
+// (MOV, the moving-obstacle term: like DYN — the box loop keeps the 8 corners, 6 slab distances and 6 corner-centre
+// coordinates live on top of the one-sample body, which alone sits at 166-168 of 168)
 template <typename R, bool WIDE, typename MM, int SPL, int MINW, bool DYN, bool LONG>
 constexpr int gtop_wave_budget() {
-  return ((!std::is_same<MM, GtopNoMma>::value && SPL == 6) || DYN || ((WIDE || LONG) && sizeof(R) == 8 && SPL >= 6) ||
+  return ((kIsMma<MM> && SPL == 6) || DYN || kIsMov<MM> || ((WIDE || LONG) && sizeof(R) == 8 && SPL >= 6) ||
           (sizeof(R) == 4 && SPL >= 6))   // (packed fp32 with the double coefficients of its exact positions: 190 VGPRs)
              ? 2
              : MINW;
@@ -702,7 +789,8 @@ gtop_eval_wave_kernel(const R *__restrict__ arg_x, const R *__restrict__ arg_Df,
                       const R *__restrict__ arg_sdf, int arg_B, int arg_m, int arg_t_stride, int arg_nx, int arg_ny,
                       int arg_nz, const GtopKernelArgs<R> arg_rest, const GtopWaveConsts<R> K, const MM st,
                       const GtopSetupConsts<R> KD) {
-  constexpr bool MMA = !std::is_same<MM, GtopNoMma>::value;
+  constexpr bool MMA = kIsMma<MM>;
+  constexpr bool MOV = kIsMov<MM>;
   static_assert(!MMA || NT == 1 || (SPL == 6 && !LONG), "the optimizer loop: one trajectory per wavefront, or two at five lanes per segment");
   // the optimizer's state, bounds, Df and T are fp64 whatever R is: with R = float only the evaluation runs in fp32
   // (its inputs converted as they are read from LDS, its cost and gradient widened for the update)
@@ -729,6 +817,8 @@ gtop_eval_wave_kernel(const R *__restrict__ arg_x, const R *__restrict__ arg_Df,
   static_assert(!LONG || (SPL == 6 && NT == 1), "more than 12 segments: five lanes per segment, one trajectory");
   static_assert(!DYN || (COLLI && MINW >= 3), "the velocity/acceleration block lives in the sample loop, one sample at a time");
   static_assert(NW == 1 || (NW == 2 && SPL == 3 && NT == 1 && !LONG && !MMA), "two wavefronts per trajectory: plain evaluation at ten lanes per segment");
+  static_assert(!MOV || (COLLI && MINW >= 3 && !kIsF32<R> && (SPL == 3 || SPL == 6) && NW == 1),
+                "the moving-obstacle term: fp64, in the sample loop, one sample at a time, ten or five lanes per segment");
   extern __shared__ __align__(16) unsigned char smem_raw[];
   R *tile = reinterpret_cast<R *>(smem_raw);   // [19][kStride] (+ [kRounds*64] gradient for the optimizer update)
   GTOP_STAMP(0);
@@ -839,6 +929,11 @@ gtop_eval_wave_kernel(const R *__restrict__ arg_x, const R *__restrict__ arg_Df,
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // staged by some lanes, read by others of this wavefront
     __builtin_amdgcn_wave_barrier();
   }
+  // MOV: the trajectory's start time on the boxes' clock (gtop_set_start_times; idle lanes shadow a live row)
+  [[maybe_unused]] double mov_t0 = 0.0;
+  if constexpr (MOV) {
+    if (st.mk.t0) mov_t0 = st.mk.t0[(size_t)(b0 + tl) * (size_t)st.mk.t0_stride];
+  }
   for (int pass = 0; pass < npass; ++pass) {
   const R *xsrc = a.x;
   if constexpr (MMA) {
@@ -861,6 +956,10 @@ gtop_eval_wave_kernel(const R *__restrict__ arg_x, const R *__restrict__ arg_Df,
   int offA[kRounds], offB[kRounds];     // (filled below, while the inputs are on their way)
   bool okq[kRounds];
   bool cost_lane = false;
+  // MOV: the start of the lane's segment on the absolute clock, ((t0 + T_0) + T_1) + ... + T_{s-1}, summed left to
+  // right; the chunked body carries the sum from chunk to chunk (its segment index grows by SPW: the same order)
+  [[maybe_unused]] double mov_seg = mov_t0;
+  [[maybe_unused]] int mov_upto = 0;
   for (int ch = 0; ch < nchunks; ++ch) {
   if constexpr (LONG) {
     s = ch * SPW + slot_w;
@@ -881,6 +980,18 @@ gtop_eval_wave_kernel(const R *__restrict__ arg_x, const R *__restrict__ arg_Df,
     Tb = a.T + (size_t)b0 * a.t_stride + tl * a.t_stride;
   }
   const R T = (R)Tb[s];
+  if constexpr (MOV) {
+    constexpr int kPre = NT == 2 ? SPW / 2 : SPW;   // the most a lane's segment index advances by: every load issued at once
+    const int target = seg_ok ? s : mov_upto;
+#pragma unroll
+    for (int j = 0; j < kPre; ++j) {
+      const int jj = mov_upto + j;
+      const bool take = jj < target;
+      const double Tj = (double)Tb[take ? jj : 0];
+      mov_seg = take ? mov_seg + Tj : mov_seg;
+    }
+    mov_upto = target > mov_upto ? target : mov_upto;
+  }
   // axis 0: the (p, v, a) triple at the segment's start and at its end; the other axes are one per-lane stride
   // further (6 within Df, 3m-3 within x: :182-187)
   const bool first = s == 0, last = s + 1 == m;
@@ -1120,6 +1231,7 @@ gtop_eval_wave_kernel(const R *__restrict__ arg_x, const R *__restrict__ arg_Df,
       constexpr bool kLoadsFirst = GTOP_LOADS_FIRST && CH == 1 && !LONG;   // (the chunked body, on the two-wavefront budget: 3 % slower with it, measured)
       [[maybe_unused]] float pmin[3], pmax[3];
       [[maybe_unused]] bool outs[CH];
+      [[maybe_unused]] double pos_mov[3];   // MOV (one sample at a time): the sample's position, for the corner centres
       // (the position polynomial in double — fp32 kernels: from the double coefficients and the double sample time)
       auto position = [&](int k, TT t, TT t2, TT t3, TT t4, TT t5) {
         if constexpr (kIsF32<R>)
@@ -1142,6 +1254,7 @@ gtop_eval_wave_kernel(const R *__restrict__ arg_x, const R *__restrict__ arg_Df,
           const float pf = position(k, tt, u2, u3, u4, u5);
           pos[k] = (double)pf;
           posf[k] = pf;
+          if constexpr (MOV) pos_mov[k] = pos[k];
           if constexpr (kRareOut) {
             pmin[k] = c == 0 ? pf : fminf(pmin[k], pf);
             pmax[k] = c == 0 ? pf : fmaxf(pmax[k], pf);
@@ -1223,6 +1336,8 @@ gtop_eval_wave_kernel(const R *__restrict__ arg_x, const R *__restrict__ arg_Df,
         const R t2 = t * t, t3 = t2 * t, t4 = t2 * t2, t5 = t4 * t;
         const R vn = vns[c], ivn = ivns[c];
         R g3[3];
+        if constexpr (MOV)   // the time-aware lookup: the 8 corners min'ed with the boxes at the sample's absolute time
+          mov_min_boxes(taps[c], a, ibox, pos_mov, mov_seg + (double)tt, st.mk, !outs[c]);
         R dist = sdf_blend(taps[c], g3[0], g3[1], g3[2]);   // g3 per voxel, not per metre
         if constexpr (!kRareOut) {   // dist = -1 (sdf_map.cpp:187); grad := 0 below, through its weight f1
           dist = outs[c] ? (R)-1 : dist;
@@ -1484,6 +1599,7 @@ gtop_eval_wave_kernel(const R *__restrict__ arg_x, const R *__restrict__ arg_Df,
   }
 }
 
+
 }  // namespace
 
 // WIDE = false needs 24-bit (signed) multiplicands and corner records below 4 GiB (record_loads)
@@ -1629,6 +1745,24 @@ bool gtop_eval_plan(int B, int m, size_t elem, int pinned_spl, bool for_optimize
   return true;
 }
 
+// The launch rule of the moving-obstacle bodies (fp64): the static rule restricted to the geometries that have one.
+// Auto: up to 6 segments ten lanes per segment, from the static rule's own switch point five lanes per segment with two
+// trajectories per wavefront (the optimizer loop: one); 7 .. 12 segments five lanes per segment; past 12 the chunked
+// body.  Pinned 3 / 6 as in the static rule, except that 3 with 7 .. 12 segments (two wavefronts per trajectory) and
+// 10 / 30 (three lanes, one lane per segment) have no moving-term body: false.
+bool gtop_eval_plan_moving(int B, int m, int pinned_spl, bool for_optimizer, GtopEvalPlan *plan) {
+  if (pinned_spl == 10 || pinned_spl == 30) return false;
+  int pin = pinned_spl;
+  if (pin == 0)
+    pin = m <= 6 ? (B >= (for_optimizer ? GTOP_OPT_TWO_PER_WAVE_F64_FROM : GTOP_TWO_PER_WAVE_F64_FROM) ? 6 : 3) : 6;
+  GtopEvalPlan p;
+  if (!gtop_eval_plan(B, m, sizeof(double), pin, for_optimizer, &p)) return false;
+  if (for_optimizer && p.nt == 2 && !gtop_eval_plan(B, m, sizeof(double), 3, true, &p)) return false;
+  if (p.nw != 1 || (p.spl != 3 && p.spl != 6)) return false;
+  *plan = p;
+  return true;
+}
+
 namespace {
 
 template <typename R, typename MM>
@@ -1679,13 +1813,40 @@ static WaveKernelFn<R, MM> pick_geometry(const GtopEvalPlan &p, int B, bool coll
   return pick_body<R, WIDE, 6, 1, 3, MM, false>(colli, dyn);
 }
 
+// The moving-obstacle bodies (MM = GtopMoving<...>; fp64): one sample at a time on the two-wavefront budget, with and without the
+// velocity / acceleration block, for ten lanes per segment (up to 6 segments), five lanes per segment with one
+// trajectory (up to 12) or — plain evaluations — two (up to 6 each), and the chunked body past 12 segments.  Three
+// lanes or one lane per segment and two wavefronts per trajectory have no such body: nullptr (gtop_eval_plan_moving
+// never picks them).
+template <bool WIDE, int SPL, int NT, typename MM, bool LONG>
+static WaveKernelFn<double, MM> pick_body_moving(bool dyn) {
+  if (dyn) return gtop_eval_wave_kernel<double, WIDE, SPL, NT, true, 3, MM, true, LONG, 1>;
+  return gtop_eval_wave_kernel<double, WIDE, SPL, NT, true, 3, MM, false, LONG, 1>;
+}
+template <bool WIDE, typename MM>
+static WaveKernelFn<double, MM> pick_geometry_moving(const GtopEvalPlan &p, bool dyn) {
+  constexpr bool MMA = kIsMma<MM>;
+  if (p.nw != 1 || (p.spl != 3 && p.spl != 6)) return nullptr;
+  if (p.is_long) return pick_body_moving<WIDE, 6, 1, MM, true>(dyn);
+  if (p.spl == 3) return pick_body_moving<WIDE, 3, 1, MM, false>(dyn);
+  if (p.nt == 2) {
+    if constexpr (MMA) return nullptr;   // (the loop keeps one trajectory per wavefront, as with DYN)
+    else return pick_body_moving<WIDE, 6, 2, MM, false>(dyn);
+  }
+  return pick_body_moving<WIDE, 6, 1, MM, false>(dyn);
+}
+
 // one launch covers up to 2^25 wavefronts (grid x 64 threads stays below 2^32); a larger batch goes in slices
 constexpr int kMaxGroupsPerLaunch = 1 << 25;
+
+template <typename MM> struct MovingBase { using type = MM; };
+template <typename Base> struct MovingBase<GtopMoving<Base>> { using type = Base; };
 
 template <typename R, typename MM>
 static hipError_t launch_wave(const GtopKernelArgs<R> &args, const MM &st, const GtopEvalPlan &plan, bool dyn,
                               hipStream_t stream) {
-  constexpr bool MMA = !std::is_same<MM, GtopNoMma>::value;
+  constexpr bool MMA = kIsMma<MM>;
+  constexpr bool MOV = kIsMov<MM>;
   if (args.B <= 0) return hipSuccess;
   GtopKernelArgs<R> wa = args;
   if (wa.step == 1) wa.ws = (R)0;   // :412-415, applied here so that the kernel need not fetch `step`
@@ -1693,7 +1854,11 @@ static hipError_t launch_wave(const GtopKernelArgs<R> &args, const MM &st, const
   dyn = dyn && wa.step == 2;        // the commented-out block's own test (:383)
   const bool wide = !gtop_field_is_narrow(wa.nx, wa.ny, wa.nz, sizeof(R));
   WaveKernelFn<R, MM> kern;
-  if constexpr (MMA && sizeof(R) == 4) {   // (the optimizer loop with fp32 evaluations: no 64-bit-index bodies — a field past 4 GiB in fp32)
+  if constexpr (MOV) {   // the moving-obstacle term lives in the sample loop: without a collision term there is none
+    using Base = typename MovingBase<MM>::type;
+    if (!colli) return launch_wave<R, Base>(args, static_cast<const Base &>(st), plan, dyn, stream);
+    kern = wide ? pick_geometry_moving<true, MM>(plan, dyn) : pick_geometry_moving<false, MM>(plan, dyn);
+  } else if constexpr (MMA && sizeof(R) == 4) {   // (the optimizer loop with fp32 evaluations: no 64-bit-index bodies — a field past 4 GiB in fp32)
     if (wide) return hipErrorInvalidValue;
     kern = pick_geometry<R, false, MM>(plan, wa.B, colli, dyn);
   } else {
@@ -1720,8 +1885,12 @@ static hipError_t launch_wave(const GtopKernelArgs<R> &args, const MM &st, const
     s.grad = wa.grad ? wa.grad + (size_t)b0 * n : nullptr;
     const int groups = (s.B + plan.nt - 1) / plan.nt;
     const int grid = 8 * ((groups + 7) / 8);   // the kernel deals its workgroups over 8 XCD-contiguous ranges
+    MM sst = st;
+    if constexpr (MOV) {   // the slice's rows of the start times
+      if (sst.mk.t0) sst.mk.t0 += (size_t)b0 * (size_t)sst.mk.t0_stride;
+    }
     hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * plan.nw), smem, stream, s.x, s.Df, s.T, s.sdf, s.B, s.m, s.t_stride, s.nx, s.ny,
-                       s.nz, s, GtopWaveConsts<R>{}, st, GtopSetupConsts<R>{});
+                       s.nz, s, GtopWaveConsts<R>{}, sst, GtopSetupConsts<R>{});
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
@@ -1733,6 +1902,25 @@ static hipError_t launch_wave(const GtopKernelArgs<R> &args, const MM &st, const
 template <typename R>
 hipError_t gtop_launch_eval(const GtopKernelArgs<R> &args, const GtopEvalPlan &plan, bool dyn, hipStream_t stream) {
   return launch_wave<R, GtopNoMma>(args, GtopNoMma{}, plan, dyn, stream);
+}
+
+template <typename Base>
+static GtopMoving<Base> moving_kernel_args(const Base &st, const GtopMovingArgs &mov) {
+  GtopMoving<Base> mm;
+  static_cast<Base &>(mm) = st;
+  mm.mk = GtopMovK{mov.rows, mov.t0, mov.nbox, mov.t0_stride};
+  return mm;
+}
+hipError_t gtop_launch_eval_moving(const GtopKernelArgs<double> &args, const GtopEvalPlan &plan, bool dyn,
+                                   const GtopMovingArgs &mov, hipStream_t stream) {
+  if (!mov.rows || mov.nbox < 1 || mov.nbox > GTOP_MOVING_MAX_BOXES) return hipErrorInvalidValue;
+  return launch_wave<double, GtopMoving<GtopNoMma>>(args, moving_kernel_args(GtopNoMma{}, mov), plan, dyn, stream);
+}
+hipError_t gtop_launch_eval_mma_moving(const GtopKernelArgs<double> &args, const GtopMmaState &st, const GtopEvalPlan &plan,
+                                       bool dyn, const GtopMovingArgs &mov, hipStream_t stream) {
+  if (!mov.rows || mov.nbox < 1 || mov.nbox > GTOP_MOVING_MAX_BOXES) return hipErrorInvalidValue;
+  if (plan.nt != 1) return hipErrorInvalidValue;
+  return launch_wave<double, GtopMoving<GtopMmaState>>(args, moving_kernel_args(st, mov), plan, dyn, stream);
 }
 
 // the optimizer loop: st.iters evaluations at st.xcur, each followed by the CCSA-MMA update, in one launch (fp64)

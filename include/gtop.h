@@ -78,7 +78,9 @@ const char *gtop_last_error(const gtop_ctx *ctx);
 /* Library/ABI version, for the loader to check (2 since round 4: the windowed map
  * update, gtop_set_field_precisions, gtop_device_clock_*, gtop_group_gather_note,
  * GTOP_ERR_INTERNAL; 3: the signed field, gtop_set_field_sign / gtop_get_field_sign /
- * gtop_group_set_field_sign; nothing of an earlier version changed meaning). */
+ * gtop_group_set_field_sign; 4: the moving-obstacle cost, gtop_set_moving_cost /
+ * gtop_get_moving_cost / gtop_set_start_times / gtop_set_start_times_device; nothing
+ * of an earlier version changed meaning). */
 int gtop_abi_version(void);
 
 /* ---- configuration -------------------------------------------------- */
@@ -469,6 +471,62 @@ int gtop_edt_coarse_query_device(gtop_ctx *ctx, int N, const void *d_pos,
                                  const void *d_time, void *d_dist, void *hip_stream);
 int gtop_edt_coarse_query(gtop_ctx *ctx, int N, const double *pos, const double *time,
                           double *dist);
+
+/* ---- moving-obstacle cost (not in the reference's callback) ---------- */
+/* Off (the default), every evaluation looks the collision samples up in the static
+ * field, as the reference's callback does (src/grad_traj_optimizer.cpp:363).  On,
+ * and with at least one box set (gtop_set_moving_boxes), the lookup of every
+ * collision sample is the time-aware one the queries above answer: for
+ * trajectory b, segment s, sample i, with local time t and position exactly as
+ * before (:353, :457-465),
+ *     tau = ((t0[b] + T[b][0]) + ... + T[b][s-1]) + t        (fp64, left to right)
+ *     (dist, grad) = evaluateEDTWithGrad(pos, tau)
+ * — the 8 corner values min'ed with the distance from each corner voxel's centre
+ * to the nearest box at tau, then the unchanged trilinear value and gradient; out
+ * of the map dist = -1, grad = 0, boxes ignored; a sample with tau < 0 is static
+ * only.  Everything downstream (:365-381) is unchanged; segment times are not
+ * variables, so nothing is differentiated through tau.  The resident field's
+ * values are taken as they are (a signed field works as for the queries).  A box
+ * over a sample drives its distance to 0, never below: the penalty's exponent is
+ * bounded by d0 / r as on an unsigned field, so the mode opens no overflow road
+ * beyond the one the signed field documents.  Inside a box all 8 corners are 0
+ * and the gradient vanishes, as in any unsigned field.
+ *
+ * Context state, so it reaches every fp64 road: gtop_eval_batch, gtop_cost_nlopt
+ * (trajectory 0's start time), gtop_cost_nlopt_shared (row i's),
+ * gtop_eval_device(GTOP_F64), gtop_optimize_batch[_ex], gtop_optimize_device[_ex]
+ * in all three fusion modes, with or without enable_dyn.  The device forms still
+ * only enqueue (no allocation, no synchronisation; capturable).  On with NO boxes:
+ * the static kernels run, results bit-identical to off.
+ * Limits:
+ *  - fp64 only: a GTOP_F32 evaluation, or an optimizer run under
+ *    gtop_set_optimizer_precision(GTOP_F32), with the mode on and boxes set is
+ *    GTOP_ERR_STATE.
+ *  - at most GTOP_MOVING_COST_MAX_BOXES boxes, each finite with scale >= 0 (the
+ *    queries take any list); otherwise GTOP_ERR_INVALID at the evaluation.
+ *  - launch geometry (gtop_set_launch_geometry): samples_per_lane 0 (auto) serves
+ *    every length the static evaluation serves (2 .. 227 segments; the optimizer
+ *    118) and every batch; 3 serves up to 6 segments, 6 every length; 10 and 30,
+ *    and 3 with more than 6 segments, have no moving-term body: GTOP_ERR_INVALID
+ *    at the evaluation (the optimizer, which ignores 10 and 30, runs its own rule).
+ *  - the gtop_group_* entry points do not forward the mode; a member context can
+ *    be configured through gtop_group_context.
+ *
+ * Start times t0 on the boxes' clock: count = 0 (or NULL) all zero (the default);
+ * count = 1 one shared value; otherwise one per trajectory, and count must equal
+ * the batch of the evaluation it is used with (for gtop_eval_batch, gtop_cost_nlopt
+ * and gtop_optimize_batch[_ex], which run the first B rows of the problem set, the
+ * problem's batch serves too) — a mismatch is GTOP_ERR_INVALID at the evaluation,
+ * nothing launched.  Host values must be finite and >= 0 (GTOP_ERR_INVALID at the
+ * call).  The device form borrows an fp64 device buffer: no copy, no
+ * synchronisation, values not inspected — it is read by every launch, so a
+ * captured launch follows what the buffer holds at replay, and a sample whose
+ * tau < 0 is static only, as in the query. */
+#define GTOP_MOVING_COST_MAX_BOXES 32
+int gtop_set_moving_cost(gtop_ctx *ctx, int enable);
+int gtop_get_moving_cost(const gtop_ctx *ctx, int *enable);
+int gtop_set_start_times(gtop_ctx *ctx, int count, const double *t0_host);
+int gtop_set_start_times_device(gtop_ctx *ctx, int count, const void *d_t0);
 
 /* ---- bookkeeping the reference keeps inside the callback ------------ */
 
