@@ -45,6 +45,16 @@ OPTI_NODE_PARAMS = dict(ws=1.0, wc=5.0, alpha=10.0, r=0.5, d0=0.8,
 _lib = None
 
 
+class GtopLimits(C.Structure):
+    """gtop_limits of include/gtop.h: what a trajectory must keep to pass (validate_batch / select_best_device)."""
+    _fields_ = [("margin", C.c_double), ("max_vel", C.c_double), ("max_acc", C.c_double), ("per_axis", C.c_int32),
+                ("allow_out_of_map", C.c_int32), ("use_boxes", C.c_int32)]
+
+    def __init__(self, margin=0.0, max_vel=0.0, max_acc=0.0, per_axis=False, allow_out_of_map=False, use_boxes=False):
+        super().__init__(float(margin), float(max_vel), float(max_acc), int(bool(per_axis)), int(bool(allow_out_of_map)),
+                         int(bool(use_boxes)))
+
+
 def library_path():
     return _SO
 
@@ -114,6 +124,11 @@ def load_library():
         "gtop_edt_coarse_query": (C.c_int, [vp, C.c_int, dp, dp, dp]),
         "gtop_sample_trajectories_device": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_double, vp, vp, C.c_int, vp]),
         "gtop_trajectory_samples": (C.c_int, [vp, C.c_int, dp, C.c_double, dp, dp, dp, C.c_int]),
+        "gtop_validate_trajectories_device": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_double,
+                                                        C.POINTER(GtopLimits), vp, vp]),
+        "gtop_select_best_device": (C.c_int, [vp, C.c_int, vp, vp, C.POINTER(GtopLimits), vp, vp, vp]),
+        "gtop_validate_batch": (C.c_int, [vp, C.c_int, dp, C.c_double, C.POINTER(GtopLimits), dp, dp,
+                                          C.POINTER(C.c_ubyte), C.POINTER(C.c_int32)]),
         "gtop_default_bounds": (C.c_int, [C.c_int, C.c_int, dp, C.c_double, C.c_double, C.c_double, dp, dp]),
         "gtop_optimize_batch": (C.c_int, [vp, C.c_int, dp, dp, dp, C.c_int, dp]),
         "gtop_optimize_device": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp, C.c_int, vp, vp]),
@@ -175,7 +190,8 @@ def load_library():
     # An OLDER build chosen through GTOP_HIP_LIB (A/B timing against a parent commit) lacks the entry points of a later
     # ABI version: those stay unbound there (calling one raises AttributeError); the in-tree library must have them all.
     since = {"gtop_set_moving_cost": 4, "gtop_get_moving_cost": 4, "gtop_set_start_times": 4,
-             "gtop_set_start_times_device": 4}
+             "gtop_set_start_times_device": 4, "gtop_validate_trajectories_device": 5, "gtop_select_best_device": 5,
+             "gtop_validate_batch": 5}
     L.gtop_abi_version.restype = C.c_int
     abi = L.gtop_abi_version() if os.environ.get("GTOP_HIP_LIB") else max(since.values())
     for name, (res, args) in sig.items():
@@ -543,6 +559,79 @@ class GtopContext:
                                                 C.c_void_p(dist.data_ptr()), C.c_void_p(grad.data_ptr()),
                                                 C.c_void_p(stream)))
         return dist, grad
+
+    # -- trajectory safety report and best-candidate selection (include/gtop.h) --
+    TRAJ_REPORT = ("n_samples", "clearance", "clearance_t", "clearance_index", "n_below_margin", "first_below_t",
+                   "n_out_of_map", "max_vel_norm", "max_acc_norm", "max_vel_axis", "max_acc_axis", "time_sum")
+
+    def validate_batch(self, x, limits, cost=None, dt_sample=0.01):
+        """The report of the context's problem at free variables x (B, n) and, with `cost` (B,) given, the selection:
+        (report (B, 12), pass (B,) bool, best (2,) int32 = [index of the passing row of least cost or -1, passing
+        rows]); pass and best are None without cost."""
+        x = _f64(x)
+        B = x.shape[0]
+        report = np.empty((B, len(self.TRAJ_REPORT)))
+        if cost is None:
+            self._chk(self._L.gtop_validate_batch(self._h, B, _p(x), float(dt_sample), C.byref(limits), None, _p(report),
+                                                  None, None))
+            return report, None, None
+        cost = _f64(cost).reshape(-1)
+        assert cost.shape[0] == B
+        ok = np.zeros(B, dtype=np.uint8)
+        best = np.zeros(2, dtype=np.int32)
+        self._chk(self._L.gtop_validate_batch(self._h, B, _p(x), float(dt_sample), C.byref(limits), _p(cost), _p(report),
+                                              ok.ctypes.data_as(C.POINTER(C.c_ubyte)),
+                                              best.ctypes.data_as(C.POINTER(C.c_int32))))
+        return report, ok.astype(bool), best
+
+    def coefficients_device(self, x, Df, T, coeff=None, stream=None):
+        """torch fp64 CUDA tensors x (B, n), Df (B, 18), T (B, m) or (m,) -> coeff (B, m, 18); asynchronous."""
+        import torch
+        assert x.is_cuda and x.dtype == Df.dtype == T.dtype == torch.float64
+        assert x.is_contiguous() and Df.is_contiguous() and T.is_contiguous()
+        B, m = x.shape[0], T.shape[-1]
+        if coeff is None:
+            coeff = torch.empty(B, m, 18, dtype=torch.float64, device=x.device)
+        if stream is None:
+            stream = torch.cuda.current_stream(x.device).cuda_stream
+        self._chk(self._L.gtop_coefficients_device(self._h, B, m, C.c_void_p(x.data_ptr()), C.c_void_p(Df.data_ptr()),
+                                                   C.c_void_p(T.data_ptr()), m if T.dim() == 2 else 0,
+                                                   C.c_void_p(coeff.data_ptr()), C.c_void_p(stream)))
+        return coeff
+
+    def validate_device(self, coeff, T, limits, dt_sample=0.01, report=None, stream=None):
+        """torch fp64 CUDA tensors coeff (B, m, 18), T (B, m) or (m,) -> report (B, 12); asynchronous, capturable
+        (pass `report` to write into a buffer of the caller's)."""
+        import torch
+        assert coeff.is_cuda and coeff.dtype == T.dtype == torch.float64 and coeff.is_contiguous() and T.is_contiguous()
+        B, m = coeff.shape[0], coeff.shape[1]
+        if report is None:
+            report = torch.empty(B, len(self.TRAJ_REPORT), dtype=torch.float64, device=coeff.device)
+        assert report.is_contiguous() and report.dtype == torch.float64 and report.numel() == B * len(self.TRAJ_REPORT)
+        if stream is None:
+            stream = torch.cuda.current_stream(coeff.device).cuda_stream
+        self._chk(self._L.gtop_validate_trajectories_device(self._h, B, m, C.c_void_p(coeff.data_ptr()),
+                                                            C.c_void_p(T.data_ptr()), m if T.dim() == 2 else 0,
+                                                            float(dt_sample), C.byref(limits),
+                                                            C.c_void_p(report.data_ptr()), C.c_void_p(stream)))
+        return report
+
+    def select_best_device(self, report, cost, limits, want_pass=True, best=None, stream=None):
+        """report (B, 12), cost (B,) torch fp64 CUDA tensors -> (pass (B,) uint8 or None, best (2,) int32);
+        asynchronous, capturable."""
+        import torch
+        assert report.is_cuda and report.dtype == cost.dtype == torch.float64 and report.is_contiguous() and cost.is_contiguous()
+        B = cost.numel()
+        assert report.numel() == B * len(self.TRAJ_REPORT)
+        ok = torch.empty(B, dtype=torch.uint8, device=report.device) if want_pass else None
+        if best is None:
+            best = torch.empty(2, dtype=torch.int32, device=report.device)
+        if stream is None:
+            stream = torch.cuda.current_stream(report.device).cuda_stream
+        self._chk(self._L.gtop_select_best_device(self._h, B, C.c_void_p(report.data_ptr()), C.c_void_p(cost.data_ptr()),
+                                                  C.byref(limits), C.c_void_p(ok.data_ptr()) if want_pass else None,
+                                                  C.c_void_p(best.data_ptr()), C.c_void_p(stream)))
+        return ok, best
 
     # -- batched optimizer --
     @staticmethod

@@ -96,6 +96,41 @@ void GradTrajOptimizer::setStartTime(double t0) {
   last_status_ = gtop_set_start_times(ctx_, 1, &t0);
 }
 
+bool GradTrajOptimizer::validateTrajectory(const Limits &limits, Report *report) {
+  if (!ctx_ || m_ < 2 || dp_.empty()) {
+    last_status_ = GTOP_ERR_STATE;
+    return false;
+  }
+  gtop_limits lim{};
+  lim.margin = limits.margin;
+  lim.max_vel = limits.max_vel;
+  lim.max_acc = limits.max_acc;
+  lim.per_axis = limits.per_axis;
+  lim.allow_out_of_map = limits.allow_out_of_map;
+  lim.use_boxes = limits.use_boxes;
+  double r[GTOP_TRAJ_REPORT];
+  const double cost = 0.0;   // one candidate: the selection is the pass test alone
+  unsigned char pass = 0;
+  int32_t best[2] = {-1, 0};
+  last_status_ = gtop_validate_batch(ctx_, 1, dp_.data(), limits.dt_sample, &lim, &cost, r, &pass, best);
+  if (last_status_ != GTOP_OK) return false;
+  if (report) {
+    report->n_samples = (int)r[0];
+    report->clearance = r[1];
+    report->clearance_time = r[2];
+    report->clearance_index = (int)r[3];
+    report->n_below_margin = (int)r[4];
+    report->first_below_time = r[5];
+    report->n_out_of_map = (int)r[6];
+    report->max_vel_norm = r[7];
+    report->max_acc_norm = r[8];
+    report->max_vel_axis = r[9];
+    report->max_acc_axis = r[10];
+    report->time_sum = r[11];
+  }
+  return pass != 0;
+}
+
 // Common tail of setPath / setKinoPath: Df, Dp (getInitialD,
 // src/qp_generator.cpp:407-451), initial coefficients (Px = A^-1 Dx,
 // :334-336 / :134-136), then the problem goes to the device.

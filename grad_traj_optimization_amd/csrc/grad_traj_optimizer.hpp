@@ -97,6 +97,27 @@ class GradTrajOptimizer {
   void setMovingObstacles(const std::vector<Vec3> &p0, const std::vector<Vec3> &vel, const std::vector<Vec3> &scale);
   void setStartTime(double t0);
 
+  // The safety report of the trajectory at the current Dp (include/gtop.h, gtop_validate_batch; not a method of the
+  // reference's class — its planner front end tests motion primitives this way, src/kinodynamic_astar.cpp:178-213):
+  // true iff no getTraj sample lies within `margin` of an obstacle (of the boxes of setMovingObstacles too, at
+  // start time + sample time, with use_boxes), none lies out of the map unless allowed, and the velocity /
+  // acceleration maxima keep to max_vel / max_acc (<= 0: off; per_axis: the largest component, not the norm).
+  // false also when the call itself fails (ok() tells the two apart).
+  struct Limits {
+    double margin = 0.0, max_vel = 0.0, max_acc = 0.0;
+    bool per_axis = false, allow_out_of_map = false, use_boxes = false;
+    double dt_sample = 0.01;
+  };
+  struct Report {
+    int n_samples = 0;
+    double clearance = 0.0, clearance_time = 0.0;
+    int clearance_index = -1, n_below_margin = 0;
+    double first_below_time = -1.0;
+    int n_out_of_map = 0;
+    double max_vel_norm = 0.0, max_acc_norm = 0.0, max_vel_axis = 0.0, max_acc_axis = 0.0, time_sum = 0.0;
+  };
+  bool validateTrajectory(const Limits &limits, Report *report = nullptr);
+
   // extras (not in the reference)
   bool ok() const { return ctx_ != nullptr && last_status_ == GTOP_OK; }
   const char *lastError() const;

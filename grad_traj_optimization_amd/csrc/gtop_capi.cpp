@@ -19,12 +19,14 @@
 #include "gtop_guard.h"
 #include "gtop_kernels.h"
 
-#define GTOP_ABI_VERSION 4   // 4: gtop_set_moving_cost, gtop_get_moving_cost, gtop_set_start_times, gtop_set_start_times_device
+#define GTOP_ABI_VERSION 5   // 5: gtop_validate_trajectories_device, gtop_select_best_device, gtop_validate_batch
+                             // 4: gtop_set_moving_cost, gtop_get_moving_cost, gtop_set_start_times, gtop_set_start_times_device
                              // 3: gtop_set_field_sign, gtop_get_field_sign, gtop_group_set_field_sign
                              // 2: gtop_update_sdf_map_window*, gtop_set_field_precisions, gtop_device_clock_*, gtop_group_gather_note, GTOP_ERR_INTERNAL
 
 struct gtop_ctx {
   int device = 0;
+  int simds = 0;   // 4 per compute unit: sizes the trajectory report's launch
   std::string err;
   hipStream_t stream = nullptr;   // used by the host-pointer entry points
 
@@ -73,6 +75,10 @@ struct gtop_ctx {
   double *t0_own = nullptr;
   size_t cap_t0 = 0;
   int t0_count = 0;
+  void *sel_part = nullptr;  // gtop_select_best_device: the partial results of its first stage (allocated at gtop_create:
+                             // the entry point itself must not allocate)
+  double *val_rep = nullptr; // gtop_validate_batch staging: report | cost, then pass and best behind them
+  size_t cap_val = 0;
   double *d_q = nullptr;     // host-API staging of gtop_edt_query: pos | time | dist | grad
   size_t cap_q = 0;
   double *pin = nullptr;     // pinned, device-visible host staging for small host-buffer evaluations: x | cost | grad
@@ -397,12 +403,18 @@ int gtop_create(gtop_ctx **out, int device) try {
   gtop_ctx *c = new (std::nothrow) gtop_ctx();
   if (!c) return fail(nullptr, GTOP_ERR_INVALID, "gtop_create: out of memory");
   c->device = device;
+  c->simds = 4 * prop.multiProcessorCount;
   if (const char *pc = std::getenv("GTOP_POLL_COMPLETION")) c->poll_completion = std::atoi(pc) != 0;
   c->poll_sentinel = kPollSentinel;
   if (const char *ps = std::getenv("GTOP_POLL_SENTINEL")) c->poll_sentinel = std::strtoull(ps, nullptr, 16);
   if ((e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)) != hipSuccess) {
     delete c;
     return fail(nullptr, GTOP_ERR_HIP, std::string("hipStreamCreateWithFlags: ") + hipGetErrorString(e));
+  }
+  if ((e = hipMalloc(&c->sel_part, (size_t)GTOP_SELECT_PARTIALS * GTOP_SELECT_PARTIAL_BYTES)) != hipSuccess) {
+    (void)hipStreamDestroy(c->stream);
+    delete c;
+    return fail(nullptr, GTOP_ERR_HIP, std::string("hipMalloc: ") + hipGetErrorString(e));
   }
   *out = c;
   return GTOP_OK;
@@ -415,7 +427,7 @@ int gtop_destroy(gtop_ctx *c) try {
   release_sdf(c);
   void *bufs[] = {c->win_occ, c->win_dist, c->rec64, c->rec32, c->occ, c->tmp1, c->tmp2, c->rows, c->boxes, c->box_rows, c->t0_own, c->d_q, c->d_pts,
                   c->d_T, c->d_Df, c->d_x, c->d_cost, c->d_grad,
-                  c->mma_vec, c->mma_scal, c->mma_int, c->mma_f, c->mma_g, c->mma_lb, c->mma_ub, c->mma_res};
+                  c->mma_vec, c->mma_scal, c->mma_int, c->mma_f, c->mma_g, c->mma_lb, c->mma_ub, c->mma_res, c->sel_part, c->val_rep};
   for (void *p : bufs)
     if (p) (void)hipFree(p);
   if (c->pin) (void)hipHostFree(c->pin);
@@ -1127,6 +1139,97 @@ int gtop_edt_coarse_query(gtop_ctx *c, int N, const double *pos, const double *t
   HIPCHK(c, hipMemcpyAsync(dt, time, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
   if ((rc = gtop_edt_coarse_query_device(c, N, dp, dt, dd, c->stream))) return rc;
   HIPCHK(c, hipMemcpyAsync(dist, dd, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return GTOP_OK;
+} GTOP_CATCH_STATUS(c)
+
+// ---- trajectory report and selection (include/gtop.h; gtop_validate.hip) ----
+static int check_limits(gtop_ctx *c, const gtop_limits *lim) {
+  if (!lim) return fail(c, GTOP_ERR_INVALID, "validate: limits is NULL");
+  if (!std::isfinite(lim->margin) || !std::isfinite(lim->max_vel) || !std::isfinite(lim->max_acc))
+    return fail(c, GTOP_ERR_INVALID, "validate: margin, max_vel and max_acc must be finite");
+  return GTOP_OK;
+}
+
+// problem_B: the batch of gtop_set_problem when the rows are its first B (a per-trajectory start-time list of that
+// length serves them), 0 otherwise
+static int validate_on_stream(gtop_ctx *c, int B, int m, const void *d_coeff, const void *d_T, int time_stride,
+                              double dt_sample, const gtop_limits *lim, void *d_report, hipStream_t s, int problem_B) {
+  if (B < 0 || m < 1 || !(dt_sample > 0.0) || (time_stride != 0 && time_stride != m))
+    return fail(c, GTOP_ERR_INVALID, "validate: need B >= 0, m >= 1, dt_sample > 0, time_stride in {0, m}");
+  int rc;
+  if ((rc = check_limits(c, lim))) return rc;
+  const bool boxes = lim->use_boxes != 0;
+  if (c->t0_count > 1 && c->t0_count != B && c->t0_count != problem_B)
+    return fail(c, GTOP_ERR_INVALID, "validate: the number of start times does not match the batch");
+  if (!c->have_grid || !c->rec64_ok) return fail(c, GTOP_ERR_STATE, "no fp64 distance field resident");
+  if (B == 0) return GTOP_OK;
+  if (!d_coeff || !d_T || !d_report) return fail(c, GTOP_ERR_INVALID, "validate: NULL buffer");
+  HIPCHK(c, hipSetDevice(c->device));
+  const int nbox = boxes ? c->nbox : 0;
+  const size_t n3 = (size_t)c->nbox * 3;
+  const double *t0 = (boxes && c->t0_count > 0) ? c->t0_dev : nullptr;
+  HIPCHK(c, gtop_launch_traj_report(c->grid, c->rec64, nbox, c->boxes, c->boxes + n3, c->boxes + 2 * n3, B, m,
+                                    static_cast<const double *>(d_coeff), static_cast<const double *>(d_T), time_stride,
+                                    dt_sample, t0, c->t0_count > 1 ? 1 : 0, lim->margin,
+                                    static_cast<double *>(d_report), c->simds, s));
+  return GTOP_OK;
+}
+
+int gtop_validate_trajectories_device(gtop_ctx *c, int B, int m, const void *d_coeff, const void *d_T, int time_stride,
+                                      double dt_sample, const gtop_limits *limits, void *d_report,
+                                      void *hip_stream) try {
+  if (!c) return GTOP_ERR_INVALID;
+  return validate_on_stream(c, B, m, d_coeff, d_T, time_stride, dt_sample, limits, d_report,
+                            static_cast<hipStream_t>(hip_stream), 0);
+} GTOP_CATCH_STATUS(c)
+
+int gtop_select_best_device(gtop_ctx *c, int B, const void *d_report, const void *d_cost, const gtop_limits *limits,
+                            void *d_pass, void *d_best, void *hip_stream) try {
+  if (!c) return GTOP_ERR_INVALID;
+  int rc;
+  if ((rc = check_limits(c, limits))) return rc;
+  if (B < 0 || !d_best || (B > 0 && (!d_report || !d_cost)))
+    return fail(c, GTOP_ERR_INVALID, "select_best: need B >= 0, best, and report and cost for B > 0");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, gtop_launch_select_best(B, static_cast<const double *>(d_report), static_cast<const double *>(d_cost),
+                                    limits->max_vel, limits->max_acc, limits->per_axis != 0, limits->allow_out_of_map != 0,
+                                    static_cast<unsigned char *>(d_pass), static_cast<int *>(d_best), c->sel_part,
+                                    static_cast<hipStream_t>(hip_stream)));
+  return GTOP_OK;
+} GTOP_CATCH_STATUS(c)
+
+int gtop_validate_batch(gtop_ctx *c, int B, const double *x, double dt_sample, const gtop_limits *limits,
+                        const double *cost, double *report, unsigned char *pass, int32_t best[2]) try {
+  if (!c) return GTOP_ERR_INVALID;
+  if (c->B == 0) return fail(c, GTOP_ERR_STATE, "gtop_set_problem / gtop_set_paths has not been called");
+  if (B < 1 || B > c->B || !x || !report)
+    return fail(c, GTOP_ERR_INVALID, "validate_batch: 1 <= B <= problem batch, x and report required");
+  if (!(dt_sample > 0.0)) return fail(c, GTOP_ERR_INVALID, "validate_batch: dt_sample must be > 0");
+  int rc;
+  if ((rc = check_limits(c, limits))) return rc;
+  if (c->t0_count > 1 && c->t0_count != B && c->t0_count != c->B)
+    return fail(c, GTOP_ERR_INVALID, "validate: the number of start times does not match the batch");
+  if (!c->have_grid || !c->rec64_ok) return fail(c, GTOP_ERR_STATE, "no fp64 distance field resident");
+  HIPCHK(c, hipSetDevice(c->device));
+  const int m = c->m;
+  const size_t n = 9 * (size_t)(m - 1), ncoef = (size_t)B * m * 18, nrep = (size_t)B * GTOP_TRAJ_REPORT;
+  if ((rc = ensure(c, &c->mma_g, &c->cap_mma_g, ncoef > (size_t)B * n ? ncoef : (size_t)B * n))) return rc;   // coefficient scratch
+  // report | cost | best (2 x int32 in one double's room) | pass (B bytes)
+  if ((rc = ensure(c, &c->val_rep, &c->cap_val, nrep + B + 1 + (B + 7) / 8))) return rc;
+  double *d_rep = c->val_rep, *d_cost = d_rep + nrep;
+  int *d_best = reinterpret_cast<int *>(d_cost + B);
+  unsigned char *d_pass = reinterpret_cast<unsigned char *>(d_cost + B + 1);
+  HIPCHK(c, hipMemcpyAsync(c->d_x, x, (size_t)B * n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  if ((rc = gtop_coefficients_device(c, B, m, c->d_x, c->d_Df, c->d_T, c->t_stride, c->mma_g, c->stream))) return rc;
+  if ((rc = validate_on_stream(c, B, m, c->mma_g, c->d_T, c->t_stride, dt_sample, limits, d_rep, c->stream, c->B))) return rc;
+  HIPCHK(c, hipMemcpyAsync(report, d_rep, nrep * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (cost) {
+    HIPCHK(c, hipMemcpyAsync(d_cost, cost, (size_t)B * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    if ((rc = gtop_select_best_device(c, B, d_rep, d_cost, limits, d_pass, d_best, c->stream))) return rc;
+    if (pass) HIPCHK(c, hipMemcpyAsync(pass, d_pass, (size_t)B, hipMemcpyDeviceToHost, c->stream));
+    if (best) HIPCHK(c, hipMemcpyAsync(best, d_best, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  }
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return GTOP_OK;
 } GTOP_CATCH_STATUS(c)

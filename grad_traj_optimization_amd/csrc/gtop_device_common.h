@@ -1,5 +1,6 @@
 // gtop_device_common.h — device-side helpers shared by the evaluation kernel
-// (gtop_kernels.hip) and the optimizer kernels (gtop_mma.hip).
+// (gtop_kernels.hip), the optimizer kernels (gtop_mma.hip), the post-processing
+// (gtop_setup.hip) and the trajectory report (gtop_validate.hip).
 #ifndef GTOP_DEVICE_COMMON_H_
 #define GTOP_DEVICE_COMMON_H_
 
@@ -38,6 +39,27 @@ __device__ __forceinline__ R gtop_wave_sum(R v) {
   } else {
     return __builtin_bit_cast(R, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
   }
+}
+
+// value of sum_j c[j] t^j the way PolynomialTraj::evaluate forms it
+// (polynomial_traj.hpp:57-66): tv(order-1-i) = pow(t, i), pt = tv . c_descending
+// The powers by multiplication: pow(t, i) for i <= 5 is the correctly rounded t^i on the host and 1-2 ulp off
+// that in a product chain (the device's pow() is itself only within an ulp), far inside the 1e-9 the points are
+// held to — and a twelfth of the instructions: 18 pow() calls were ~95 % of this kernel (176 -> 31 us for 1 024
+// trajectories / 538 k samples).
+// (Unfused wherever it is included, as in gtop_setup.hip, whose arithmetic is the reference's: the sampling kernel and
+// the trajectory report of gtop_validate.hip get the same points, bit for bit.)
+__device__ __forceinline__ double poly_eval(const double *c, double t) {
+#pragma clang fp contract(off)
+  const double t2 = t * t, t3 = t2 * t, t4 = t2 * t2, t5 = t4 * t;
+  double s = 0.0;
+  s += t5 * c[5];   // dot over descending powers: t^5 c5 first
+  s += t4 * c[4];
+  s += t3 * c[3];
+  s += t2 * c[2];
+  s += t * c[1];
+  s += c[0];        // pow(t, 0) = 1
+  return s;
 }
 
 // ---------------------------------------------------------------------------

@@ -30,6 +30,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "gtop_edt_lookup.h"
 #include "gtop_kernels.h"
 
 namespace {
@@ -57,9 +58,7 @@ edt_query_kernel(const GtopGrid g, const double *__restrict__ field, const doubl
   __syncthreads();
   double p[3] = {xyz[3 * tid], xyz[3 * tid + 1], xyz[3 * tid + 2]};
   const double t = live ? time[i] : -1.0;
-  // isInMap, sdf_map.cpp:55-69
-  bool out = false;
-  for (int k = 0; k < 3; ++k) out |= (p[k] < g.min_range[k] + 1e-4) | (p[k] > g.max_range[k] - 1e-4);
+  const bool out = gtop_edt_out_of_map(g, p);   // isInMap, sdf_map.cpp:55-69
   const bool dyn = live & (COARSE || !out) & (t >= 0.0);
   int idx[3];
   double diff[3] = {0, 0, 0};
@@ -72,37 +71,13 @@ edt_query_kernel(const GtopGrid g, const double *__restrict__ field, const doubl
     const double v = field[((size_t)cx * g.ny + cy) * g.nz + cz];
     coarse = out ? -1.0 : v;
   } else {
-    // base index and diff, sdf_map.cpp:201-209
-    for (int k = 0; k < 3; ++k) {
-      const double pm = p[k] - 0.5 * g.res;
-      idx[k] = (int)floor((pm - g.origin[k]) * g.res_inv);
-      diff[k] = (p[k] - ((idx[k] + 0.5) * g.res + g.origin[k])) * g.res_inv;
-    }
-    // The 8 corner loads of sdf_map.cpp:211-219, each index clamped per axis (getDistance(int,int,int), :166-174),
-    // from the CORNER RECORDS (gtop_records.hip): the two consecutive records of levels iz and iz + 1 hold all eight,
-    // clamps applied — 64 contiguous bytes, four 16-byte loads at one address (round 3 read four (z, z+1) pairs from
-    // four lines: 4.24 lines of 128 bytes per query, 16 bytes used of each; now 1.25).
-    {
-      typedef double d2 __attribute__((ext_vector_type(2)));
-      const int cx = min(max(idx[0], -1), g.nx - 1) + 1, cy = min(max(idx[1], -1), g.ny - 1) + 1;
-      const int cz = min(max(idx[2], -1), g.nz - 1) + 1;
-      const d2 *r = reinterpret_cast<const d2 *>(rec + 4 * (((size_t)cx * (g.ny + 1) + cy) * (g.nz + 2) + cz));
-      const d2 q0 = r[0], q1 = r[1], q2 = r[2], q3 = r[3];
-      values[0][0][0] = q0.x; values[0][1][0] = q0.y; values[1][0][0] = q1.x; values[1][1][0] = q1.y;
-      values[0][0][1] = q2.x; values[0][1][1] = q2.y; values[1][0][1] = q3.x; values[1][1][1] = q3.y;
-    }
+    // base index, diff and the 8 corner values from the corner records: gtop_edt_lookup.h
+    gtop_edt_corners(g, rec, p, idx, diff, values);
   }
   // min over the boxes (edt_environment.cpp:26-73): at the 8 corner centres (:96-98), or at the position (:131)
   double dbox = 10000000.0;   // :64
   double vmax = 0.0;          // the largest of the 8 corner values so far
-  if constexpr (!COARSE) {
-#pragma unroll
-    for (int x = 0; x < 2; ++x)
-#pragma unroll
-      for (int y = 0; y < 2; ++y)
-#pragma unroll
-        for (int z = 0; z < 2; ++z) vmax = fmax(vmax, values[x][y][z]);
-  }
+  if constexpr (!COARSE) vmax = gtop_edt_vmax(values);
   for (int b0 = 0; b0 < nbox; b0 += kBoxChunk) {
     const int nb = min(kBoxChunk, nbox - b0);
     __syncthreads();
@@ -115,11 +90,7 @@ edt_query_kernel(const GtopGrid g, const double *__restrict__ field, const doubl
     if (dyn) {
       for (int b = 0; b < nb; ++b) {
         double bmin[3], bmax[3];
-        for (int k = 0; k < 3; ++k) {
-          const double c = bx[b][k] + bx[b][3 + k] * t;
-          bmax[k] = c + 0.5 * bx[b][6 + k];
-          bmin[k] = c - 0.5 * bx[b][6 + k];
-        }
+        gtop_edt_box_faces(bx[b], t, bmin, bmax);
         if constexpr (COARSE) {
           double d2 = 0.0;
           for (int k = 0; k < 3; ++k) {
@@ -129,35 +100,7 @@ edt_query_kernel(const GtopGrid g, const double *__restrict__ field, const doubl
           const double d = sqrt(d2);   // dist.norm()
           dbox = d < dbox ? d : dbox;
         } else {
-          // per axis and corner offset: 0 inside the slab, else the distance to its nearer face (:36-40)
-          double d1[3][2];
-          for (int k = 0; k < 3; ++k)
-            for (int o = 0; o < 2; ++o) {
-              const double pt = (idx[k] + o + 0.5) * g.res + g.origin[k];
-              d1[k][o] = (pt >= bmin[k] && pt <= bmax[k]) ? 0.0 : fmin(fabs(pt - bmin[k]), fabs(pt - bmax[k]));
-            }
-          // The corner nearest to the box takes, per axis, the smaller of the two offsets' distances, and its
-          // distance is the same floating-point expression as in the loop below; every other corner's is no
-          // smaller (sums of non-negative terms and sqrt round monotonically).  A box that does not undercut the
-          // LARGEST of the 8 current values there cannot change any of them: skipped, bit for bit the same result —
-          // with a few dozen boxes in a map most are far from a query (2^20 queries, 32 boxes: 323 -> 211 us; a
-          // wavefront still pays for a box any of its 64 queries is near).
-          const double near2 = fmin(d1[0][0], d1[0][1]) * fmin(d1[0][0], d1[0][1]) +
-                               fmin(d1[1][0], d1[1][1]) * fmin(d1[1][0], d1[1][1]) +
-                               fmin(d1[2][0], d1[2][1]) * fmin(d1[2][0], d1[2][1]);
-          if (sqrt(near2) < vmax) {
-            vmax = 0.0;
-#pragma unroll
-            for (int x = 0; x < 2; ++x)
-#pragma unroll
-              for (int y = 0; y < 2; ++y)
-#pragma unroll
-                for (int z = 0; z < 2; ++z) {
-                  const double d2 = sqrt(d1[0][x] * d1[0][x] + d1[1][y] * d1[1][y] + d1[2][z] * d1[2][z]);   // dist.norm()
-                  values[x][y][z] = d2 < values[x][y][z] ? d2 : values[x][y][z];
-                  vmax = fmax(vmax, values[x][y][z]);
-                }
-          }
+          gtop_edt_box_min(g, bmin, bmax, idx, values, vmax);   // with the exact skip
         }
       }
     }
@@ -167,13 +110,8 @@ edt_query_kernel(const GtopGrid g, const double *__restrict__ field, const doubl
     return;
   }
   // trilinear value and gradient, edt_environment.cpp:104-121 (= sdf_map.cpp:221-239)
-  const double v00 = (1 - diff[0]) * values[0][0][0] + diff[0] * values[1][0][0];
-  const double v01 = (1 - diff[0]) * values[0][0][1] + diff[0] * values[1][0][1];
-  const double v10 = (1 - diff[0]) * values[0][1][0] + diff[0] * values[1][1][0];
-  const double v11 = (1 - diff[0]) * values[0][1][1] + diff[0] * values[1][1][1];
-  const double v0 = (1 - diff[1]) * v00 + diff[1] * v10;
-  const double v1 = (1 - diff[1]) * v01 + diff[1] * v11;
-  const double d = (1 - diff[2]) * v0 + diff[2] * v1;
+  const GtopTrilinear tl = gtop_edt_trilinear(diff, values);
+  const double v00 = tl.v00, v01 = tl.v01, v10 = tl.v10, v11 = tl.v11, v0 = tl.v0, v1 = tl.v1, d = tl.d;
   double gx = (1 - diff[2]) * (1 - diff[1]) * (values[1][0][0] - values[0][0][0]);
   gx += (1 - diff[2]) * diff[1] * (values[1][1][0] - values[0][1][0]);
   gx += diff[2] * (1 - diff[1]) * (values[1][0][1] - values[0][0][1]);

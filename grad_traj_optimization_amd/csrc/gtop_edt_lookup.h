@@ -1,0 +1,115 @@
+// gtop_edt_lookup.h — the interpolating lookup of EDTEnvironment::evaluateEDTWithGrad
+// (src/edt_environment.cpp:76-122 of EpicOne1/grad_traj_optimization) as device
+// functions, shared by the batched query (gtop_edt.hip) and the trajectory report
+// (gtop_validate.hip): the in-map test, base index / diff / the 8 corner values
+// from the corner records, the min over one box with the exact skip, and the
+// trilinear value.  The library is built with -ffp-contract=on, so the same source
+// expression rounds the same way wherever it is inlined: both kernels get the same
+// distance, bit for bit.  The gradient stays with the query kernel.
+#ifndef GTOP_EDT_LOOKUP_H_
+#define GTOP_EDT_LOOKUP_H_
+
+#include <hip/hip_runtime.h>
+
+#include "gtop_kernels.h"
+
+// isInMap, sdf_map.cpp:55-69
+__device__ __forceinline__ bool gtop_edt_out_of_map(const GtopGrid &g, const double p[3]) {
+  bool out = false;
+  for (int k = 0; k < 3; ++k) out |= (p[k] < g.min_range[k] + 1e-4) | (p[k] > g.max_range[k] - 1e-4);
+  return out;
+}
+
+// base index and diff, sdf_map.cpp:201-209, and the 8 corner loads of sdf_map.cpp:211-219, each index clamped per axis
+// (getDistance(int,int,int), :166-174), from the CORNER RECORDS (gtop_records.hip): the two consecutive records of
+// levels iz and iz + 1 hold all eight, clamps applied — 64 contiguous bytes, four 16-byte loads at one address (round 3
+// read four (z, z+1) pairs from four lines: 4.24 lines of 128 bytes per query, 16 bytes used of each; now 1.25).
+__device__ __forceinline__ void gtop_edt_corners(const GtopGrid &g, const double *__restrict__ rec, const double p[3],
+                                                 int idx[3], double diff[3], double values[2][2][2]) {
+  for (int k = 0; k < 3; ++k) {
+    const double pm = p[k] - 0.5 * g.res;
+    idx[k] = (int)floor((pm - g.origin[k]) * g.res_inv);
+    diff[k] = (p[k] - ((idx[k] + 0.5) * g.res + g.origin[k])) * g.res_inv;
+  }
+  typedef double d2 __attribute__((ext_vector_type(2)));
+  const int cx = min(max(idx[0], -1), g.nx - 1) + 1, cy = min(max(idx[1], -1), g.ny - 1) + 1;
+  const int cz = min(max(idx[2], -1), g.nz - 1) + 1;
+  const d2 *r = reinterpret_cast<const d2 *>(rec + 4 * (((size_t)cx * (g.ny + 1) + cy) * (g.nz + 2) + cz));
+  const d2 q0 = r[0], q1 = r[1], q2 = r[2], q3 = r[3];
+  values[0][0][0] = q0.x; values[0][1][0] = q0.y; values[1][0][0] = q1.x; values[1][1][0] = q1.y;
+  values[0][0][1] = q2.x; values[0][1][1] = q2.y; values[1][0][1] = q3.x; values[1][1][1] = q3.y;
+}
+
+// the largest of the 8 corner values (0 at least): what a box has to undercut to matter
+__device__ __forceinline__ double gtop_edt_vmax(const double values[2][2][2]) {
+  double vmax = 0.0;
+#pragma unroll
+  for (int x = 0; x < 2; ++x)
+#pragma unroll
+    for (int y = 0; y < 2; ++y)
+#pragma unroll
+      for (int z = 0; z < 2; ++z) vmax = fmax(vmax, values[x][y][z]);
+  return vmax;
+}
+
+// the faces of box bx = {p0, vel, scale} at time t (obj_predictor.h:57-66, edt_environment.cpp:30-33)
+__device__ __forceinline__ void gtop_edt_box_faces(const double *bx, double t, double bmin[3], double bmax[3]) {
+  for (int k = 0; k < 3; ++k) {
+    const double c = bx[k] + bx[3 + k] * t;
+    bmax[k] = c + 0.5 * bx[6 + k];
+    bmin[k] = c - 0.5 * bx[6 + k];
+  }
+}
+
+// values := min(values, distance from each corner voxel's centre to the box) (edt_environment.cpp:26-73, :96-98)
+__device__ __forceinline__ void gtop_edt_box_min(const GtopGrid &g, const double bmin[3], const double bmax[3],
+                                                 const int idx[3], double values[2][2][2], double &vmax) {
+  // per axis and corner offset: 0 inside the slab, else the distance to its nearer face (:36-40)
+  double d1[3][2];
+  for (int k = 0; k < 3; ++k)
+    for (int o = 0; o < 2; ++o) {
+      const double pt = (idx[k] + o + 0.5) * g.res + g.origin[k];
+      d1[k][o] = (pt >= bmin[k] && pt <= bmax[k]) ? 0.0 : fmin(fabs(pt - bmin[k]), fabs(pt - bmax[k]));
+    }
+  // The corner nearest to the box takes, per axis, the smaller of the two offsets' distances, and its
+  // distance is the same floating-point expression as in the loop below; every other corner's is no
+  // smaller (sums of non-negative terms and sqrt round monotonically).  A box that does not undercut the
+  // LARGEST of the 8 current values there cannot change any of them: skipped, bit for bit the same result —
+  // with a few dozen boxes in a map most are far from a query (2^20 queries, 32 boxes: 323 -> 211 us; a
+  // wavefront still pays for a box any of its 64 queries is near).
+  const double near2 = fmin(d1[0][0], d1[0][1]) * fmin(d1[0][0], d1[0][1]) +
+                       fmin(d1[1][0], d1[1][1]) * fmin(d1[1][0], d1[1][1]) +
+                       fmin(d1[2][0], d1[2][1]) * fmin(d1[2][0], d1[2][1]);
+  if (sqrt(near2) < vmax) {
+    vmax = 0.0;
+#pragma unroll
+    for (int x = 0; x < 2; ++x)
+#pragma unroll
+      for (int y = 0; y < 2; ++y)
+#pragma unroll
+        for (int z = 0; z < 2; ++z) {
+          const double d2 = sqrt(d1[0][x] * d1[0][x] + d1[1][y] * d1[1][y] + d1[2][z] * d1[2][z]);   // dist.norm()
+          values[x][y][z] = d2 < values[x][y][z] ? d2 : values[x][y][z];
+          vmax = fmax(vmax, values[x][y][z]);
+        }
+  }
+}
+
+// trilinear value, edt_environment.cpp:104-112 (= sdf_map.cpp:221-229); the intermediates are what the gradient
+// (:114-121) is formed from
+struct GtopTrilinear {
+  double v00, v01, v10, v11, v0, v1, d;
+};
+__device__ __forceinline__ GtopTrilinear gtop_edt_trilinear(const double diff[3], const double values[2][2][2]) {
+  GtopTrilinear r;
+  r.v00 = (1 - diff[0]) * values[0][0][0] + diff[0] * values[1][0][0];
+  r.v01 = (1 - diff[0]) * values[0][0][1] + diff[0] * values[1][0][1];
+  r.v10 = (1 - diff[0]) * values[0][1][0] + diff[0] * values[1][1][0];
+  r.v11 = (1 - diff[0]) * values[0][1][1] + diff[0] * values[1][1][1];
+  r.v0 = (1 - diff[1]) * r.v00 + diff[1] * r.v10;
+  r.v1 = (1 - diff[1]) * r.v01 + diff[1] * r.v11;
+  r.d = (1 - diff[2]) * r.v0 + diff[2] * r.v1;
+  return r;
+}
+
+#endif  // GTOP_EDT_LOOKUP_H_

@@ -182,4 +182,21 @@ hipError_t gtop_launch_edt_query(const GtopGrid &g, const double *field, const d
                                  const double *box_vel, const double *box_scale, int N, const double *pos,
                                  const double *time, double *dist, double *grad, hipStream_t stream);
 
+// ---- trajectory report + selection (gtop_validate.hip), fp64 -----------------
+#define GTOP_TRAJ_REPORT 12   // = include/gtop.h
+// report[b] of the trajectories (coeff, T) as include/gtop.h lays it out: the getTraj samples looked up as
+// edt_query_kernel<false> looks (pos, tau) up, tau = t0[b * t0_stride] + eval_t (t0 NULL = 0) — with nbox = 0 static only
+hipError_t gtop_launch_traj_report(const GtopGrid &g, const double *rec, int nbox, const double *box_p0,
+                                   const double *box_vel, const double *box_scale, int B, int m, const double *coeff,
+                                   const double *T, int t_stride, double dt_sample, const double *t0, int t0_stride,
+                                   double margin, double *report, int simds /* of the device: sizes the launch */,
+                                   hipStream_t stream);
+// pass[b] (may be NULL) and best[2] = {passing row of least cost (lowest index on a tie, -1 if none), passing rows};
+// two launches; workspace: GTOP_SELECT_PARTIALS x GTOP_SELECT_PARTIAL_BYTES bytes of device memory
+#define GTOP_SELECT_PARTIALS 256
+#define GTOP_SELECT_PARTIAL_BYTES 16
+hipError_t gtop_launch_select_best(int B, const double *report, const double *cost, double max_vel, double max_acc,
+                                   int per_axis, int allow_out_of_map, unsigned char *pass, int *best, void *workspace,
+                                   hipStream_t stream);
+
 #endif  // GTOP_KERNELS_H_

@@ -59,24 +59,6 @@ setup_paths_kernel(int B, int m, const double *__restrict__ wp, double mean_v, d
   }
 }
 
-// value of sum_j c[j] t^j the way PolynomialTraj::evaluate forms it
-// (polynomial_traj.hpp:57-66): tv(order-1-i) = pow(t, i), pt = tv . c_descending
-// The powers by multiplication: pow(t, i) for i <= 5 is the correctly rounded t^i on the host and 1-2 ulp off
-// that in a product chain (the device's pow() is itself only within an ulp), far inside the 1e-9 the points are
-// held to — and a twelfth of the instructions: 18 pow() calls were ~95 % of this kernel (176 -> 31 us for 1 024
-// trajectories / 538 k samples).
-__device__ __forceinline__ double poly_eval(const double *c, double t) {
-  const double t2 = t * t, t3 = t2 * t, t4 = t2 * t2, t5 = t4 * t;
-  double s = 0.0;
-  s += t5 * c[5];   // dot over descending powers: t^5 c5 first
-  s += t4 * c[4];
-  s += t3 * c[3];
-  s += t2 * c[2];
-  s += t * c[1];
-  s += c[0];        // pow(t, 0) = 1
-  return s;
-}
-
 // PolynomialTraj's evaluation of one optimised trajectory (polynomial_traj.hpp:37-204), one WAVEFRONT per
 // trajectory:
 //   * getTraj / getLength (:69-92): the samples every dt_sample are spread over the lanes, 64 at a time.  The

@@ -79,8 +79,10 @@ const char *gtop_last_error(const gtop_ctx *ctx);
  * update, gtop_set_field_precisions, gtop_device_clock_*, gtop_group_gather_note,
  * GTOP_ERR_INTERNAL; 3: the signed field, gtop_set_field_sign / gtop_get_field_sign /
  * gtop_group_set_field_sign; 4: the moving-obstacle cost, gtop_set_moving_cost /
- * gtop_get_moving_cost / gtop_set_start_times / gtop_set_start_times_device; nothing
- * of an earlier version changed meaning). */
+ * gtop_get_moving_cost / gtop_set_start_times / gtop_set_start_times_device; 5: the
+ * trajectory report and selection, gtop_validate_trajectories_device /
+ * gtop_select_best_device / gtop_validate_batch; nothing of an earlier version
+ * changed meaning). */
 int gtop_abi_version(void);
 
 /* ---- configuration -------------------------------------------------- */
@@ -527,6 +529,86 @@ int gtop_set_moving_cost(gtop_ctx *ctx, int enable);
 int gtop_get_moving_cost(const gtop_ctx *ctx, int *enable);
 int gtop_set_start_times(gtop_ctx *ctx, int count, const double *t0_host);
 int gtop_set_start_times_device(gtop_ctx *ctx, int count, const void *d_t0);
+
+/* ---- trajectory safety report and best-candidate selection -------------- */
+/* (Not a PolynomialTraj method.)  Replaces what a caller assembled by hand after
+ * an optimisation: gtop_sample_trajectories_device (24 B per sample to HBM), then
+ * gtop_edt_query_device (32 B per sample back, a gradient nobody wanted), then a
+ * host or torch reduction; and the max_v / max_a of GTOP_TRAJ_STATS, which keep
+ * the reference's end-of-segment quirk (polynomial_traj.hpp:144-204) and are not
+ * the maxima along the curve.  The semantics are those of the reference's planner
+ * front end, which tests every expanded motion primitive this way
+ * (src/kinodynamic_astar.cpp:178-213): a per-axis velocity limit (:180) and
+ * evaluateCoarseEDT(pos, time) <= margin_ along the primitive (:207) — here at
+ * the samples of PolynomialTraj::getTraj (polynomial_traj.hpp:69-78: eval_t
+ * accumulated from 0 by dt_sample while eval_t <= time_sum; count, times and
+ * positions are bit for bit those of gtop_sample_trajectories_device), with the
+ * interpolating lookup of gtop_edt_query_device: a sample's distance is the
+ * `dist` that query returns for (pos, tau), bit for bit, tau = t0[b] + eval_t
+ * (one fp64 addition; t0 = the start times of gtop_set_start_times[_device],
+ * same count rules) with use_boxes set, static only (tau = -1) otherwise; out of
+ * the map it is -1.  Any number of boxes, as for the queries; a signed field is
+ * used as it is.  use_boxes is independent of gtop_set_moving_cost: validation
+ * is a query, not the cost.  Velocity and acceleration are the polynomial's
+ * first and second derivative at the sample's local time.
+ * report is B x GTOP_TRAJ_REPORT doubles per trajectory:
+ *   [0] number of samples
+ *   [1] clearance: the least distance over the samples (an out-of-map sample
+ *       contributes -1)        [2] eval_t of the first sample that attains it
+ *   [3] that sample's index
+ *   [4] number of samples with distance <= margin (out-of-map samples count
+ *       whenever margin >= -1) [5] eval_t of the first such sample, -1 if none
+ *   [6] number of samples out of the map
+ *   [7] max ||v||_2   [8] max ||a||_2   over the samples
+ *   [9] max |v_k|     [10] max |a_k|    over the samples and the three axes
+ *   [11] time_sum
+ * One wavefront per trajectory, nothing per sample goes to HBM.
+ *
+ * Selection: row b PASSES iff report[b][4] == 0, and report[b][6] == 0 unless
+ * allow_out_of_map, and max_vel <= 0 or its velocity figure <= max_vel, and
+ * max_acc <= 0 or its acceleration figure <= max_acc (per_axis: entries 9 and 10
+ * instead of 7 and 8), and cost[b] is finite.  pass[b] (uint8, may be NULL) says
+ * so; best[0] (int32) = the passing row of least cost, lowest index on a tie, -1
+ * if none passes; best[1] = the number of passing rows.  Deterministic.
+ *
+ * The _device forms only enqueue (the report one launch, the selection two): no
+ * allocation, no synchronisation, no host round trip; capturable — a captured
+ * report reads the boxes, the start times and the field as they are at replay.
+ * gtop_validate_batch serves the first B rows of the context's problem at free
+ * variables x (coefficients as gtop_trajectory_stats forms them); with cost ==
+ * NULL the selection is skipped and pass / best are left alone.
+ * Errors, nothing launched: dt_sample <= 0, a non-finite margin, max_vel or
+ * max_acc: GTOP_ERR_INVALID; a start-time count on the context that is neither
+ * 0, 1 nor B (for gtop_validate_batch the problem's batch serves too), with or
+ * without use_boxes: GTOP_ERR_INVALID; no fp64 field resident: GTOP_ERR_STATE.
+ * B = 0 is accepted by both device forms: the report launches nothing, the
+ * selection writes best = {-1, 0} (gtop_validate_batch needs B >= 1, as
+ * gtop_trajectory_stats does).
+ * The selection's first stage leaves its partial results in a small workspace
+ * the context owns (allocated by gtop_create, which fails with GTOP_ERR_HIP if
+ * that allocation fails): gtop_select_best_device calls on ONE context must be
+ * ordered with each other — the same stream, or events / graph dependencies
+ * between them; two of them in flight at once (two streams, parallel branches
+ * of a graph) race on it.  Use one context per concurrent selection.
+ * fp64 only.  The gtop_group_* entry points do not forward it; a member context
+ * can be used through gtop_group_context. */
+typedef struct {
+  double margin;            /* a sample with distance <= margin is a violation */
+  double max_vel, max_acc;  /* <= 0: that limit is off */
+  int32_t per_axis;         /* limits apply to max |v_k|, |a_k| (kinodynamic_astar.cpp:180), not to the norms */
+  int32_t allow_out_of_map; /* out-of-map samples alone do not fail a row */
+  int32_t use_boxes;        /* distances against the moving boxes at tau = t0 + eval_t */
+} gtop_limits;
+#define GTOP_TRAJ_REPORT 12
+int gtop_validate_trajectories_device(gtop_ctx *ctx, int B, int m, const void *d_coeff,
+                                      const void *d_T, int time_stride, double dt_sample,
+                                      const gtop_limits *limits, void *d_report, void *hip_stream);
+int gtop_select_best_device(gtop_ctx *ctx, int B, const void *d_report, const void *d_cost,
+                            const gtop_limits *limits, void *d_pass, void *d_best,
+                            void *hip_stream);
+int gtop_validate_batch(gtop_ctx *ctx, int B, const double *x, double dt_sample,
+                        const gtop_limits *limits, const double *cost, double *report,
+                        unsigned char *pass, int32_t best[2]);
 
 /* ---- bookkeeping the reference keeps inside the callback ------------ */
 

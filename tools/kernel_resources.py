@@ -3,7 +3,9 @@
 hipcc -Rpass-analysis=kernel-resource-usage); exits non-zero if any kernel spills — run by tests/test_capi.py, so a
 compiler or flag change that pushes a body into scratch (the hand-issued loads of the latency variant depend on the
 register allocator keeping their results where they land) is seen at build time.
-usage: tools/kernel_resources.py [--asm-out FILE] [extra hipcc flags...]"""
+usage: tools/kernel_resources.py [--asm-out FILE] [--source FILE.hip] [extra hipcc flags...]
+--source names another file of csrc/ (gtop_validate.hip, gtop_edt.hip, gtop_setup.hip, ...); the default is
+gtop_kernels.hip."""
 import os
 import re
 import subprocess
@@ -14,10 +16,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "grad_traj_optimization_amd", "csrc")
 
 
-def analyse(extra=(), asm_out="/tmp/gtop_kernels.s"):
+def analyse(extra=(), asm_out="/tmp/gtop_kernels.s", source="gtop_kernels.hip"):
+    """source: the file under csrc/ to compile (the default is the evaluation kernels' file)."""
     cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-I" + os.path.join(ROOT, "include"),
            "-I" + CSRC, "-ffp-contract=on", "-mllvm", "-amdgpu-kernarg-preload-count=10", *extra, "-x", "hip",
-           os.path.join(CSRC, "gtop_kernels.hip"), "-S", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage",
+           os.path.join(CSRC, source), "-S", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage",
            "-o", asm_out]
     t0 = time.time()
     out = subprocess.run(cmd, capture_output=True, text=True)
@@ -108,7 +111,10 @@ def main():
     asm_out = "/tmp/gtop_kernels.s"
     if args[:1] == ["--asm-out"]:
         asm_out, args = args[1], args[2:]
-    rows, secs = analyse(args, asm_out)
+    source = "gtop_kernels.hip"
+    if args[:1] == ["--source"]:
+        source, args = args[1], args[2:]
+    rows, secs = analyse(args, asm_out, source)
     bad = 0
     for r in rows:
         spill = r["scratch"] or r["vgpr_spill"]      # to memory; SGPR "spills" go to VGPR lanes (v_writelane), listed only
