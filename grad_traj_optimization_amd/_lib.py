@@ -116,6 +116,9 @@ def load_library():
         "gtop_set_moving_boxes": (C.c_int, [vp, C.c_int, dp, dp, dp]),
         "gtop_set_moving_cost": (C.c_int, [vp, C.c_int]),
         "gtop_get_moving_cost": (C.c_int, [vp, ip]),
+        "gtop_set_gradient_mode": (C.c_int, [vp, C.c_int]),
+        "gtop_get_gradient_mode": (C.c_int, [vp, ip]),
+        "gtop_group_set_gradient_mode": (C.c_int, [vp, C.c_int]),
         "gtop_set_start_times": (C.c_int, [vp, C.c_int, dp]),
         "gtop_set_start_times_device": (C.c_int, [vp, C.c_int, vp]),
         "gtop_edt_query_device": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp]),
@@ -191,7 +194,8 @@ def load_library():
     # ABI version: those stay unbound there (calling one raises AttributeError); the in-tree library must have them all.
     since = {"gtop_set_moving_cost": 4, "gtop_get_moving_cost": 4, "gtop_set_start_times": 4,
              "gtop_set_start_times_device": 4, "gtop_validate_trajectories_device": 5, "gtop_select_best_device": 5,
-             "gtop_validate_batch": 5}
+             "gtop_validate_batch": 5, "gtop_set_gradient_mode": 6, "gtop_get_gradient_mode": 6,
+             "gtop_group_set_gradient_mode": 6}
     L.gtop_abi_version.restype = C.c_int
     abi = L.gtop_abi_version() if os.environ.get("GTOP_HIP_LIB") else max(since.values())
     for name, (res, args) in sig.items():
@@ -507,6 +511,22 @@ class GtopContext:
         on = C.c_int(0)
         self._chk(self._L.gtop_get_moving_cost(self._h, C.byref(on)))
         return bool(on.value)
+
+    # -- gradient mode (include/gtop.h: not in the reference) --
+    GRADIENT_REFERENCE, GRADIENT_CONSISTENT = 0, 1
+
+    def set_gradient_mode(self, consistent=True):
+        """Which gradient every evaluation and optimizer run of this context returns / uses: the reference's callback
+        line by line (False, the default: a drop-in reproduces the reference's iterates) or the gradient of the cost as
+        returned (True: the one to optimise with).  The cost is the same bit for bit (include/gtop.h,
+        gtop_set_gradient_mode)."""
+        self._chk(self._L.gtop_set_gradient_mode(self._h, self.GRADIENT_CONSISTENT if consistent else self.GRADIENT_REFERENCE))
+
+    @property
+    def gradient_mode(self):
+        mode = C.c_int(0)
+        self._chk(self._L.gtop_get_gradient_mode(self._h, C.byref(mode)))
+        return int(mode.value)
 
     def set_start_times(self, t0=None):
         """The trajectories' start times on the boxes' clock: None = all zero, a scalar = one shared value, else one
@@ -828,6 +848,10 @@ class GtopGroup:
         d.update(kw)
         p = GtopParams(**d)
         self._chk(self._L.gtop_group_set_params(self._h, C.byref(p)))
+
+    def set_gradient_mode(self, consistent=True):
+        """GtopContext.set_gradient_mode on every member."""
+        self._chk(self._L.gtop_group_set_gradient_mode(self._h, 1 if consistent else 0))
 
     def set_field_sign(self, signed=True, max_depth=0.0):
         """GtopContext.set_field_sign on every member."""

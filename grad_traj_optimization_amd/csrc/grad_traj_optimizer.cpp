@@ -65,6 +65,7 @@ void GradTrajOptimizer::pushParams() {
   p.step = step_;
   p.enable_dyn = cfg_.enable_dyn;
   last_status_ = gtop_set_params(ctx_, &p);
+  if (last_status_ == GTOP_OK) last_status_ = gtop_set_gradient_mode(ctx_, cfg_.gradient_mode);
 }
 
 void GradTrajOptimizer::initSDFMap(Vec3 map_size_3d, Vec3 origin, double resolution) {
@@ -397,6 +398,7 @@ bool GradTrajBatch::optimizeTrajectories(int step) {
   p.step = step;
   p.enable_dyn = cfg_.enable_dyn;
   if ((last_status_ = gtop_group_set_params(grp_, &p)) != GTOP_OK) return true;
+  if ((last_status_ = gtop_group_set_gradient_mode(grp_, cfg_.gradient_mode)) != GTOP_OK) return true;
   for (int i = 0; i < gtop_group_size(grp_); ++i)
     gtop_set_optimizer_precision(gtop_group_context(grp_, i), cfg_.optimizer_fp32 ? GTOP_F32 : GTOP_F64);
   const double maxtime = step == OPT_FIRST_STEP ? cfg_.time_limit_1 : (step == OPT_SECOND_STEP ? cfg_.time_limit_2 : 0.0);

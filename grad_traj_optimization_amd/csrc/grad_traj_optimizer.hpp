@@ -69,6 +69,10 @@ class GradTrajOptimizer {
     // the device optimizer's evaluations in fp32 (gtop_set_optimizer_precision; its state and results stay fp64):
     // for large batches through GradTrajBatch; needs the device optimizer (optimize_on_device, or GradTrajBatch)
     int optimizer_fp32 = 0;
+    // which gradient the cost function and the device optimizer use (include/gtop.h, gtop_set_gradient_mode):
+    // 0 = GTOP_GRADIENT_REFERENCE, the reference's callback line by line (its iterates); 1 = GTOP_GRADIENT_CONSISTENT,
+    // the gradient of the cost as returned — the one to optimise with
+    int gradient_mode = 0;
   };
 
   GradTrajOptimizer();

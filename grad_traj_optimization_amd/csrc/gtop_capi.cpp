@@ -19,7 +19,8 @@
 #include "gtop_guard.h"
 #include "gtop_kernels.h"
 
-#define GTOP_ABI_VERSION 5   // 5: gtop_validate_trajectories_device, gtop_select_best_device, gtop_validate_batch
+#define GTOP_ABI_VERSION 6   // 6: gtop_set_gradient_mode, gtop_get_gradient_mode, gtop_group_set_gradient_mode
+                             // 5: gtop_validate_trajectories_device, gtop_select_best_device, gtop_validate_batch
                              // 4: gtop_set_moving_cost, gtop_get_moving_cost, gtop_set_start_times, gtop_set_start_times_device
                              // 3: gtop_set_field_sign, gtop_get_field_sign, gtop_group_set_field_sign
                              // 2: gtop_update_sdf_map_window*, gtop_set_field_precisions, gtop_device_clock_*, gtop_group_gather_note, GTOP_ERR_INTERNAL
@@ -69,6 +70,7 @@ struct gtop_ctx {
   // p0, vel, scale / 2 in a buffer of GTOP_MOVING_COST_MAX_BOXES rows allocated once (its address is what a captured
   // launch holds) and rewritten by gtop_set_moving_boxes — and the start times on the boxes' clock
   int moving_cost = 0;
+  int grad_mode = GTOP_GRADIENT_REFERENCE;   // gtop_set_gradient_mode: read by every evaluation / optimizer call as it is made
   double *box_rows = nullptr;
   bool box_rows_ok = false;        // the list fits and every box is finite with a non-negative extent
   const double *t0_dev = nullptr;  // count > 0: owned (t0_own) or borrowed
@@ -341,6 +343,7 @@ int launch_eval(gtop_ctx *c, const R *sdf, int B, int m, const void *d_x, const 
       else if (!gtop_eval_plan_moving(B, m, c->spl, false, &plan))
         return fail(c, GTOP_ERR_INVALID, "moving-obstacle cost: no body for this launch geometry / length (samples_per_lane "
                                          "10 and 30, 3 with more than 6 segments; one wavefront's LDS: 227 segments)");
+      plan.consistent = c->grad_mode == GTOP_GRADIENT_CONSISTENT;
       HIPCHK(c, gtop_launch_eval_moving(a, plan, c->prm.enable_dyn != 0, mov, stream));
       return GTOP_OK;
     }
@@ -359,6 +362,7 @@ int launch_eval(gtop_ctx *c, const R *sdf, int B, int m, const void *d_x, const 
   else if (!gtop_eval_plan(B, m, sizeof(R), c->spl, false, &plan))
     return fail(c, GTOP_ERR_INVALID, "this many segments cannot be served (ten lanes per segment: up to 6 segments; "
                                      "one wavefront's LDS: 227)");
+  plan.consistent = c->grad_mode == GTOP_GRADIENT_CONSISTENT;
   HIPCHK(c, gtop_launch_eval<R>(a, plan, c->prm.enable_dyn != 0, stream));
   return GTOP_OK;
 }
@@ -1042,6 +1046,20 @@ int gtop_get_moving_cost(const gtop_ctx *c, int *enable) {
   return GTOP_OK;
 }
 
+int gtop_set_gradient_mode(gtop_ctx *c, int mode) {
+  if (!c) return GTOP_ERR_INVALID;
+  if (mode != GTOP_GRADIENT_REFERENCE && mode != GTOP_GRADIENT_CONSISTENT)
+    return fail(c, GTOP_ERR_INVALID, "gradient mode: must be GTOP_GRADIENT_REFERENCE (0) or GTOP_GRADIENT_CONSISTENT (1)");
+  c->grad_mode = mode;
+  return GTOP_OK;
+}
+
+int gtop_get_gradient_mode(const gtop_ctx *c, int *mode) {
+  if (!c || !mode) return GTOP_ERR_INVALID;
+  *mode = c->grad_mode;
+  return GTOP_OK;
+}
+
 int gtop_set_start_times(gtop_ctx *c, int count, const double *t0_host) try {
   if (!c) return GTOP_ERR_INVALID;
   if (count < 0) return fail(c, GTOP_ERR_INVALID, "set_start_times: count < 0");
@@ -1294,6 +1312,7 @@ static int optimize_device_impl(gtop_ctx *c, int B, int m, void *d_x, const void
   if (!planned)
     return fail(c, GTOP_ERR_INVALID, "optimize: this many segments cannot be served (ten lanes per segment: up to 6; "
                                      "one wavefront's LDS with the optimizer's state: 118)");
+  plan.consistent = c->grad_mode == GTOP_GRADIENT_CONSISTENT;   // (the separate-update form's evaluations take the plan too)
   const bool fused = c->fuse_mma != 0;
   const bool resident = c->fuse_mma == 2;   // one launch runs all max_evals evaluations of every trajectory
   st.iters = resident ? max_evals : 1;

@@ -318,6 +318,12 @@ int gtop_group_set_params(gtop_group *g, const gtop_params *p) try {
   return GTOP_OK;
 } GTOP_CATCH_STATUS(g)
 
+int gtop_group_set_gradient_mode(gtop_group *g, int mode) try {
+  if (!g) return GTOP_ERR_INVALID;
+  for (Member &mb : g->mem) GCTX(g, mb, gtop_set_gradient_mode(mb.ctx, mode));
+  return GTOP_OK;
+} GTOP_CATCH_STATUS(g)
+
 int gtop_group_set_field_sign(gtop_group *g, int signed_mode, double max_depth) try {
   if (!g) return GTOP_ERR_INVALID;
   for (Member &mb : g->mem) GCTX(g, mb, gtop_set_field_sign(mb.ctx, signed_mode, max_depth));

@@ -67,6 +67,9 @@ struct GtopEvalPlan {
   int spl, nt;
   bool is_long;
   int nw;   // wavefronts per trajectory: 2 for 7 .. 12 segments at ten lanes per segment (small batches), else 1
+  // which gradient the bodies compute (gtop_set_gradient_mode): 0 the reference's callback, 1 the consistent one.  The
+  // launch rule leaves it 0 and does not look at it — both modes have a body for every geometry; the caller sets it.
+  int consistent;
 };
 // The launch rule.  pinned_spl: 0 = auto, 3 or 6; for_optimizer: the optimizer loop and the evaluations of its
 // multi-launch forms (the same rule with the loop's own switch point to two trajectories per wavefront).  false: the request cannot be served (m < 2, spl 3 with more than 6
@@ -75,6 +78,10 @@ bool gtop_eval_plan(int B, int m, size_t elem, int pinned_spl, bool for_optimize
 // dyn: enable_dyn (the kernel applies it at step 2 only, as the commented-out block would)
 template <typename R>
 hipError_t gtop_launch_eval(const GtopKernelArgs<R> &args, const GtopEvalPlan &plan, bool dyn, hipStream_t stream);
+// The consistent-gradient bodies live in an object of their own (gtop_kernels.hip compiled with -DGTOP_CONSISTENT_TU);
+// the *_consistent launchers are that object's and are called by the launchers of the same name only.
+template <typename R>
+hipError_t gtop_launch_eval_consistent(const GtopKernelArgs<R> &args, const GtopEvalPlan &plan, bool dyn, hipStream_t stream);
 
 // ---- the moving-obstacle term (gtop_set_moving_cost): the lookup of every collision sample becomes
 // evaluateEDTWithGrad(pos, tau), the 8 corner values min'ed with the distance to the nearest box at the sample's
@@ -92,6 +99,11 @@ hipError_t gtop_launch_eval_moving(const GtopKernelArgs<double> &args, const Gto
                                    const GtopMovingArgs &mov, hipStream_t stream);
 hipError_t gtop_launch_eval_mma_moving(const GtopKernelArgs<double> &args, const GtopMmaState &st, const GtopEvalPlan &plan,
                                        bool dyn, const GtopMovingArgs &mov, hipStream_t stream);
+hipError_t gtop_launch_eval_moving_consistent(const GtopKernelArgs<double> &args, const GtopEvalPlan &plan, bool dyn,
+                                              const GtopMovingArgs &mov, hipStream_t stream);
+hipError_t gtop_launch_eval_mma_moving_consistent(const GtopKernelArgs<double> &args, const GtopMmaState &st,
+                                                  const GtopEvalPlan &plan, bool dyn, const GtopMovingArgs &mov,
+                                                  hipStream_t stream);
 
 // `bytes` from src to each of the first n_dsts pointers of `dsts` (device memory of this or of a peer GPU mapped into
 // this process; 16-byte aligned), one kernel: gtop_push.hip
@@ -159,6 +171,10 @@ hipError_t gtop_launch_eval_mma(const GtopKernelArgs<double> &args, const GtopMm
                                 bool dyn, hipStream_t stream);
 hipError_t gtop_launch_eval_mma(const GtopKernelArgs<float> &args, const GtopMmaState &st, const GtopEvalPlan &plan,
                                 bool dyn, hipStream_t stream);
+hipError_t gtop_launch_eval_mma_consistent(const GtopKernelArgs<double> &args, const GtopMmaState &st,
+                                           const GtopEvalPlan &plan, bool dyn, hipStream_t stream);
+hipError_t gtop_launch_eval_mma_consistent(const GtopKernelArgs<float> &args, const GtopMmaState &st,
+                                           const GtopEvalPlan &plan, bool dyn, hipStream_t stream);
 hipError_t gtop_launch_mma_init(const GtopMmaState &st, int B, int n, const double *x0, hipStream_t stream);
 hipError_t gtop_launch_mma_update(const GtopMmaState &st, int B, int n, const double *fcur, const double *gcur,
                                   hipStream_t stream);

@@ -53,6 +53,9 @@ constexpr int red_stride(int spl) {
   return busy | 1;
 }
 
+#if defined(GTOP_STAMPS) && defined(GTOP_CONSISTENT_TU)
+#undef GTOP_STAMPS   // (the stamps are the reference-mode object's)
+#endif
 // Diagnostic build (-DGTOP_STAMPS): s_memtime at the phase boundaries of lane 0
 // of wave 0 of the first 4096 workgroups, into a buffer of its own that nothing
 // else reads.  Never defined in the shipped library.
@@ -553,7 +556,10 @@ __device__ __forceinline__ f2 sdf_query_pair(const GtopKernelArgs<float> &a, con
 // double; the sample times in double), rounded to `float` (:457-465) — and the cell they fall in is found in double
 // (sdf_query_pair), so the fp32 path reads the same cells and decides out-of-map the same way as the fp64 path and
 // the reference on the same inputs.  Everything else — velocity, blend, penalty, accumulation — is packed fp32.
-template <bool DYN, bool WIDE>
+// CONS (gtop_set_gradient_mode(GTOP_GRADIENT_CONSISTENT)): the gradient of the cost as returned — the collision weight
+// without its spurious factor cd, and in the DYN block sgn(v), sgn(a) and the sum of the three axes' penalties on the
+// d|v|/dx term (see the fp64 path of gtop_eval_wave_kernel).  The cost accumulator is untouched.
+template <bool DYN, bool WIDE, bool CONS>
 __device__ __forceinline__ void sample_pair_f32(const GtopKernelArgs<float> &a, const IndexBox &box, const double (&qd)[3][6],
                                                 const float *cq, double tA, double tB, bool liveA, bool liveB, float wdt,
                                                 float dt, f2 (&acc2)[kRedVals]) {
@@ -597,7 +603,9 @@ __device__ __forceinline__ void sample_pair_f32(const GtopKernelArgs<float> &a, 
   const f2 cd = splat(a.alpha) * e;                // :509
   const f2 gd = splat(-a.alpha_over_r) * e;        // :514
   f2 csum = splat(wdt) * (cd * vn);                // :373
-  f2 f1 = splat(wdt * a.res_inv) * (gd * cd * vn);   // 1/res: g3 is per voxel
+  f2 f1;                                             // 1/res: g3 is per voxel
+  if constexpr (CONS) f1 = splat(wdt * a.res_inv) * (gd * vn);   // d(cd vn dt)/dp = gd grad vn dt (e is 0 past the loop bound)
+  else f1 = splat(wdt * a.res_inv) * (gd * cd * vn);
   const f2 f2_ = splat(wdt) * (cd * ivn);
   if (outA) f1.x = 0.0f;
   if (outB) f1.y = 0.0f;
@@ -621,11 +629,23 @@ __device__ __forceinline__ void sample_pair_f32(const GtopKernelArgs<float> &a, 
     }
     const f2 sdt = {liveA ? dt : 0.0f, liveB ? dt : 0.0f};   // every term of the block carries dt; 0 past the loop bound
     csum += (splat(a.alpha_v) * ((ev[0] + ev[1]) + ev[2]) + splat(a.alpha_a) * ((ea[0] + ea[1]) + ea[2])) * vn * sdt;
+    if constexpr (CONS) {
+      // S = sum over the axes of cv + ca on the d|v|/dx term, sgn(v), sgn(a) (sgn(+-0) = 0) on the penalties' own
+      const f2 call = (splat(a.alpha_v) * ((ev[0] + ev[1]) + ev[2]) + splat(a.alpha_a) * ((ea[0] + ea[1]) + ea[2])) * ivn;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        const f2 sv = {(float)((vel[k].x > 0.0f) - (vel[k].x < 0.0f)), (float)((vel[k].y > 0.0f) - (vel[k].y < 0.0f))};
+        const f2 sa = {(float)((acc3[k].x > 0.0f) - (acc3[k].x < 0.0f)), (float)((acc3[k].y > 0.0f) - (acc3[k].y < 0.0f))};
+        w2[k] += (splat(a.gv_scale) * ev[k] * sv * vn + call * vel[k]) * sdt;
+        w3[k] = (splat(a.ga_scale) * ea[k] * sa * vn) * sdt;
+      }
+    } else {
     const f2 clast = (splat(a.alpha_v) * ev[2] + splat(a.alpha_a) * ea[2]) * ivn;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
       w2[k] += (splat(a.gv_scale) * ev[k] * vn + clast * vel[k]) * sdt;
       w3[k] = (splat(a.ga_scale) * ea[k] * vn) * sdt;
+    }
     }
   }
 #pragma unroll
@@ -756,6 +776,15 @@ template <typename Base> struct GtopMoving : Base {
 template <typename MM> constexpr bool kIsMov = false;
 template <typename Base> constexpr bool kIsMov<GtopMoving<Base>> = true;
 template <typename MM> constexpr bool kIsMma = std::is_base_of<GtopMmaState, MM>::value;
+// CONS, the consistent gradient (gtop_set_gradient_mode(GTOP_GRADIENT_CONSISTENT)): carried by MM as MOV is —
+// GtopConsistent<GtopNoMma>, GtopConsistent<GtopMmaState>, GtopConsistent<GtopMoving<...>>, an empty wrapper — so that
+// the reference-mode bodies keep their template arguments, their kernel arguments, their names and their code.  It
+// changes the gradient weights of the sample loop only (stage B below; sample_pair_f32); a launch without a collision
+// term (:346) has no such body and runs the reference one.
+template <typename Base> struct GtopConsistent : Base {};
+template <typename MM> constexpr bool kIsCons = false;
+template <typename Base> constexpr bool kIsCons<GtopConsistent<Base>> = true;
+template <typename Base> constexpr bool kIsMov<GtopConsistent<Base>> = kIsMov<Base>;
 // DYN compiles in the velocity / acceleration penalties the reference has commented out
 // (src/grad_traj_optimizer.cpp:383-407, formulas :517-535; they sit inside the collision sample loop, so DYN needs
 // COLLI; the launcher picks DYN only for enable_dyn at step 2, as the block's own `step == 2` test would).
@@ -791,6 +820,8 @@ gtop_eval_wave_kernel(const R *__restrict__ arg_x, const R *__restrict__ arg_Df,
                       const GtopSetupConsts<R> KD) {
   constexpr bool MMA = kIsMma<MM>;
   constexpr bool MOV = kIsMov<MM>;
+  constexpr bool CONS = kIsCons<MM>;
+  static_assert(!CONS || COLLI, "the consistent gradient differs in the sample loop only");
   static_assert(!MMA || NT == 1 || (SPL == 6 && !LONG), "the optimizer loop: one trajectory per wavefront, or two at five lanes per segment");
   // the optimizer's state, bounds, Df and T are fp64 whatever R is: with R = float only the evaluation runs in fp32
   // (its inputs converted as they are read from LDS, its cost and gradient widened for the update)
@@ -1127,10 +1158,12 @@ gtop_eval_wave_kernel(const R *__restrict__ arg_x, const R *__restrict__ arg_Df,
     };
     const R aw_all = pen_alpha * wdt;
     // (sdt: the sample's own dt, zero past the loop bound — the factor every DYN term carries; unused otherwise)
-    auto sample_time = [&](int j, TT &t, R &awj, R &sdt) {
+    // (wdj, CONS only: wc times the sample's dt, zero past the loop bound — the collision gradient's weight without cd)
+    auto sample_time = [&](int j, TT &t, R &awj, R &sdt, [[maybe_unused]] R &wdj) {
       t = (TT)(li + j * LPS) * dtt + (TT)1e-3;
       awj = aw_all;
       sdt = dt;
+      if constexpr (CONS) wdj = wdt;
       if (any_tiny) {
         if (tiny_T) {
           const TT dtq = tiny_dt();
@@ -1138,6 +1171,7 @@ gtop_eval_wave_kernel(const R *__restrict__ arg_x, const R *__restrict__ arg_Df,
           for (int i = 0; i < li + j * LPS; ++i) t += dtq;
           awj = (t < Tt) ? pen_alpha * (wc * (R)dtq) : (R)0;
           sdt = (t < Tt) ? (R)dtq : (R)0;
+          if constexpr (CONS) wdj = (t < Tt) ? wc * (R)dtq : (R)0;
           // a sample past the loop bound (:353) is not evaluated by the reference; here it is, with weight 0 — at the
           // first sample's time rather than on the extrapolated polynomial, where an exp could overflow into 0 * inf
           t = (t < Tt) ? t : (TT)1e-3;
@@ -1148,12 +1182,14 @@ gtop_eval_wave_kernel(const R *__restrict__ arg_x, const R *__restrict__ arg_Df,
     TT ts[NTS];
     R aw[NTS];
     [[maybe_unused]] R sdts[NTS];
+    [[maybe_unused]] R wds[NTS];
     if constexpr (MINW <= 2) {
 #pragma unroll
       for (int j = 0; j < SPL; ++j) {
         ts[j] = (TT)(li + j * LPS) * dtt + (TT)1e-3;
         aw[j] = aw_all;
         sdts[j] = dt;
+        if constexpr (CONS) wds[j] = wdt;
       }
       if (any_tiny) {   // ONE wave-uniform branch for all of the lane's samples: the addition chain runs on from one to the next
         if (tiny_T) {
@@ -1166,6 +1202,7 @@ gtop_eval_wave_kernel(const R *__restrict__ arg_x, const R *__restrict__ arg_Df,
             ts[j] = (t < Tt) ? t : (TT)1e-3;   // (past the loop bound: weight 0, evaluated at the first sample's time; see sample_time)
             aw[j] = (t < Tt) ? pen_alpha * (wc * (R)dtq) : (R)0;
             sdts[j] = (t < Tt) ? (R)dtq : (R)0;
+            if constexpr (CONS) wds[j] = (t < Tt) ? wc * (R)dtq : (R)0;
           }
         }
       }
@@ -1195,11 +1232,14 @@ gtop_eval_wave_kernel(const R *__restrict__ arg_x, const R *__restrict__ arg_Df,
 #pragma unroll 1
       for (int jj = 0; jj < SPL; jj += 2) {
         TT tA, tB;
-        R awA, awB, sdA, sdB;
-        sample_time(jj, tA, awA, sdA);
-        sample_time(jj + 1, tB, awB, sdB);
+        // (wdA, wdB are not used: the packed path weights every live sample with the segment's one (float)(wc * dt), in
+        // both modes — T * (1/30) and the replay's quotient T / 30 differ by a double ulp, which the cast to float
+        // absorbs, and `live` clears the terms of a sample past the loop bound)
+        R awA, awB, sdA, sdB, wdA, wdB;
+        sample_time(jj, tA, awA, sdA, wdA);
+        sample_time(jj + 1, tB, awB, sdB, wdB);
         // (live = inside the loop bound of :353; without DYN every term carries alpha, so alpha*wc*dt != 0 says the same)
-        sample_pair_f32<DYN, WIDE>(reinterpret_cast<const GtopKernelArgs<float> &>(a), ibox, qd, cq, tA, tB,
+        sample_pair_f32<DYN, WIDE, CONS>(reinterpret_cast<const GtopKernelArgs<float> &>(a), ibox, qd, cq, tA, tB,
                                    DYN ? sdA != (R)0 : awA != (R)0, DYN ? sdB != (R)0 : awB != (R)0, (float)wdt,
                                    (float)dt, acc2);
       }
@@ -1214,7 +1254,7 @@ gtop_eval_wave_kernel(const R *__restrict__ arg_x, const R *__restrict__ arg_Df,
       [[maybe_unused]] R accs[CH][3];
       SdfTap<R> taps[CH];
       gtop_d2 raw[ASMLD ? CH : 1][4];
-      if constexpr (MINW > 2) sample_time(j0, ts[0], aw[0], sdts[0]);
+      if constexpr (MINW > 2) sample_time(j0, ts[0], aw[0], sdts[0], wds[0]);
       // The position of a sample (:457-465, sums in the reference's order) goes through `float` (the reference's
       // local), so isInMap's double comparisons (sdf_map.cpp:55-69) are decided exactly by float comparisons against
       // the bounds rounded INTO the box (a.lo_f = the smallest float >= lo, a.hi_f = the largest <= hi: for a float p,
@@ -1358,7 +1398,10 @@ gtop_eval_wave_kernel(const R *__restrict__ arg_x, const R *__restrict__ arg_Df,
         const R cv = cdw * vn;
         acc[18] = gfma(cdw, vn, acc[18]);   // += cv: :373, weighted as in :417-418 (fusions are spelled out: -ffp-contract=on)
         // g_colli.row(k) += (gd*grad(k)*cd*vn * T*Ldp + cd*(vel(k)/vn) * T*V*Ldp) * dt   (:376-381); gd of :514
-        R f1 = ((pen_gd * a.res_inv) * e) * cv;   // (out of the map, rare-branch form: g3 = 0)
+        // CONS: the derivative of the cost term cd(dist) vn dt — gd*grad(k)*vn, the factor cd of :376 is not in it
+        R f1;   // (out of the map, rare-branch form: g3 = 0)
+        if constexpr (CONS) f1 = ((pen_gd * a.res_inv) * e) * (wds[MINW <= 2 ? j0 + c : 0] * vn);
+        else f1 = ((pen_gd * a.res_inv) * e) * cv;
         if constexpr (!kRareOut) f1 = outs[c] ? (R)0 : f1;   // grad := 0
         const R f2 = cdw * ivn;
         const R d2 = (R)2 * t, d3 = K.k3 * t2, d4 = (R)4 * t3, d5 = K.k5 * t4;
@@ -1378,11 +1421,23 @@ gtop_eval_wave_kernel(const R *__restrict__ arg_x, const R *__restrict__ arg_Df,
           }
           const R csum_dyn = a.alpha_v * ((ev[0] + ev[1]) + ev[2]) + a.alpha_a * ((ea[0] + ea[1]) + ea[2]);
           acc[18] = gfma(csum_dyn * vn, sdt, acc[18]);
+          if constexpr (CONS) {
+            // the derivative of that cost: d|v_k| = sgn(v_k), d|a_k| = sgn(a_k) (sgn(+-0) = 0: an idle axis gets no
+            // push), and d vn/dv_k = v_k/vn carries the SUM of the three axes' penalties
+            const R call = csum_dyn * ivn;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+              const R sv = (R)((vel[k] > (R)0) - (vel[k] < (R)0)), sa = (R)((acc3[k] > (R)0) - (acc3[k] < (R)0));
+              dw2[k] = (a.gv_scale * ev[k] * sv * vn + call * vel[k]) * sdt;
+              dw3[k] = (a.ga_scale * ea[k] * sa * vn) * sdt;
+            }
+          } else {
           const R clast = (a.alpha_v * ev[2] + a.alpha_a * ea[2]) * ivn;
 #pragma unroll
           for (int k = 0; k < 3; ++k) {
             dw2[k] = (a.gv_scale * ev[k] * vn + clast * vel[k]) * sdt;
             dw3[k] = (a.ga_scale * ea[k] * vn) * sdt;          // on T*V*V = [0, 0, 2, 6t, 12t^2, 20t^3]
+          }
           }
         }
 #pragma unroll
@@ -1602,8 +1657,21 @@ gtop_eval_wave_kernel(const R *__restrict__ arg_x, const R *__restrict__ arg_Df,
 
 }  // namespace
 
+// This file is compiled TWICE (csrc/Makefile): as it stands — every reference-mode body, the launch rule, the launchers
+// the C-ABI layer calls — and with -DGTOP_CONSISTENT_TU into an object of its own that holds the consistent-gradient
+// bodies (MM wrapped in GtopConsistent) behind launchers named *_consistent, which the launchers of the first object
+// forward to when the plan asks for that mode.  Two objects so that the two sets of bodies compile side by side and
+// the reference-mode object is the same code, instruction for instruction, as before the mode existed.
+#ifdef GTOP_CONSISTENT_TU
+template <typename MM> using GtopModeOf = GtopConsistent<MM>;
+#define GTOP_LAUNCHER(name) name##_consistent
+#else
+template <typename MM> using GtopModeOf = MM;
+#define GTOP_LAUNCHER(name) name
+#endif
+
 // WIDE = false needs 24-bit (signed) multiplicands and corner records below 4 GiB (record_loads)
-bool gtop_field_is_narrow(int nx, int ny, int nz, size_t elem) {
+static bool gtop_field_is_narrow(int nx, int ny, int nz, size_t elem) {
   const unsigned long long nrec = (unsigned long long)(nx + 1) * (ny + 1) * (nz + 2);
   return (unsigned long long)(nx + 1) * (ny + 1) < (1ull << 23) && nz + 2 < (1 << 23) && nrec * 4 * elem < (1ull << 32);
 }
@@ -1666,6 +1734,7 @@ static size_t wave_lds_bytes(const GtopEvalPlan &p, int m, size_t elem, bool mma
 // follows the same rule with its own switch points (elem: the precision of its evaluations).  pinned_spl = 3 or 6 overrides the lanes-per-segment choice where it can
 // be honoured (3: up to 6 segments; 30 = one lane per segment: up to 12 segments, plain evaluations; by itself the rule
 // takes it for fp32 batches of 65 536 six-segment trajectories and more).
+#ifndef GTOP_CONSISTENT_TU
 bool gtop_eval_plan(int B, int m, size_t elem, int pinned_spl, bool for_optimizer, GtopEvalPlan *plan) {
   if (m < 2 || (pinned_spl != 0 && pinned_spl != 3 && pinned_spl != 6 && pinned_spl != 10 && pinned_spl != 30)) return false;
   GtopEvalPlan p{};
@@ -1755,13 +1824,14 @@ bool gtop_eval_plan_moving(int B, int m, int pinned_spl, bool for_optimizer, Gto
   int pin = pinned_spl;
   if (pin == 0)
     pin = m <= 6 ? (B >= (for_optimizer ? GTOP_OPT_TWO_PER_WAVE_F64_FROM : GTOP_TWO_PER_WAVE_F64_FROM) ? 6 : 3) : 6;
-  GtopEvalPlan p;
+  GtopEvalPlan p{};
   if (!gtop_eval_plan(B, m, sizeof(double), pin, for_optimizer, &p)) return false;
   if (for_optimizer && p.nt == 2 && !gtop_eval_plan(B, m, sizeof(double), 3, true, &p)) return false;
   if (p.nw != 1 || (p.spl != 3 && p.spl != 6)) return false;
   *plan = p;
   return true;
 }
+#endif  // GTOP_CONSISTENT_TU
 
 namespace {
 
@@ -1772,14 +1842,17 @@ using WaveKernelFn = void (*)(const R *, const R *, const R *, const R *, int, i
 // one geometry: the collision-free, the ordinary and the DYN instantiation (DYN: one sample at a time, MINW >= 3)
 template <typename R, bool WIDE, int SPL, int NT, int MINW, typename MM, bool LONG, int NW = 1>
 static WaveKernelFn<R, MM> pick_body(bool colli, bool dyn) {
-  if (!colli) return gtop_eval_wave_kernel<R, WIDE, SPL, NT, false, MINW, MM, false, LONG, NW>;   // (:346: no sample loop, no DYN)
+  if (!colli) {   // (:346: no sample loop, no DYN — and no consistent-gradient body: the launchers run the reference one)
+    if constexpr (kIsCons<MM>) return nullptr;
+    else return gtop_eval_wave_kernel<R, WIDE, SPL, NT, false, MINW, MM, false, LONG, NW>;
+  }
   if (dyn) return gtop_eval_wave_kernel<R, WIDE, SPL, NT, true, (MINW < 3 ? 3 : MINW), MM, true, LONG, NW>;
   return gtop_eval_wave_kernel<R, WIDE, SPL, NT, true, MINW, MM, false, LONG, NW>;
 }
 
 template <typename R, bool WIDE, typename MM>
 static WaveKernelFn<R, MM> pick_geometry(const GtopEvalPlan &p, int B, bool colli, bool dyn) {
-  constexpr bool MMA = !std::is_same<MM, GtopNoMma>::value;
+  constexpr bool MMA = kIsMma<MM>;
   if (p.is_long) return pick_body<R, WIDE, 6, 1, 3, MM, true>(colli, dyn);
   if (p.spl == 30) {
     if constexpr (MMA) return nullptr;   // (the optimizer loop: one or two trajectories per wavefront)
@@ -1804,8 +1877,12 @@ static WaveKernelFn<R, MM> pick_geometry(const GtopEvalPlan &p, int B, bool coll
   if (p.nt == 2) {
     if constexpr (MMA) {   // (the loop never takes two trajectories per wavefront with DYN: gtop_optimize_device_ex)
       if (dyn) return nullptr;
-      return colli ? gtop_eval_wave_kernel<R, WIDE, 6, 2, true, 3, MM, false, false, 1>
-                   : gtop_eval_wave_kernel<R, WIDE, 6, 2, false, 3, MM, false, false, 1>;
+      if constexpr (kIsCons<MM>) {
+        return colli ? gtop_eval_wave_kernel<R, WIDE, 6, 2, true, 3, MM, false, false, 1> : nullptr;
+      } else {
+        return colli ? gtop_eval_wave_kernel<R, WIDE, 6, 2, true, 3, MM, false, false, 1>
+                     : gtop_eval_wave_kernel<R, WIDE, 6, 2, false, 3, MM, false, false, 1>;
+      }
     } else {
       return pick_body<R, WIDE, 6, 2, 3, MM, false>(colli, dyn);
     }
@@ -1842,6 +1919,17 @@ constexpr int kMaxGroupsPerLaunch = 1 << 25;
 template <typename MM> struct MovingBase { using type = MM; };
 template <typename Base> struct MovingBase<GtopMoving<Base>> { using type = Base; };
 
+// the collision term is in force (:346), as launch_wave decides it
+template <typename R> static bool has_collision_term(const GtopKernelArgs<R> &args) {
+  return !((args.wc < (R)0 ? -args.wc : args.wc) < (R)1e-4);
+}
+// the launch's MM argument in this object's gradient mode
+template <typename MM> static GtopModeOf<MM> mode_args(const MM &st) {
+  GtopModeOf<MM> w;
+  static_cast<MM &>(w) = st;
+  return w;
+}
+
 template <typename R, typename MM>
 static hipError_t launch_wave(const GtopKernelArgs<R> &args, const MM &st, const GtopEvalPlan &plan, bool dyn,
                               hipStream_t stream) {
@@ -1850,13 +1938,15 @@ static hipError_t launch_wave(const GtopKernelArgs<R> &args, const MM &st, const
   if (args.B <= 0) return hipSuccess;
   GtopKernelArgs<R> wa = args;
   if (wa.step == 1) wa.ws = (R)0;   // :412-415, applied here so that the kernel need not fetch `step`
-  const bool colli = !((wa.wc < (R)0 ? -wa.wc : wa.wc) < (R)1e-4);   // :346
+  const bool colli = has_collision_term(wa);   // :346
   dyn = dyn && wa.step == 2;        // the commented-out block's own test (:383)
   const bool wide = !gtop_field_is_narrow(wa.nx, wa.ny, wa.nz, sizeof(R));
   WaveKernelFn<R, MM> kern;
   if constexpr (MOV) {   // the moving-obstacle term lives in the sample loop: without a collision term there is none
-    using Base = typename MovingBase<MM>::type;
-    if (!colli) return launch_wave<R, Base>(args, static_cast<const Base &>(st), plan, dyn, stream);
+    if constexpr (!kIsCons<MM>) {   // (the consistent-gradient launchers are only called with a collision term)
+      using Base = typename MovingBase<MM>::type;
+      if (!colli) return launch_wave<R, Base>(args, static_cast<const Base &>(st), plan, dyn, stream);
+    }
     kern = wide ? pick_geometry_moving<true, MM>(plan, dyn) : pick_geometry_moving<false, MM>(plan, dyn);
   } else if constexpr (MMA && sizeof(R) == 4) {   // (the optimizer loop with fp32 evaluations: no 64-bit-index bodies — a field past 4 GiB in fp32)
     if (wide) return hipErrorInvalidValue;
@@ -1899,9 +1989,19 @@ static hipError_t launch_wave(const GtopKernelArgs<R> &args, const MM &st, const
 
 }  // namespace
 
+// The launchers.  In the reference-mode object (kReferenceObject) a plan that asks for the consistent gradient goes to
+// the other object's launcher of the same name + _consistent — unless the launch has no collision term (:346): the two
+// modes are then the same function and the reference body serves both.
+#ifdef GTOP_CONSISTENT_TU
+constexpr bool kReferenceObject = false;
+#else
+constexpr bool kReferenceObject = true;
+#endif
+
 template <typename R>
-hipError_t gtop_launch_eval(const GtopKernelArgs<R> &args, const GtopEvalPlan &plan, bool dyn, hipStream_t stream) {
-  return launch_wave<R, GtopNoMma>(args, GtopNoMma{}, plan, dyn, stream);
+hipError_t GTOP_LAUNCHER(gtop_launch_eval)(const GtopKernelArgs<R> &args, const GtopEvalPlan &plan, bool dyn, hipStream_t stream) {
+  if (kReferenceObject && plan.consistent && has_collision_term(args)) return gtop_launch_eval_consistent<R>(args, plan, dyn, stream);
+  return launch_wave<R, GtopModeOf<GtopNoMma>>(args, mode_args(GtopNoMma{}), plan, dyn, stream);
 }
 
 template <typename Base>
@@ -1911,41 +2011,47 @@ static GtopMoving<Base> moving_kernel_args(const Base &st, const GtopMovingArgs 
   mm.mk = GtopMovK{mov.rows, mov.t0, mov.nbox, mov.t0_stride};
   return mm;
 }
-hipError_t gtop_launch_eval_moving(const GtopKernelArgs<double> &args, const GtopEvalPlan &plan, bool dyn,
-                                   const GtopMovingArgs &mov, hipStream_t stream) {
+hipError_t GTOP_LAUNCHER(gtop_launch_eval_moving)(const GtopKernelArgs<double> &args, const GtopEvalPlan &plan, bool dyn,
+                                                  const GtopMovingArgs &mov, hipStream_t stream) {
   if (!mov.rows || mov.nbox < 1 || mov.nbox > GTOP_MOVING_MAX_BOXES) return hipErrorInvalidValue;
-  return launch_wave<double, GtopMoving<GtopNoMma>>(args, moving_kernel_args(GtopNoMma{}, mov), plan, dyn, stream);
+  if (kReferenceObject && plan.consistent && has_collision_term(args)) return gtop_launch_eval_moving_consistent(args, plan, dyn, mov, stream);
+  return launch_wave<double, GtopModeOf<GtopMoving<GtopNoMma>>>(args, mode_args(moving_kernel_args(GtopNoMma{}, mov)), plan, dyn, stream);
 }
-hipError_t gtop_launch_eval_mma_moving(const GtopKernelArgs<double> &args, const GtopMmaState &st, const GtopEvalPlan &plan,
-                                       bool dyn, const GtopMovingArgs &mov, hipStream_t stream) {
+hipError_t GTOP_LAUNCHER(gtop_launch_eval_mma_moving)(const GtopKernelArgs<double> &args, const GtopMmaState &st,
+                                                      const GtopEvalPlan &plan, bool dyn, const GtopMovingArgs &mov,
+                                                      hipStream_t stream) {
   if (!mov.rows || mov.nbox < 1 || mov.nbox > GTOP_MOVING_MAX_BOXES) return hipErrorInvalidValue;
   if (plan.nt != 1) return hipErrorInvalidValue;
-  return launch_wave<double, GtopMoving<GtopMmaState>>(args, moving_kernel_args(st, mov), plan, dyn, stream);
+  if (kReferenceObject && plan.consistent && has_collision_term(args)) return gtop_launch_eval_mma_moving_consistent(args, st, plan, dyn, mov, stream);
+  return launch_wave<double, GtopModeOf<GtopMoving<GtopMmaState>>>(args, mode_args(moving_kernel_args(st, mov)), plan, dyn, stream);
 }
 
 // the optimizer loop: st.iters evaluations at st.xcur, each followed by the CCSA-MMA update, in one launch (fp64)
-hipError_t gtop_launch_eval_mma(const GtopKernelArgs<double> &args, const GtopMmaState &st, const GtopEvalPlan &plan,
-                                bool dyn, hipStream_t stream) {
+hipError_t GTOP_LAUNCHER(gtop_launch_eval_mma)(const GtopKernelArgs<double> &args, const GtopMmaState &st,
+                                               const GtopEvalPlan &plan, bool dyn, hipStream_t stream) {
   if (plan.nw != 1 || plan.spl == 30 || plan.spl == 10 || (plan.nt != 1 && !(plan.nt == 2 && plan.spl == 6 && !plan.is_long))) return hipErrorInvalidValue;
-  return launch_wave<double, GtopMmaState>(args, st, plan, dyn, stream);
+  if (kReferenceObject && plan.consistent && has_collision_term(args)) return gtop_launch_eval_mma_consistent(args, st, plan, dyn, stream);
+  return launch_wave<double, GtopModeOf<GtopMmaState>>(args, mode_args(st), plan, dyn, stream);
 }
 // the same loop with the evaluations in fp32 on the fp32 field: args.Df / args.T still point at fp64 rows (the state,
 // the bounds, the update and the results are fp64; see the kernel's `In`), args.x / cost / grad are not read
-hipError_t gtop_launch_eval_mma(const GtopKernelArgs<float> &args, const GtopMmaState &st, const GtopEvalPlan &plan,
-                                bool dyn, hipStream_t stream) {
+hipError_t GTOP_LAUNCHER(gtop_launch_eval_mma)(const GtopKernelArgs<float> &args, const GtopMmaState &st,
+                                               const GtopEvalPlan &plan, bool dyn, hipStream_t stream) {
   if (plan.nw != 1 || plan.spl == 30 || plan.spl == 10 || (plan.nt != 1 && !(plan.nt == 2 && plan.spl == 6 && !plan.is_long))) return hipErrorInvalidValue;
-  return launch_wave<float, GtopMmaState>(args, st, plan, dyn, stream);
+  if (kReferenceObject && plan.consistent && has_collision_term(args)) return gtop_launch_eval_mma_consistent(args, st, plan, dyn, stream);
+  return launch_wave<float, GtopModeOf<GtopMmaState>>(args, mode_args(st), plan, dyn, stream);
 }
 
-#ifdef GTOP_STAMPS
+#if defined(GTOP_STAMPS) && !defined(GTOP_CONSISTENT_TU)
 extern "C" int gtop_debug_read_stamps(unsigned long long *out /*4096*16*/) {
   return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_gtop_stamps), sizeof(unsigned long long) * 4096 * 16);
 }
 #endif
 
-template hipError_t gtop_launch_eval<double>(const GtopKernelArgs<double> &, const GtopEvalPlan &, bool, hipStream_t);
-template hipError_t gtop_launch_eval<float>(const GtopKernelArgs<float> &, const GtopEvalPlan &, bool, hipStream_t);
+template hipError_t GTOP_LAUNCHER(gtop_launch_eval)<double>(const GtopKernelArgs<double> &, const GtopEvalPlan &, bool, hipStream_t);
+template hipError_t GTOP_LAUNCHER(gtop_launch_eval)<float>(const GtopKernelArgs<float> &, const GtopEvalPlan &, bool, hipStream_t);
 
+#ifndef GTOP_CONSISTENT_TU
 // ---------------------------------------------------------------------------
 // Device-side clock stamp (gtop_device_clock_stamp): one lane reads the constant-rate wall clock (the counter the
 // optimizer loop's maxtime rule uses) and folds it into minmax[0] = earliest, minmax[1] = latest stamp.  Captured as
@@ -1966,3 +2072,4 @@ hipError_t gtop_launch_clock_stamp(unsigned long long *minmax, hipStream_t strea
   hipLaunchKernelGGL(gtop_clock_stamp_kernel, dim3(1), dim3(64), 0, stream, minmax);
   return hipGetLastError();
 }
+#endif  // GTOP_CONSISTENT_TU

@@ -81,8 +81,9 @@ const char *gtop_last_error(const gtop_ctx *ctx);
  * gtop_group_set_field_sign; 4: the moving-obstacle cost, gtop_set_moving_cost /
  * gtop_get_moving_cost / gtop_set_start_times / gtop_set_start_times_device; 5: the
  * trajectory report and selection, gtop_validate_trajectories_device /
- * gtop_select_best_device / gtop_validate_batch; nothing of an earlier version
- * changed meaning). */
+ * gtop_select_best_device / gtop_validate_batch; 6: the gradient mode,
+ * gtop_set_gradient_mode / gtop_get_gradient_mode / gtop_group_set_gradient_mode;
+ * nothing of an earlier version changed meaning). */
 int gtop_abi_version(void);
 
 /* ---- configuration -------------------------------------------------- */
@@ -189,7 +190,11 @@ int gtop_get_sdf(gtop_ctx *ctx, double *dist_host, int grid_out[3]);
  * (GTOP_F32 evaluations, gtop_set_optimizer_precision(GTOP_F32)) and about 709
  * in fp64.  max_depth is the control: keep max_depth <= 80*r - d0 for fp32 use.
  * With the default D = 10000 a box without any free voxel holds -10000 and the
- * penalty there is inf even in fp64. */
+ * penalty there is inf even in fp64.
+ * (Those thresholds are the COST's, which carries the exponential once.  The
+ * reference's collision gradient carries it squared — see the gradient mode below —
+ * and overflows at half the exponent; under GTOP_GRADIENT_CONSISTENT the gradient
+ * carries it once and the thresholds above hold for it too.) */
 int gtop_set_field_sign(gtop_ctx *ctx, int signed_mode, double max_depth);
 int gtop_get_field_sign(const gtop_ctx *ctx, int *signed_mode, double *max_depth);
 
@@ -334,6 +339,8 @@ const char *gtop_group_gather_backend(const gtop_group *g);
  * librccl.so not found: ..." — a fallback from RCCL to copies is never silent. */
 const char *gtop_group_gather_note(const gtop_group *g);
 int gtop_group_set_params(gtop_group *g, const gtop_params *p);
+/* gtop_set_gradient_mode on every member */
+int gtop_group_set_gradient_mode(gtop_group *g, int mode);
 /* gtop_set_field_sign on every member */
 int gtop_group_set_field_sign(gtop_group *g, int signed_mode, double max_depth);
 int gtop_group_init_sdf_map(gtop_group *g, const double map_size[3], const double origin[3], double resolution);
@@ -529,6 +536,53 @@ int gtop_set_moving_cost(gtop_ctx *ctx, int enable);
 int gtop_get_moving_cost(const gtop_ctx *ctx, int *enable);
 int gtop_set_start_times(gtop_ctx *ctx, int count, const double *t0_host);
 int gtop_set_start_times_device(gtop_ctx *ctx, int count, const void *d_t0);
+
+/* ---- gradient mode (not in the reference) --------------------------------- */
+/* The gradient the evaluations return by default is the reference's callback line
+ * by line, and that is not the gradient of the cost they return:
+ *  - collision term (src/grad_traj_optimizer.cpp:376-381): gd*grad(k)*cd*vel_norm,
+ *    where the derivative of cd(dist)*vel_norm*dt is gd*grad(k)*vel_norm — a spurious
+ *    factor cd = alpha*exp((d0 - dist)/r), 10 at dist = d0 and above 40 at dist = 0
+ *    with the shipped parameters;
+ *  - the enable_dyn block (:383-407): cv, ca in the gradient are the values the cost
+ *    loop left behind (the last axis's), there is no sign(v) / sign(a) factor, and
+ *    the d|v|/dx term carries one axis's penalty instead of the sum.
+ * GTOP_GRADIENT_REFERENCE (the default) keeps all of that: a drop-in reproduces the
+ * reference's iterates.  GTOP_GRADIENT_CONSISTENT changes the GRADIENT only; for a
+ * live sample (inside the loop bound of :353), axis k:
+ *
+ *   g_colli.row(k) += ( gd*grad(k)*vel_norm * T*Ldp
+ *                       + cd*(vel(k)/vel_norm) * T*V*Ldp ) * dt
+ *   and, where the enable_dyn block is active (enable_dyn != 0 and step == 2):
+ *   S = sum_j (cv_j + ca_j)                                    over the three axes
+ *   g_vel.row(k) += ( gv_k*sgn(vel(k))*vel_norm + S*vel(k)/vel_norm ) * T*V*Ldp * dt
+ *   g_acc.row(k) += ( ga_k*sgn(acc(k))*vel_norm ) * T*V*V*Ldp * dt
+ *   sgn(+-0) = 0: an axis with exactly zero velocity (the two idle axes of an
+ *   axis-aligned path) gets no push.
+ *
+ * Everything else is as in reference mode: the cost, bit for bit; position,
+ * velocity and acceleration through `float`; vel_norm = |v| + 1e-5, also in the
+ * quotient; out of the map dist = -1 and grad := 0; + 1e-5 on every gradient entry;
+ * |wc| < 1e-4 skips the sample loop (the two modes are then the same function);
+ * ws = 0 at step 1; with the moving-obstacle cost on, dist and grad come from the
+ * time-aware lookup; a signed field is taken as it is.
+ * "Consistent" means: the derivative of the returned cost with the float round
+ * trips treated as the identity, the field as differentiable inside a cell, and
+ * d vel_norm / d v = v / vel_norm (the 1e-5 of vel_norm in the quotient biases one
+ * term by 1e-5/|v|).  It matches finite differences of the cost at the 1e-6 level,
+ * not to rounding.
+ *
+ * Context state, read when a call is made (a captured gtop_eval_device replays
+ * with the mode it was captured with): gtop_eval_batch, gtop_cost_nlopt,
+ * gtop_cost_nlopt_shared, gtop_eval_device of both precisions,
+ * gtop_optimize_batch[_ex] and gtop_optimize_device[_ex] in all three fusion modes
+ * and both optimizer precisions, moving-obstacle cost on or off, enable_dyn on or
+ * off, every launch geometry and length those serve — no limit of its own.  The
+ * device forms still only enqueue.  Other values of `mode`: GTOP_ERR_INVALID. */
+#define GTOP_GRADIENT_REFERENCE 0  /* default: the reference's callback, as shipped */
+#define GTOP_GRADIENT_CONSISTENT 1
+int gtop_set_gradient_mode(gtop_ctx *ctx, int mode);
+int gtop_get_gradient_mode(const gtop_ctx *ctx, int *mode);
 
 /* ---- trajectory safety report and best-candidate selection -------------- */
 /* (Not a PolynomialTraj method.)  Replaces what a caller assembled by hand after
