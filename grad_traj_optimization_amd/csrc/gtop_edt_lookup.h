@@ -6,6 +6,11 @@
 // trilinear value.  The library is built with -ffp-contract=on, so the same source
 // expression rounds the same way wherever it is inlined: both kernels get the same
 // distance, bit for bit.  The gradient stays with the query kernel.
+// The STATIC lookup (base index, diff, trilinear value; the gradient in gtop_edt.hip) is unfused, as poly_eval is:
+// it is sdf_map.cpp's arithmetic operation for operation, so a static query returns the bits of the reference's
+// getDistWithGradTrilinear.  Fused, a gradient component that cancels between corners of very different size (free
+// voxels at 10000 beside an obstacle's: v1 - v0 = 0.03 at |v| = 5750) left the reference by 3e-11 of itself, past
+// the 1e-12 the query is held to (tests/test_gpu_records.py, the window without new points).
 #ifndef GTOP_EDT_LOOKUP_H_
 #define GTOP_EDT_LOOKUP_H_
 
@@ -26,6 +31,7 @@ __device__ __forceinline__ bool gtop_edt_out_of_map(const GtopGrid &g, const dou
 // read four (z, z+1) pairs from four lines: 4.24 lines of 128 bytes per query, 16 bytes used of each; now 1.25).
 __device__ __forceinline__ void gtop_edt_corners(const GtopGrid &g, const double *__restrict__ rec, const double p[3],
                                                  int idx[3], double diff[3], double values[2][2][2]) {
+#pragma clang fp contract(off)
   for (int k = 0; k < 3; ++k) {
     const double pm = p[k] - 0.5 * g.res;
     idx[k] = (int)floor((pm - g.origin[k]) * g.res_inv);
@@ -101,6 +107,7 @@ struct GtopTrilinear {
   double v00, v01, v10, v11, v0, v1, d;
 };
 __device__ __forceinline__ GtopTrilinear gtop_edt_trilinear(const double diff[3], const double values[2][2][2]) {
+#pragma clang fp contract(off)
   GtopTrilinear r;
   r.v00 = (1 - diff[0]) * values[0][0][0] + diff[0] * values[1][0][0];
   r.v01 = (1 - diff[0]) * values[0][0][1] + diff[0] * values[1][0][1];
