@@ -1,5 +1,5 @@
 // gtop_device_common.h — device-side helpers shared by the evaluation kernel
-// (gtop_kernels.hip), the optimizer kernels (gtop_mma.hip), the post-processing
+// (gtop_wave_kernel.h), the optimizer kernels (gtop_mma.hip), the post-processing
 // (gtop_setup.hip) and the trajectory report (gtop_validate.hip).
 #ifndef GTOP_DEVICE_COMMON_H_
 #define GTOP_DEVICE_COMMON_H_

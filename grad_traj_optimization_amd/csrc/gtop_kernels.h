@@ -1,12 +1,14 @@
 // gtop_kernels.h — launch interface between the C-ABI layer (gtop_capi.cpp)
-// and the gfx950 kernels (gtop_kernels.hip, gtop_esdf.hip).  Internal; the
-// public boundary is include/gtop.h.
+// and the gfx950 kernels (the launchers of gtop_kernels.hip, gtop_esdf.hip, ...); the launch rule and its
+// GtopEvalPlan are gtop_launch_rule.h's, included here.  Internal; the public boundary is include/gtop.h.
 #ifndef GTOP_KERNELS_H_
 #define GTOP_KERNELS_H_
 
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+
+#include "gtop_launch_rule.h"
 
 // Kernel arguments of gtop_eval_wave_kernel<R>, all in the arithmetic type R of the
 // launch (double for GTOP_F64, float for GTOP_F32).
@@ -29,7 +31,7 @@ struct GtopKernelArgs {
   float lo_f[3], hi_f[3];   // lo rounded up / hi rounded down to float: for a float p, p < lo <=> p < lo_f, p > hi <=> p > hi_f
   R res, res_inv;
   // posToIndex's constants in double whatever R is: the fp32 kernels decide which cell a sample reads as the reference
-  // does, in double on the widened float position (gtop_kernels.hip IndexBox); the fp64 kernels do not read these
+  // does, in double on the widened float position (gtop_wave_kernel.h IndexBox); the fp64 kernels do not read these
   double idx_origin[3], idx_half, idx_rinv;
   // parameters — grad_traj_optimizer.cpp:5-32
   R ws, wc, alpha, d0, alpha_v, r_v, v0, alpha_a, r_a, a0;
@@ -60,21 +62,6 @@ struct GtopMmaState {
   int *out_code, *out_nevals;
 };
 enum { GTOP_MMA_FTOL_REACHED = 3, GTOP_MMA_XTOL_REACHED = 4, GTOP_MMA_MAXEVAL_REACHED = 5, GTOP_MMA_MAXTIME_REACHED = 6 };
-// How one launch is laid out on the wavefronts: spl = samples per lane (3: ten lanes per segment, one trajectory of up
-// to 6 segments per wavefront; 6: five lanes per segment, up to 12 segments), nt = trajectories per wavefront (2 only
-// at spl 6 with up to 6 segments), is_long = more than 12 segments (the wavefront walks them 12 at a time).
-struct GtopEvalPlan {
-  int spl, nt;
-  bool is_long;
-  int nw;   // wavefronts per trajectory: 2 for 7 .. 12 segments at ten lanes per segment (small batches), else 1
-  // which gradient the bodies compute (gtop_set_gradient_mode): 0 the reference's callback, 1 the consistent one.  The
-  // launch rule leaves it 0 and does not look at it — both modes have a body for every geometry; the caller sets it.
-  int consistent;
-};
-// The launch rule.  pinned_spl: 0 = auto, 3 or 6; for_optimizer: the optimizer loop and the evaluations of its
-// multi-launch forms (the same rule with the loop's own switch point to two trajectories per wavefront).  false: the request cannot be served (m < 2, spl 3 with more than 6
-// segments, more segments than one wavefront's LDS holds — 227, in the optimizer loop 118).
-bool gtop_eval_plan(int B, int m, size_t elem, int pinned_spl, bool for_optimizer, GtopEvalPlan *plan);
 // dyn: enable_dyn (the kernel applies it at step 2 only, as the commented-out block would)
 template <typename R>
 hipError_t gtop_launch_eval(const GtopKernelArgs<R> &args, const GtopEvalPlan &plan, bool dyn, hipStream_t stream);
@@ -93,8 +80,6 @@ struct GtopMovingArgs {
   const double *t0;     // start times on the boxes' clock; NULL = all zero
   int t0_stride;        // 0 = one shared value, 1 = one per trajectory
 };
-// the launch rule restricted to the geometries that have a moving-term body; false: none serves the request
-bool gtop_eval_plan_moving(int B, int m, int pinned_spl, bool for_optimizer, GtopEvalPlan *plan);
 hipError_t gtop_launch_eval_moving(const GtopKernelArgs<double> &args, const GtopEvalPlan &plan, bool dyn,
                                    const GtopMovingArgs &mov, hipStream_t stream);
 hipError_t gtop_launch_eval_mma_moving(const GtopKernelArgs<double> &args, const GtopMmaState &st, const GtopEvalPlan &plan,

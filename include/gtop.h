@@ -679,7 +679,7 @@ int gtop_clear_cost_curve(gtop_ctx *ctx);
 
 /* ---- tuning knobs (not in the reference) ---------------------------- */
 
-/* Launch geometry of the evaluation kernel (csrc/gtop_kernels.hip,
+/* Launch geometry of the evaluation kernel (csrc/gtop_launch_rule.cpp,
  * gtop_eval_plan).  A wavefront always holds whole segments; `waves` must be 0
  * or 1 (the number of wavefronts per workgroup follows from the rule below and
  * is not a knob).  samples_per_lane:

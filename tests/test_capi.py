@@ -91,6 +91,44 @@ def test_no_kernel_spills_to_scratch_memory(tmp_path):
     assert seen == 2 and len(violations) == 1 and "v_mov_b32_e32 v30, v9" in violations[0], violations
 
 
+def _fake_listing(ordinal, cuid, mul="v_mul_f64 v[0:1], v[2:3], v[4:5]", vgprs=12):
+    """Two functions as hipcc -S lays them out: k1 (with a branch, a kernel descriptor and a metadata entry) behind k0."""
+    def fn(name, n, body, nv):
+        return (f"\t.section\t.text.{name},\"axG\",@progbits,{name},comdat\n\t.globl\t{name} ; -- Begin function {name}\n"
+                f"\t.p2align\t8\n\t.type\t{name},@function\n{name}: ; @{name}\n; %bb.0:\n{body}\ts_endpgm\n"
+                f"\t.section\t.rodata,\"a\",@progbits\n\t.amdhsa_kernel {name}\n\t\t.amdhsa_next_free_vgpr {nv}\n"
+                f"\t.end_amdhsa_kernel\n\t.section\t.text.{name},\"axG\",@progbits,{name},comdat\n.Lfunc_end{n}:\n"
+                f"\t.size\t{name}, .Lfunc_end{n}-{name}\n ; -- End function\n")
+    k1 = (f"\ts_cbranch_scc1 .LBB{ordinal}_2\n.LBB{ordinal}_1:{' ' * (30 - len(str(ordinal)))}; =>This Loop Header: Depth=1\n"
+          f"\t{mul}\n\ts_branch .LBB{ordinal}_1\n.LBB{ordinal}_2:\n")
+    fns = [fn(f"pad{i}", i, "", 4) for i in range(ordinal)] + [fn("k1", ordinal, k1, vgprs)]
+    meta = "".join(f"  - .agpr_count:     0\n    .name:           {n}\n    .vgpr_count:     {v}\n"
+                   for n, v in [(f"pad{i}", 4) for i in range(ordinal)] + [("k1", vgprs)])
+    return ("\t.amdgcn_target \"amdgcn-amd-amdhsa--gfx950\"\n" + "".join(fns) +
+            f"\t.section\t.AMDGPU.gpr_maximums,\"\",@progbits\n\t.type\t__hip_cuid_{cuid},@object\n__hip_cuid_{cuid}:\n"
+            f"\t.amdgpu_metadata\n---\namdhsa.kernels:\n{meta}amdhsa.target:   amdgcn-amd-amdhsa--gfx950\n...\n")
+
+
+def test_listing_comparison_sees_code_and_not_position():
+    """tools/kernel_resources.py --compare, the gate of a refactor of the kernels: the same body at another position in
+    the file (another ordinal in its local labels, another compilation-unit id) is equal; one changed instruction and
+    one changed .amdhsa_next_free_vgpr are reported, each for the part it is in."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("kernel_resources", os.path.join(ROOT, "tools", "kernel_resources.py"))
+    kr = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(kr)
+    base = _fake_listing(1, "aaaa")
+    parts = kr.split_listing(base)
+    assert sorted(parts) == ["k1", "pad0"] and len(parts["k1"]["text"]) > 10 and len(parts["k1"]["amdhsa"]) == 3
+    assert len(parts["k1"]["metadata"]) == 3 and not any("pad0" in ln for ln in parts["k1"]["text"])
+    n, only_old, only_new, differ = kr.compare_listings(base, _fake_listing(12, "bbbb"))
+    assert (n, only_old, differ) == (2, [], {}) and len(only_new) == 11
+    n, only_old, only_new, differ = kr.compare_listings(base, _fake_listing(1, "aaaa", mul="v_mul_f64 v[0:1], v[2:3], v[6:7]"))
+    assert (n, only_old, only_new, differ) == (2, [], [], {"k1": ["text"]})
+    n, only_old, only_new, differ = kr.compare_listings(base, _fake_listing(1, "aaaa", vgprs=13))
+    assert (n, only_old, only_new, differ) == (2, [], [], {"k1": ["amdhsa", "metadata"]})
+
+
 def test_eigen_adapter_header_says_what_it_needs(tmp_path):
     """include/grad_traj_optimization/grad_traj_optimizer.h (the reference-shaped class with Eigen signatures) must fail
     with a readable message in an image without Eigen, and compile against the test double of the Eigen types
@@ -113,7 +151,7 @@ def test_eigen_adapter_header_says_what_it_needs(tmp_path):
 
 
 def test_reciprocal_divisions_of_the_per_wavefront_task_lists_are_exact():
-    """csrc/gtop_kernels.hip, the geometries with 21 / m or 64 / m trajectories per wavefront: a lane's trajectory is
+    """csrc/gtop_wave_kernel.h, the geometries with 21 / m or 64 / m trajectories per wavefront: a lane's trajectory is
     slot / m by a 16-bit reciprocal and a task's trajectory qi / n by a 24-bit one (no integer division in the kernel).
     Exhaustively, for every segment count and every index the kernel can form: the same as floor division, and the
     product stays inside 32 bits."""

@@ -194,8 +194,8 @@ def test_twin_takes_the_timed_lookup(oracle_mod):
 
 
 def test_consistent_bodies_use_no_scratch_memory(tmp_path):
-    """tests/test_capi.py's build-time check on the consistent-gradient object (csrc/gtop_kernels.hip compiled with
-    -DGTOP_CONSISTENT_TU): no body spills, every body has a collision term, the latency body keeps its two wavefronts
+    """tests/test_capi.py's build-time check on the consistent-gradient object (csrc/gtop_kernels.hip — the bodies of
+    csrc/gtop_wave_kernel.h — compiled with -DGTOP_CONSISTENT_TU): no body spills, every body has a collision term, the latency body keeps its two wavefronts
     per SIMD, and nothing names a hand-issued load's registers before the wait that covers it."""
     import importlib.util
     spec = importlib.util.spec_from_file_location("kernel_resources", os.path.join(ROOT, "tools", "kernel_resources.py"))

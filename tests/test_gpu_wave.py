@@ -1,4 +1,4 @@
-"""gtop_eval_wave_kernel (csrc/gtop_kernels.hip) through every instantiation: one trajectory of up
+"""gtop_eval_wave_kernel (csrc/gtop_wave_kernel.h, launched by csrc/gtop_kernels.hip) through every instantiation: one trajectory of up
 to 6 segments per wavefront (samples per lane 3; latency variant below 3 072 trajectories, three-wavefront variant
 above), one of up to 12 or two of up to 6 (samples per lane 6), three lanes per segment with 21 / m whole trajectories per
 wavefront (samples per lane 10), one lane per segment with 64 / m (samples per lane 30), fp64 and fp32 (packed pairs at 6,

@@ -1,9 +1,12 @@
 #!/usr/bin/env python3
-"""Kernel count, registers, spills and occupancy of every kernel in csrc/gtop_kernels.hip (a CPU-side compile:
+"""Kernel count, registers, spills and occupancy of every kernel in csrc/gtop_kernels.hip — the instantiations of
+gtop_eval_wave_kernel (csrc/gtop_wave_kernel.h) its launchers select — (a CPU-side compile:
 hipcc -Rpass-analysis=kernel-resource-usage); exits non-zero if any kernel spills — run by tests/test_capi.py, so a
 compiler or flag change that pushes a body into scratch (the hand-issued loads of the latency variant depend on the
 register allocator keeping their results where they land) is seen at build time.
 usage: tools/kernel_resources.py [--asm-out FILE] [--source FILE.hip] [extra hipcc flags...]
+       tools/kernel_resources.py --table                  (profiles/kernel_table.md: every body of both objects)
+       tools/kernel_resources.py --compare OLD.s NEW.s    (two ISA listings kernel by kernel; non-zero if they differ)
 --source names another file of csrc/ (gtop_validate.hip, gtop_edt.hip, gtop_setup.hip, ...); the default is
 gtop_kernels.hip."""
 import os
@@ -55,7 +58,7 @@ def _vregs(text):
 
 
 def check_asm_loads(asm_path):
-    """The hand-issued distance-field loads (inline asm `global_load_dwordx4`, csrc/gtop_kernels.hip asm_load_pair) are
+    """The hand-issued distance-field loads (inline asm `global_load_dwordx4`, csrc/gtop_wave_kernel.h asm_load_pair) are
     invisible to the compiler's wait-count insertion: the kernel waits for them itself (gtop_wait_pairs).  That is sound
     only while NOTHING touches a load's destination registers between its issue and the s_waitcnt that covers it — a
     v_mov the register allocator inserts after a compiler or flag change would read registers that have not landed.
@@ -106,8 +109,95 @@ def check_asm_loads(asm_path):
     return seen, bad
 
 
+def table():
+    """One markdown row per kernel of the two objects gtop_kernels.hip is compiled into."""
+    ver = subprocess.run(["/opt/rocm/bin/hipcc", "--version"], capture_output=True, text=True).stdout
+    print("Compiler: " + next(ln.strip() for ln in ver.splitlines() if "clang version" in ln))
+    for title, extra in (("reference-mode object", ()), ("consistent-gradient object", ("-DGTOP_CONSISTENT_TU",))):
+        rows, _ = analyse(extra, os.devnull)
+        print(f"\n## {title}: {len(rows)} kernels\n\n| kernel | VGPRs | SGPRs | waves/SIMD | scratch |\n|---|---|---|---|---|")
+        for r in rows:
+            print(f"| `{r['kernel']}` | {r['vgprs']} | {r['sgprs']} | {r['waves_per_simd']} | {r['scratch']} |")
+    return 0
+
+
+# .LBB<n>_<k>, .LJTI<n>_<k>, .Lfunc_end<n>, and BB<n>_<k> in the loop comments
+_LOCAL_LABEL = re.compile(r"(\.Lfunc_begin|\.Lfunc_end|\.L[A-Za-z]+(?=\d+_\d)|\bBB(?=\d+_\d))\d+")
+
+
+def split_listing(text):
+    """An ISA listing (hipcc -S --cuda-device-only) per function symbol: {name: {"text", "amdhsa", "metadata"}}, each a
+    list of lines — the instruction text (labels, directives and the resource comments behind it included), the
+    .amdhsa_kernel block and the kernel's entry in the metadata.  Lines that name the compilation unit's id
+    (__hip_cuid_...) are dropped, and the function's ordinal in local labels is replaced: neither depends on the
+    function's code, both on where and beside what it was compiled."""
+    out, cur, part, in_meta, section = {}, None, "text", False, None
+    for line in text.splitlines():
+        if "__hip_cuid_" in line:
+            continue
+        line = re.sub(r"\s+;", " ;", _LOCAL_LABEL.sub(lambda m: m.group(1) + "N", line.rstrip()))   # (comment column: the label's width)
+        if in_meta:
+            if line.startswith("  - "):
+                cur = []
+            elif not line.startswith("    "):
+                cur = None
+            if cur is not None:
+                cur.append(line)
+                m = re.match(r"    \.name:\s+(\S+)", line)
+                if m:
+                    out.setdefault(m.group(1), {"text": [], "amdhsa": []})["metadata"] = cur
+            continue
+        if line.startswith("amdhsa.kernels:"):
+            in_meta, cur = True, None
+            continue
+        m = re.search(r"; -- Begin function (\S+)", line)
+        if m:
+            if cur is not None and cur["text"] and cur["text"][-1] is section:
+                cur["text"].pop()   # the .section line in front of a function is that function's
+            cur, part = out.setdefault(m.group(1), {"text": [], "amdhsa": []}), "text"
+            if section is not None:
+                cur["text"].append(section)
+        elif ".AMDGPU.gpr_maximums" in line:
+            cur = None
+        section = line if line.lstrip().startswith(".section") else None
+        if cur is None:
+            continue
+        if line.lstrip().startswith(".amdhsa_kernel "):
+            part = "amdhsa"
+        cur[part].append(line)
+        if line.lstrip().startswith(".end_amdhsa_kernel"):
+            part = "text"
+    return out
+
+
+def compare_listings(old_text, new_text):
+    """(kernels compared, names only in old, names only in new, {name: [parts that differ]})"""
+    old, new = split_listing(old_text), split_listing(new_text)
+    differ = {}
+    for name in sorted(set(old) & set(new)):
+        parts = [k for k in ("text", "amdhsa", "metadata") if old[name].get(k) != new[name].get(k)]
+        if parts:
+            differ[name] = parts
+    return len(set(old) & set(new)), sorted(set(old) - set(new)), sorted(set(new) - set(old)), differ
+
+
+def compare(old_path, new_path):
+    n, only_old, only_new, differ = compare_listings(open(old_path).read(), open(new_path).read())
+    print(f"{n} kernels compared, {len(differ)} differ, {len(only_old)} only in {old_path}, {len(only_new)} only in {new_path}")
+    for tag, names in (("only old", only_old), ("only new", only_new)):
+        for name in names:
+            print(f"  {tag}: {name}")
+    for name, parts in differ.items():
+        print(f"  differs in {', '.join(parts)}: {name}")
+    return 1 if differ or only_old or only_new else 0
+
+
 def main():
     args = sys.argv[1:]
+    if args[:1] == ["--table"]:
+        return table()
+    if args[:1] == ["--compare"] and len(args) == 3:
+        return compare(args[1], args[2])
     asm_out = "/tmp/gtop_kernels.s"
     if args[:1] == ["--asm-out"]:
         asm_out, args = args[1], args[2:]
