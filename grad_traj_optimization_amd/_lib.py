@@ -607,9 +607,10 @@ class GtopContext:
     def coefficients_device(self, x, Df, T, coeff=None, stream=None):
         """torch fp64 CUDA tensors x (B, n), Df (B, 18), T (B, m) or (m,) -> coeff (B, m, 18); asynchronous."""
         import torch
-        assert x.is_cuda and x.dtype == Df.dtype == T.dtype == torch.float64
+        assert x.is_cuda and Df.is_cuda and T.is_cuda and x.dtype == Df.dtype == T.dtype == torch.float64
         assert x.is_contiguous() and Df.is_contiguous() and T.is_contiguous()
         B, m = x.shape[0], T.shape[-1]
+        assert x.numel() == B * 9 * (m - 1) and Df.numel() == B * 18 and (T.dim() == 1 or T.shape == (B, m))
         if coeff is None:
             coeff = torch.empty(B, m, 18, dtype=torch.float64, device=x.device)
         if stream is None:
@@ -618,6 +619,75 @@ class GtopContext:
                                                    C.c_void_p(T.data_ptr()), m if T.dim() == 2 else 0,
                                                    C.c_void_p(coeff.data_ptr()), C.c_void_p(stream)))
         return coeff
+
+    def setup_paths_device(self, waypoints, mean_v=1.8, init_time=0.3, T=None, Df=None, x0=None, stream=None):
+        """torch fp64 CUDA tensor waypoints (B, m+1, 3) -> T (B, m), Df (B, 18), x0 (B, 9(m-1)): setPath's segment
+        times, fixed derivatives and straight-line free variables; asynchronous."""
+        import torch
+        assert waypoints.is_cuda and waypoints.dtype == torch.float64 and waypoints.is_contiguous()
+        assert waypoints.dim() == 3 and waypoints.shape[2] == 3
+        B, m = waypoints.shape[0], waypoints.shape[1] - 1
+        n = 9 * (m - 1)
+        if T is None:
+            T = torch.empty(B, m, dtype=torch.float64, device=waypoints.device)
+        if Df is None:
+            Df = torch.empty(B, 18, dtype=torch.float64, device=waypoints.device)
+        if x0 is None:
+            x0 = torch.empty(B, max(n, 0), dtype=torch.float64, device=waypoints.device)
+        for t, cnt in ((T, B * m), (Df, B * 18), (x0, B * n)):
+            assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and t.numel() == max(cnt, 0)
+        if stream is None:
+            stream = torch.cuda.current_stream(waypoints.device).cuda_stream
+        self._chk(self._L.gtop_setup_paths_device(self._h, B, m, C.c_void_p(waypoints.data_ptr()), float(mean_v),
+                                                  float(init_time), C.c_void_p(T.data_ptr()), C.c_void_p(Df.data_ptr()),
+                                                  C.c_void_p(x0.data_ptr()), C.c_void_p(stream)))
+        return T, Df, x0
+
+    def eval_trajectories_device(self, coeff, T, dt_sample=0.01, stats=None, stream=None):
+        """torch fp64 CUDA tensors coeff (B, m, 18), T (B, m) or (m,) -> stats (B, 9), the columns of TRAJ_STATS;
+        asynchronous."""
+        import torch
+        assert coeff.is_cuda and T.is_cuda and coeff.dtype == T.dtype == torch.float64
+        assert coeff.is_contiguous() and T.is_contiguous() and coeff.dim() == 3 and coeff.shape[2] == 18
+        B, m = coeff.shape[0], coeff.shape[1]
+        assert T.shape == (m,) or T.shape == (B, m)
+        if stats is None:
+            stats = torch.empty(B, len(self.TRAJ_STATS), dtype=torch.float64, device=coeff.device)
+        assert stats.is_cuda and stats.is_contiguous() and stats.dtype == torch.float64
+        assert stats.numel() == B * len(self.TRAJ_STATS)
+        if stream is None:
+            stream = torch.cuda.current_stream(coeff.device).cuda_stream
+        self._chk(self._L.gtop_eval_trajectories_device(self._h, B, m, C.c_void_p(coeff.data_ptr()),
+                                                        C.c_void_p(T.data_ptr()), m if T.dim() == 2 else 0,
+                                                        float(dt_sample), C.c_void_p(stats.data_ptr()),
+                                                        C.c_void_p(stream)))
+        return stats
+
+    def sample_trajectories_device(self, coeff, T, dt_sample=0.01, max_samples=4096, stats=None, samples=None,
+                                   stream=None):
+        """torch fp64 CUDA tensors coeff (B, m, 18), T (B, m) or (m,) -> (stats (B, 9), samples (B, max_samples, 3)):
+        the getTraj points; trajectory b has stats[b, 8] of them, the first max_samples are stored and the rows behind
+        them are left as they were (zero in a buffer allocated here); asynchronous."""
+        import torch
+        assert coeff.is_cuda and T.is_cuda and coeff.dtype == T.dtype == torch.float64
+        assert coeff.is_contiguous() and T.is_contiguous() and coeff.dim() == 3 and coeff.shape[2] == 18
+        B, m = coeff.shape[0], coeff.shape[1]
+        assert T.shape == (m,) or T.shape == (B, m)
+        max_samples = int(max_samples)
+        if stats is None:
+            stats = torch.empty(B, len(self.TRAJ_STATS), dtype=torch.float64, device=coeff.device)
+        if samples is None:
+            samples = torch.zeros(B, max(max_samples, 0), 3, dtype=torch.float64, device=coeff.device)
+        for t, cnt in ((stats, B * len(self.TRAJ_STATS)), (samples, B * max_samples * 3)):
+            assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and t.numel() == max(cnt, 0)
+        if stream is None:
+            stream = torch.cuda.current_stream(coeff.device).cuda_stream
+        self._chk(self._L.gtop_sample_trajectories_device(self._h, B, m, C.c_void_p(coeff.data_ptr()),
+                                                          C.c_void_p(T.data_ptr()), m if T.dim() == 2 else 0,
+                                                          float(dt_sample), C.c_void_p(stats.data_ptr()),
+                                                          C.c_void_p(samples.data_ptr()), max_samples,
+                                                          C.c_void_p(stream)))
+        return stats, samples
 
     def validate_device(self, coeff, T, limits, dt_sample=0.01, report=None, stream=None):
         """torch fp64 CUDA tensors coeff (B, m, 18), T (B, m) or (m,) -> report (B, 12); asynchronous, capturable

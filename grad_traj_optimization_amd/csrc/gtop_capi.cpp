@@ -946,7 +946,8 @@ int gtop_sample_trajectories_device(gtop_ctx *c, int B, int m, const void *d_coe
   if (B < 0 || m < 1 || !(dt_sample > 0.0) || (time_stride != 0 && time_stride != m) || max_samples < 0)
     return fail(c, GTOP_ERR_INVALID, "eval_trajectories: need B >= 0, m >= 1, dt_sample > 0, time_stride in {0, m}");
   if (B == 0) return GTOP_OK;
-  if (!d_coeff || !d_T || !d_stats) return fail(c, GTOP_ERR_INVALID, "eval_trajectories: NULL buffer");
+  if (!d_coeff || !d_T || !d_stats || (max_samples > 0 && !d_samples))
+    return fail(c, GTOP_ERR_INVALID, "eval_trajectories: NULL buffer");
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, gtop_launch_eval_trajectories(B, m, static_cast<const double *>(d_coeff), static_cast<const double *>(d_T),
                                           time_stride, dt_sample, static_cast<double *>(d_stats),

@@ -444,7 +444,8 @@ int gtop_eval_trajectories_device(gtop_ctx *ctx, int B, int m, const void *d_coe
  * as the reference does, while eval_t <= time_sum): samples is
  * B x max_samples x 3; trajectory b has stats[b][8] points, of which the first
  * min(stats[b][8], max_samples) are stored.  src/opti_node.cpp:108-120 publishes
- * exactly these. */
+ * exactly these.  max_samples = 0 asks for the statistics alone (d_samples is
+ * not read then); with max_samples > 0 a NULL d_samples is refused. */
 int gtop_sample_trajectories_device(gtop_ctx *ctx, int B, int m, const void *d_coeff,
                                     const void *d_T, int time_stride, double dt_sample,
                                     void *d_stats, void *d_samples, int max_samples,
