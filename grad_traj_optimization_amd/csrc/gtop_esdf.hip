@@ -39,6 +39,8 @@
 //     the plane is dealt to the XCDs in 64-lane chunks (not one contiguous eighth each) so that each gets an
 //     even sample of the map (65 -> 56 us at 200^3; per-wavefront timeline: tools/esdf_stamps.py).
 // Result: bit-identical to the CPU restatement and to scipy's exact EDT (tests).
+// Which instantiation serves a grid, on what launch grid, and which voxels a (workgroup, thread) owns is stated once, in
+// gtop_esdf_plan.h (host-only; pinned by tests/test_esdf_plan.py, run at every limit by tests/test_gpu_esdf_limits.py).
 // Rejected with measurements: an LDS-tiled variant of the scans (4-6x slower, round 1); the reference's own
 // lower-envelope algorithm with one lane per line and the stack in LDS (155 us for the x sweep at 200^3, 2.8 ms
 // at 400^3: a line's pops diverge across the 64 lanes and 4 B x line length of LDS per lane leaves one
@@ -47,6 +49,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "gtop_esdf_plan.h"
 #include "gtop_kernels.h"
 
 namespace {
@@ -85,7 +88,7 @@ esdf_mark_kernel(const GtopGrid g, const double *__restrict__ pts, int npts,
 }
 
 // z sweep (sdf_map.cpp:311-326): one wavefront per (x,y) column.
-constexpr int kMaxChunks = 64;   // columns up to 4096 voxels
+// (columns of up to 64 * kEsdfMaxChunks voxels: gtop_esdf_plan.h)
 
 // The seeds of a transform: the occupied voxels (the distance field), or — FREE, the signed field's second transform —
 // every voxel that is not occupied.  A template parameter: the predicate is fixed per instantiation, and the unsigned
@@ -98,7 +101,7 @@ __device__ __forceinline__ void esdf_z_body(const GtopGrid &g, const uint8_t *__
                                             uint16_t *__restrict__ out16, uint8_t *__restrict__ colany,
                                             int *__restrict__ n_empty_slabs) {
   if (blockIdx.x == 0 && threadIdx.x == 0) *n_empty_slabs = 0;   // counted by the y sweep / esdf_rows_kernel, read by the x sweep
-  __shared__ unsigned long long masks[4][kMaxChunks];
+  __shared__ unsigned long long masks[4][kEsdfMaxChunks];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const size_t ncol = (size_t)g.nx * g.ny;
   const int nz = g.nz, nchunk = (nz + 63) >> 6;
@@ -291,9 +294,8 @@ struct __attribute__((aligned(16))) PkV { gtop_u16x2 p[4]; };
 // y sweep (sdf_map.cpp:328-346): out(x,y,z) = min over candidate columns v of (y-v)^2 + in(x,v,z).
 // 32-bit index arithmetic throughout (nvox < 2^31; ny, nz < 2^15 so that v*nz is a 24-bit product).
 // LOCAL: the workgroup builds its slab's candidate list itself, in LDS, from the z sweep's per-column flags (ny <=
-// kYLocalMax) — no esdf_rows_kernel launch between the sweeps (5 us of a 110 us build at 200^3), and the list is
+// kEsdfYLocalMax) — no esdf_rows_kernel launch between the sweeps (5 us of a 110 us build at 200^3), and the list is
 // then read from LDS instead of global memory.
-constexpr int kYLocalMax = 2048;
 
 template <int V, bool LOCAL>
 __global__ void __launch_bounds__(256)
@@ -303,20 +305,16 @@ esdf_y_kernel(const GtopGrid g, const int *__restrict__ fin, int *__restrict__ f
   constexpr int U = 4;   // candidates per round trip and side
   const int nyz = g.ny * g.nz;
   const int ny = g.ny, nz = g.nz;
-  // Workgroups are dealt round-robin over the 8 XCDs, each with its own L2: slab x (whose voxels only read
-  // slab x) goes to XCD x mod 8, so a slab is fetched into ONE L2 instead of all eight.
-  // grid = 8 * ceil(nx/8) * bps workgroups, bps = ceil(nyz/V/256).
+  // slab x goes to XCD x mod 8 (gtop_esdf_y_lane, gtop_esdf_plan.h: grid = 8 * ceil(nx/8) * ceil(nyz/V/256) workgroups)
 #ifdef GTOP_ESDF_STAMPS
   const unsigned long long t0_stamp = wall_clock64();
   int trips = 0;
 #endif
-  const int bps = (nyz / V + 255) >> 8;
-  const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
-  const int x = xcd + 8 * (j / bps);
-  const int r = ((j % bps) * 256 + (int)threadIdx.x) * V;
-  __shared__ unsigned short s_cols[LOCAL ? kYLocalMax : 1];
-  __shared__ unsigned long long s_mask[LOCAL ? kYLocalMax / 64 : 1];
-  __shared__ int s_pref[LOCAL ? kYLocalMax / 64 + 1 : 1];
+  const GtopEsdfYLane yl = gtop_esdf_y_lane(blockIdx.x, (int)threadIdx.x, nyz, V);
+  const int x = yl.x, r = yl.r;
+  __shared__ unsigned short s_cols[LOCAL ? kEsdfYLocalMax : 1];
+  __shared__ unsigned long long s_mask[LOCAL ? kEsdfYLocalMax / 64 : 1];
+  __shared__ int s_pref[LOCAL ? kEsdfYLocalMax / 64 + 1 : 1];
   if constexpr (LOCAL) {
     if (x >= g.nx) return;   // (workgroup-uniform)
     if (threadIdx.x < 64) {  // one wavefront: ballots over the slab's column flags, 64 columns at a time
@@ -346,7 +344,7 @@ esdf_y_kernel(const GtopGrid g, const int *__restrict__ fin, int *__restrict__ f
       }
       if (lane == 0) {
         s_pref[(ny + 63) >> 6] = base;
-        if (j % bps == 0) {   // the slab's number of obstacle columns (0: the x sweep jumps over its rows)
+        if (yl.first) {   // the slab's number of obstacle columns (0: the x sweep jumps over its rows)
           cnt_out[x] = base;
           if (base == 0) atomicAdd(cnt_out + g.nx, 1);
         }
@@ -461,13 +459,11 @@ esdf_y16_kernel(const GtopGrid g, const uint16_t *__restrict__ fin16, const int 
   constexpr int U = 4, V = 8;   // candidates per round trip and side; voxels per lane
   const int nyz = g.ny * g.nz;
   const int ny = g.ny, nz = g.nz;
-  const int bps = (nyz / V + 255) >> 8;
-  const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
-  const int x = xcd + 8 * (j / bps);
-  const int r_raw = ((j % bps) * 256 + (int)threadIdx.x) * V;
-  __shared__ unsigned short s_cols[LOCAL ? kYLocalMax : 1];
-  __shared__ unsigned long long s_mask[LOCAL ? kYLocalMax / 64 : 1];
-  __shared__ int s_pref[LOCAL ? kYLocalMax / 64 + 1 : 1];
+  const GtopEsdfYLane yl = gtop_esdf_y_lane(blockIdx.x, (int)threadIdx.x, nyz, V);
+  const int x = yl.x, r_raw = yl.r;
+  __shared__ unsigned short s_cols[LOCAL ? kEsdfYLocalMax : 1];
+  __shared__ unsigned long long s_mask[LOCAL ? kEsdfYLocalMax / 64 : 1];
+  __shared__ int s_pref[LOCAL ? kEsdfYLocalMax / 64 + 1 : 1];
   if (x >= g.nx) return;   // (workgroup-uniform)
   if constexpr (LOCAL) {
     if (threadIdx.x < 64) {  // one wavefront: ballots over the slab's column flags (as esdf_y_kernel)
@@ -497,7 +493,7 @@ esdf_y16_kernel(const GtopGrid g, const uint16_t *__restrict__ fin16, const int 
       }
       if (lane == 0) {
         s_pref[(ny + 63) >> 6] = base;
-        if (j % bps == 0) {
+        if (yl.first) {
           cnt_out[x] = base;
           if (base == 0) atomicAdd(cnt_out + g.nx, 1);
         }
@@ -638,17 +634,13 @@ esdf_y16_kernel(const GtopGrid g, const uint16_t *__restrict__ fin16, const int 
 }
 
 // x sweep (sdf_map.cpp:348-364): out(q) = min_v ((q-v)^2 + in(v)), scanning outward; then
-// dist = min(res*sqrt(out), previous).  A lane owns a block of V voxels along z times kXB = 4 consecutive slabs
+// dist = min(res*sqrt(out), previous).  A lane owns a block of V voxels along z times kEsdfXB = 4 consecutive slabs
 // along x: the rows the four slabs' scans need overlap almost entirely, so one pass outward from the block
 // (rows q0-d and q0+3+d, distance d+e resp. d+3-e to the block's e-th slab) serves all of them — a quarter of the
 // loads of four separate scans, which is what bounded this kernel (L2 bandwidth: every row was re-read by the
 // ~2 x 20 slabs around it).  Element indices advance by +-nyz per step and are CLAMPED to the line's ends instead
 // of masked: past an end the lane re-reads the end row with a larger d, an over-estimate of a candidate it has
 // already seen, which can never win: exact.  The scan stops when (d+1)^2 >= the worst of the block's minima.
-#ifndef GTOP_ESDF_XB
-#define GTOP_ESDF_XB 4
-#endif
-constexpr int kXB = GTOP_ESDF_XB;
 
 // Slabs without any obstacle hold nothing but "no obstacle" after the y sweep: a candidate from such a row can never
 // lower a minimum (INF + d^2 >= INF).  The x scans therefore JUMP over runs of empty slabs: before a batch, if the
@@ -657,18 +649,17 @@ constexpr int kXB = GTOP_ESDF_XB;
 // and the dense path stays as it was).  Exact, and what makes sparse maps cheap — a few obstacles in a 200^3 map:
 // 189 of 200 slabs empty: x sweep 103 -> 25 us.  near[0][x] / near[1][x] = the nearest slab with obstacles at or left / at or right
 // of x (-1 / n when there is none), built by the workgroup from cnt[] (y sweep / esdf_rows_kernel) with ballots;
-// lines of more than kSlabMax slabs scan every row.
-constexpr int kSlabMax = 2048;
+// lines of more than kEsdfSlabMax slabs scan every row.
 struct EsdfSlabRuns {
-  short near[2][kSlabMax];
-  unsigned long long mask[kSlabMax / 64];
+  short near[2][kEsdfSlabMax];
+  unsigned long long mask[kEsdfSlabMax / 64];
   int any_empty;   // 0: every slab holds obstacles — the scans then never ask
 };
 __device__ __forceinline__ bool esdf_stage_slab_runs(EsdfSlabRuns *sr, const int *__restrict__ cnt, int n) {
   // (building the tables costs a workgroup ~2 us: only where at least a quarter of the slabs is empty — cnt[n] counts
   // them — i.e. where the jumps pay; 200^3 at 2 % occupancy has 31 empty slabs and gains nothing, 400^3 at 4 % has a
   // handful and 16 000 workgroups)
-  if (n <= kSlabMax && cnt[n] * 4 >= n) {
+  if (gtop_esdf_slab_tables_possible(n) && cnt[n] * 4 >= n) {
     const int lane = threadIdx.x & 63, nw = blockDim.x >> 6, w = threadIdx.x >> 6, nch = (n + 63) >> 6;
     if (threadIdx.x == 0) sr->any_empty = 0;
     __syncthreads();
@@ -725,7 +716,7 @@ __device__ __forceinline__ double esdf_interior(double res, double neg_depth, do
   return v > neg_depth ? v : neg_depth;
 }
 
-// the scan of one lane's block: V voxels from `first` (slab 0) times the kXB slabs from q0
+// the scan of one lane's block: V voxels from `first` (slab 0) times the kEsdfXB slabs from q0
 template <int V, bool SIGNED = false>
 __device__ __forceinline__ void esdf_x_scan_block(const GtopGrid &g, const int *__restrict__ fin, double *__restrict__ dist,
                                                   float *__restrict__ dist32, const int first, const int q0,
@@ -752,21 +743,21 @@ __device__ __forceinline__ void esdf_x_scan_block(const GtopGrid &g, const int *
   const int n = g.nx;
   const int last = first + (n - 1) * nyz;   // the line's end voxels: first, last
   // the block's own rows (slabs past the end of the line shadow the last one; they are not stored)
-  int row[kXB];
-  IntV<V> best[kXB];
+  int row[kEsdfXB];
+  IntV<V> best[kEsdfXB];
 #pragma unroll
-  for (int e = 0; e < kXB; ++e) {
+  for (int e = 0; e < kEsdfXB; ++e) {
     row[e] = first + min(q0 + e, n - 1) * nyz;
     best[e] = load_row(row[e]);
   }
   {
-    IntV<V> own[kXB];
+    IntV<V> own[kEsdfXB];
 #pragma unroll
-    for (int e = 0; e < kXB; ++e) own[e] = best[e];
+    for (int e = 0; e < kEsdfXB; ++e) own[e] = best[e];
 #pragma unroll
-    for (int e = 0; e < kXB; ++e)
+    for (int e = 0; e < kEsdfXB; ++e)
 #pragma unroll
-      for (int o = 0; o < kXB; ++o)
+      for (int o = 0; o < kEsdfXB; ++o)
         if (o != e)
 #pragma unroll
           for (int v = 0; v < V; ++v) best[e].v[v] = min(best[e].v[v], (e - o) * (e - o) + own[o].v[v]);
@@ -774,15 +765,15 @@ __device__ __forceinline__ void esdf_x_scan_block(const GtopGrid &g, const int *
   auto worst_of = [&]() {
     int w = 0;
 #pragma unroll
-    for (int e = 0; e < kXB; ++e)
+    for (int e = 0; e < kEsdfXB; ++e)
 #pragma unroll
       for (int v = 0; v < V; ++v) w = max(w, best[e].v[v]);
     return w;
   };
   int worst = worst_of();
-  const int reach = max(max(q0, n - kXB - q0), 0);
-  int lo = row[0], hi = row[kXB - 1], d = 0;
-  int xl = q0, xh = min(q0 + kXB - 1, n - 1);   // the slabs of lo / hi
+  const int reach = max(max(q0, n - kEsdfXB - q0), 0);
+  int lo = row[0], hi = row[kEsdfXB - 1], d = 0;
+  int xl = q0, xh = min(q0 + kEsdfXB - 1, n - 1);   // the slabs of lo / hi
   int run_ahead = esdf_empty_run(sr, n, xl, xh);
   // The loads of a batch are independent and issue together; entries past the exact
   // cut-off cannot win (in(v) >= 0), so reading a few of them changes nothing.
@@ -815,8 +806,8 @@ __device__ __forceinline__ void esdf_x_scan_block(const GtopGrid &g, const int *
     for (int u = 0; u < kScanBatch; ++u) {
       ++d;
 #pragma unroll
-      for (int e = 0; e < kXB; ++e) {
-        const int dl = d + e, dr = d + (kXB - 1 - e);
+      for (int e = 0; e < kEsdfXB; ++e) {
+        const int dl = d + e, dr = d + (kEsdfXB - 1 - e);
         const int dl2 = __mul24(dl, dl), dr2 = __mul24(dr, dr);   // (24-bit multiplies are full rate, 32-bit ones a
                                                                   // quarter; d <= 2^15, f <= kInf: sums below 2^31)
 #pragma unroll
@@ -829,7 +820,7 @@ __device__ __forceinline__ void esdf_x_scan_block(const GtopGrid &g, const int *
   // sdf_map.cpp:355-361: min(res*sqrt(val), previous) with previous = 10000 after the
   // reset; a line without obstacles carries DBL_MAX there, i.e. keeps the 10000
 #pragma unroll
-  for (int e = 0; e < kXB; ++e) {
+  for (int e = 0; e < kEsdfXB; ++e) {
     if (q0 + e >= n) break;
 #pragma unroll
     for (int v = 0; v < V; ++v) {
@@ -853,36 +844,23 @@ __device__ __forceinline__ void esdf_x_scan_block(const GtopGrid &g, const int *
 }
 
 
-// XCD-aware order of the x sweep's work: a lane of the yz plane belongs to ONE XCD for every slab block, block
-// after block — the rows a lane reads are then shared, in one L2, with the lanes of the neighbouring slab blocks
-// that run at the same time (dealt linearly, every XCD walked every slab: 1.44 ms -> 0.96 ms at 400^3 with this
-// order).  grid = 8 * ceil(n/kXB) * bpp workgroups, bpp = workgroups per XCD and slab block, nl = lanes per slab
-// block.  Returns false for a lane without work.
-template <int BLOCK = 256, bool SHADOW = false>
+// The x sweep's lane: XCD-aware, 64-lane chunks of the yz plane dealt round-robin over the XCDs (gtop_esdf_x_lane,
+// gtop_esdf_plan.h, which also states the grid: gtop_esdf_x_blocks).  nl = lanes per slab block.  Returns false for a
+// lane without work.
+template <int BLOCK = kEsdfXBlock, bool SHADOW = false>
 __device__ __forceinline__ bool esdf_x_lane(const int nl, int *fl, int *q0) {
-#ifdef GTOP_ESDF_X_PARTS   // round 2's first form: XCD c owns the c-th eighth of the plane (one contiguous part)
+#ifdef GTOP_ESDF_X_PARTS   // tuning, round 2's first form: XCD c owns the c-th eighth of the plane (one contiguous part)
   const int part = (nl + 7) >> 3, bpp = (part + BLOCK - 1) / BLOCK;
   const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
   const int li = (j % bpp) * BLOCK + (int)threadIdx.x;
-  *q0 = (j / bpp) * kXB;
+  *q0 = (j / bpp) * kEsdfXB;
   *fl = xcd * part + li;
   return li < part && *fl < nl;
 #else
-  // 64-lane chunks of the plane dealt round-robin over the XCDs: the same lanes of every slab block still meet in
-  // one L2, and every XCD gets an even sample of the map (with one contiguous eighth each, the XCD that owned the
-  // most open space finished 10 us after the others at 200^3)
-  const int cpx = (((nl + 63) >> 6) + 7) >> 3, bpp = (cpx * 64 + BLOCK - 1) / BLOCK;   // chunks, workgroups per XCD
-  const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
-  const int li = (j % bpp) * BLOCK + (int)threadIdx.x;
-  *q0 = (j / bpp) * kXB;
-  *fl = (((li >> 6) << 3) + xcd) * 64 + (li & 63);
-  if (SHADOW) {   // a wavefront with any work keeps all its lanes: those past the end shadow the last lane with work
-    const int wave_first = *fl - (li & 63);
-    if ((li >> 6) >= cpx || wave_first >= nl) return false;
-    if (*fl >= nl) *fl = nl - 1;
-    return true;
-  }
-  return (li >> 6) < cpx && *fl < nl;
+  const GtopEsdfXLane l = gtop_esdf_x_lane(blockIdx.x, (int)threadIdx.x, nl, BLOCK, SHADOW);
+  *q0 = l.q0;
+  *fl = l.fl;
+  return l.work;
 #endif
 }
 
@@ -919,7 +897,7 @@ esdf_x_signed_kernel(const GtopGrid g, const int *__restrict__ fin, double *__re
 // The x sweep on packed 16-bit values.  Squared distances below 2^16 (255 voxels: 51 m at the reference's 0.2 m)
 // fit 16 bits, and the min-plus step on two voxels is then ONE v_pk_add_u16 (saturating) + ONE v_pk_min_u16 —
 // a third of the 32-bit form's instructions per candidate — and a 16-byte load brings 8 voxels.  The y sweep
-// leaves min(value, 0xFFFF) beside its int32 output; a lane owns 8 voxels along z times kXB slabs.  The packed scan
+// leaves min(value, 0xFFFF) beside its int32 output; a lane owns 8 voxels along z times kEsdfXB slabs.  The packed scan
 // returns min(exact, 0xFFFF) for every voxel whatever the inputs: a saturated candidate (>= 0xFFFF, d^2 clamped
 // likewise) can never beat a minimum below 0xFFFF and unsaturated ones are exact.  A wavefront that ends with a
 // saturated minimum (more than 255 voxels of free space, a line without obstacles) takes the 32-bit scan above for
@@ -948,13 +926,9 @@ __device__ __forceinline__ double esdf_sqrt_u16(int n) {
 #endif
 }
 
-#ifndef GTOP_ESDF_X16_BLOCK
-#define GTOP_ESDF_X16_BLOCK 128
-#endif
 #ifndef GTOP_ESDF_X16_BATCH
 #define GTOP_ESDF_X16_BATCH 4
 #endif
-constexpr int kX16Block = GTOP_ESDF_X16_BLOCK;
 
 template <bool SIGNED>
 __device__ __forceinline__ void esdf_x16_body(const GtopGrid &g, const uint16_t *__restrict__ f16, const int *__restrict__ fin,
@@ -970,22 +944,22 @@ __device__ __forceinline__ void esdf_x16_body(const GtopGrid &g, const uint16_t 
 #ifdef GTOP_ESDF_STAMPS
   const unsigned long long t0 = wall_clock64();
 #endif
-  if (!esdf_x_lane<kX16Block, true>(nyz >> 3, &fl, &q0)) return;   // (whole wavefronts only: see the epilogue)
+  if (!esdf_x_lane<kEsdfX16Block, true>(nyz >> 3, &fl, &q0)) return;   // (whole wavefronts only: see the epilogue)
   // first voxel of the wavefront's chunk of the plane: lane 0 is never a shadow
   const int wave_base = __builtin_amdgcn_readfirstlane(fl) << 3;
   const int first = fl << 3;
   const int last = first + (n - 1) * nyz;
-  int row[kXB];
-  PkV best[kXB];
+  int row[kEsdfXB];
+  PkV best[kEsdfXB];
 #pragma unroll
-  for (int e = 0; e < kXB; ++e) {
+  for (int e = 0; e < kEsdfXB; ++e) {
     row[e] = first + min(q0 + e, n - 1) * nyz;
     best[e] = *reinterpret_cast<const PkV *>(f16 + row[e]);
   }
   auto worst_of = [&]() {
     gtop_u16x2 w = best[0].p[0];
 #pragma unroll
-    for (int e = 0; e < kXB; ++e)
+    for (int e = 0; e < kEsdfXB; ++e)
 #pragma unroll
       for (int p = 0; p < 4; ++p) w = __builtin_elementwise_max(w, best[e].p[p]);
     return max((int)w.x, (int)w.y);
@@ -998,13 +972,13 @@ __device__ __forceinline__ void esdf_x16_body(const GtopGrid &g, const uint16_t 
     return r;
   };
   {
-    PkV own[kXB];
+    PkV own[kEsdfXB];
 #pragma unroll
-    for (int e = 0; e < kXB; ++e) own[e] = best[e];
+    for (int e = 0; e < kEsdfXB; ++e) own[e] = best[e];
 #pragma unroll
-    for (int e = 0; e < kXB; ++e)
+    for (int e = 0; e < kEsdfXB; ++e)
 #pragma unroll
-      for (int o = 0; o < kXB; ++o)
+      for (int o = 0; o < kEsdfXB; ++o)
         if (o != e) {
           const gtop_u16x2 dd = splat(e - o);
 #pragma unroll
@@ -1013,9 +987,9 @@ __device__ __forceinline__ void esdf_x16_body(const GtopGrid &g, const uint16_t 
         }
   }
   int worst = worst_of();
-  const int reach = max(max(q0, n - kXB - q0), 0);
-  int lo = row[0], hi = row[kXB - 1], d = 0;
-  int xl = q0, xh = min(q0 + kXB - 1, n - 1);   // the slabs of lo / hi
+  const int reach = max(max(q0, n - kEsdfXB - q0), 0);
+  int lo = row[0], hi = row[kEsdfXB - 1], d = 0;
+  int xl = q0, xh = min(q0 + kEsdfXB - 1, n - 1);   // the slabs of lo / hi
   int run_ahead = esdf_empty_run(sr, n, xl, xh);
   while (d < reach) {
     if (__mul24(d + 1, d + 1) >= worst) break;
@@ -1046,8 +1020,8 @@ __device__ __forceinline__ void esdf_x16_body(const GtopGrid &g, const uint16_t 
     for (int u = 0; u < kScanBatch; ++u) {
       ++d;
 #pragma unroll
-      for (int e = 0; e < kXB; ++e) {
-        const gtop_u16x2 sl = splat(d + e), sr = splat(d + (kXB - 1 - e));
+      for (int e = 0; e < kEsdfXB; ++e) {
+        const gtop_u16x2 sl = splat(d + e), sr = splat(d + (kEsdfXB - 1 - e));
 #pragma unroll
         for (int p = 0; p < 4; ++p)
           best[e].p[p] = __builtin_elementwise_min(
@@ -1072,10 +1046,10 @@ __device__ __forceinline__ void esdf_x16_body(const GtopGrid &g, const uint16_t 
   // 4s .. 4s+3; lane l then reads word 64k + l, k = 0 .. 3: the voxel pair 128k + 2l of the wavefront's 512), so
   // that every store instruction writes 1 KB of whole lines (the vector-memory path was 79 % busy at 400^3, nearly
   // half of its requests these partial lines).
-  __shared__ unsigned int s_tr[kX16Block / 64][256];
+  __shared__ unsigned int s_tr[kEsdfX16Block / 64][256];
   const int wv = (int)threadIdx.x >> 6, ln = (int)threadIdx.x & 63;
 #pragma unroll
-  for (int e = 0; e < kXB; ++e) {
+  for (int e = 0; e < kEsdfXB; ++e) {
     if (q0 + e >= n) break;
     __builtin_amdgcn_wave_barrier();
     *reinterpret_cast<uint4 *>(&s_tr[wv][4 * ln]) = *reinterpret_cast<const uint4 *>(&best[e]);
@@ -1115,7 +1089,7 @@ __device__ __forceinline__ void esdf_x16_body(const GtopGrid &g, const uint16_t 
 #endif
 }
 
-__global__ void __launch_bounds__(kX16Block)
+__global__ void __launch_bounds__(kEsdfX16Block)
 #ifdef GTOP_ESDF_X16_WPE
 __attribute__((amdgpu_waves_per_eu(GTOP_ESDF_X16_WPE)))
 #endif
@@ -1125,7 +1099,7 @@ esdf_x16_kernel(const GtopGrid g, const uint16_t *__restrict__ f16, const int *_
 }
 
 // the signed field's interior pass (see esdf_x_signed_kernel)
-__global__ void __launch_bounds__(kX16Block)
+__global__ void __launch_bounds__(kEsdfX16Block)
 esdf_x16_signed_kernel(const GtopGrid g, const uint16_t *__restrict__ f16, const int *__restrict__ fin,
                        double *__restrict__ dist, float *__restrict__ dist32, const int *__restrict__ cnt,
                        const uint8_t *__restrict__ occ, double neg_depth) {
@@ -1152,95 +1126,71 @@ hipError_t gtop_launch_esdf_mark(const GtopGrid &g, const double *pts, int npts,
   return hipGetLastError();
 }
 
+// Both are views of the launch plan (gtop_esdf_plan.h).
 bool gtop_esdf_supported(const GtopGrid &g) {
-  return g.nz <= 64 * kMaxChunks && g.nx <= 32768 && g.ny <= 32768;
+  GtopEsdfPlan p;
+  return gtop_esdf_plan(g.nx, g.ny, g.nz, &p);
 }
 
 size_t gtop_esdf_rows_ints(const GtopGrid &g) {
-  const size_t ncol = (size_t)g.nx * g.ny;
-  const size_t nvox = ncol * (size_t)g.nz;
-  // cols, rank, cnt (+ the count of empty slabs), colany (bytes), padding to 16 bytes, the y sweep's 16-bit output, the
-  // z sweep's 16-bit output (each nvox 16-bit words, rounded up to 16 bytes)
-  return ((2 * ncol + (size_t)g.nx + 1 + (ncol + 3) / 4 + 3) & ~(size_t)3) + 2 * (((nvox + 1) / 2 + 3) & ~(size_t)3);   // (cnt: nx + 1)
+  GtopEsdfPlan p;
+  gtop_esdf_plan(g.nx, g.ny, g.nz, &p);
+  return p.rows_ints;
 }
 
 // One exact transform and its store.  FREE = false: seeds are the occupied voxels, every voxel gets
 // min(res*sqrt(n), 10000).  FREE = true (the signed field's second transform): seeds are the free voxels, and only the
-// occupied voxels are stored, as esdf_interior.  The y sweeps run unchanged on either.
+// occupied voxels are stored, as esdf_interior.  The y sweeps run unchanged on either.  Which kernel serves a sweep, and
+// on what grid, is the plan's (gtop_esdf_plan): nothing below looks at the grid's sizes.
 template <bool FREE>
 static hipError_t esdf_build_pass(const GtopGrid &g, const uint8_t *occ, int *tmp1, int *tmp2, int *rows, double *dist,
                                   float *dist32, double neg_depth, hipStream_t stream) {
-  const size_t ncol = (size_t)g.nx * g.ny;
-  int *cols = rows, *rank = rows + ncol, *cnt = rows + 2 * ncol;
-  uint8_t *colany = reinterpret_cast<uint8_t *>(rows + 2 * ncol + g.nx + 1);   // cnt[nx] = number of empty slabs
-  uint16_t *f16 = reinterpret_cast<uint16_t *>(rows + ((2 * ncol + (size_t)g.nx + 1 + (ncol + 3) / 4 + 3) & ~(size_t)3));
-  const size_t nvox_all = ncol * (size_t)g.nz;
-  uint16_t *z16_buf = f16 + 2 * (((nvox_all + 1) / 2 + 3) & ~(size_t)3);   // behind the y sweep's 16-bit output
-#ifndef GTOP_ESDF_Y16
-#define GTOP_ESDF_Y16 1
-#endif
-#ifndef GTOP_ESDF_X16
-#define GTOP_ESDF_X16 1
-#endif
-#ifndef GTOP_ESDF_VEC
-#define GTOP_ESDF_VEC 4
-#endif
-  // the packed 16-bit y sweep (8 voxels per lane): where the packed x sweep runs and a lane's 8 voxels share a y
-  const bool y16k = GTOP_ESDF_Y16 && GTOP_ESDF_X16 && GTOP_ESDF_VEC == 4 && g.nz % 8 == 0;
-  uint16_t *z16 = y16k ? z16_buf : (uint16_t *)nullptr;
-  const unsigned zblocks = (unsigned)((ncol + 3) / 4 < 65536 ? (ncol + 3) / 4 : 65536);
+  GtopEsdfPlan p;
+  if (!gtop_esdf_plan(g.nx, g.ny, g.nz, &p)) return hipErrorInvalidValue;   // (the callers ask gtop_esdf_supported first)
+  int *cols = rows, *rank = rows + p.off_rank, *cnt = rows + p.off_cnt;     // cnt[nx] = number of empty slabs
+  uint8_t *colany = reinterpret_cast<uint8_t *>(rows + p.off_colany);
+  uint16_t *f16 = reinterpret_cast<uint16_t *>(rows + p.off_y16);
+  // the z sweep's 16-bit output, read by the packed y sweep alone
+  uint16_t *z16 = p.y_vox == 8 ? reinterpret_cast<uint16_t *>(rows + p.off_z16) : (uint16_t *)nullptr;
+  const dim3 zgrid(p.z_blocks), zblock(kEsdfZBlock);
 #define ZS(NCH) (esdf_z_small_kernel<NCH, FREE>)
-  switch ((g.nz + 63) >> 6) {
-    case 1: hipLaunchKernelGGL(ZS(1), dim3(zblocks), dim3(256), 0, stream, g, occ, tmp1, z16, colany, cnt + g.nx); break;
-    case 2: hipLaunchKernelGGL(ZS(2), dim3(zblocks), dim3(256), 0, stream, g, occ, tmp1, z16, colany, cnt + g.nx); break;
-    case 3: hipLaunchKernelGGL(ZS(3), dim3(zblocks), dim3(256), 0, stream, g, occ, tmp1, z16, colany, cnt + g.nx); break;
-    case 4: hipLaunchKernelGGL(ZS(4), dim3(zblocks), dim3(256), 0, stream, g, occ, tmp1, z16, colany, cnt + g.nx); break;
-    case 5: hipLaunchKernelGGL(ZS(5), dim3(zblocks), dim3(256), 0, stream, g, occ, tmp1, z16, colany, cnt + g.nx); break;
-    case 6: hipLaunchKernelGGL(ZS(6), dim3(zblocks), dim3(256), 0, stream, g, occ, tmp1, z16, colany, cnt + g.nx); break;
-    case 7: hipLaunchKernelGGL(ZS(7), dim3(zblocks), dim3(256), 0, stream, g, occ, tmp1, z16, colany, cnt + g.nx); break;
-    case 8: hipLaunchKernelGGL(ZS(8), dim3(zblocks), dim3(256), 0, stream, g, occ, tmp1, z16, colany, cnt + g.nx); break;
-    default: hipLaunchKernelGGL((FREE ? esdf_z_free_kernel : esdf_z_kernel), dim3(zblocks), dim3(256), 0, stream, g, occ, tmp1, z16, colany, cnt + g.nx);
+  if (p.z_lds) {
+    hipLaunchKernelGGL((FREE ? esdf_z_free_kernel : esdf_z_kernel), zgrid, zblock, 0, stream, g, occ, tmp1, z16, colany, cnt + g.nx);
+  } else {
+    switch (p.z_chunks) {
+      case 1: hipLaunchKernelGGL(ZS(1), zgrid, zblock, 0, stream, g, occ, tmp1, z16, colany, cnt + g.nx); break;
+      case 2: hipLaunchKernelGGL(ZS(2), zgrid, zblock, 0, stream, g, occ, tmp1, z16, colany, cnt + g.nx); break;
+      case 3: hipLaunchKernelGGL(ZS(3), zgrid, zblock, 0, stream, g, occ, tmp1, z16, colany, cnt + g.nx); break;
+      case 4: hipLaunchKernelGGL(ZS(4), zgrid, zblock, 0, stream, g, occ, tmp1, z16, colany, cnt + g.nx); break;
+      case 5: hipLaunchKernelGGL(ZS(5), zgrid, zblock, 0, stream, g, occ, tmp1, z16, colany, cnt + g.nx); break;
+      case 6: hipLaunchKernelGGL(ZS(6), zgrid, zblock, 0, stream, g, occ, tmp1, z16, colany, cnt + g.nx); break;
+      case 7: hipLaunchKernelGGL(ZS(7), zgrid, zblock, 0, stream, g, occ, tmp1, z16, colany, cnt + g.nx); break;
+      case 8: hipLaunchKernelGGL(ZS(8), zgrid, zblock, 0, stream, g, occ, tmp1, z16, colany, cnt + g.nx); break;
+      default: return hipErrorInvalidValue;   // (a grid without columns)
+    }
   }
 #undef ZS
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-#ifndef GTOP_ESDF_YLOCAL
-#define GTOP_ESDF_YLOCAL 1
-#endif
-  const bool ylocal = GTOP_ESDF_YLOCAL && g.ny <= kYLocalMax;   // the y sweep lists its slab's candidates itself
-  if (!ylocal) {
-    hipLaunchKernelGGL(esdf_rows_kernel, dim3(g.nx < 65536 ? g.nx : 65536), dim3(64), 0, stream, g,
-                       (const uint8_t *)colany, cols, rank, cnt);
+  const bool ylocal = !p.rows_kernel;   // the y sweep lists its slab's candidates itself
+  if (p.rows_kernel) {
+    hipLaunchKernelGGL(esdf_rows_kernel, dim3(p.rows_blocks), dim3(64), 0, stream, g, (const uint8_t *)colany, cols, rank, cnt);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
-  const int nyz = g.ny * g.nz;
-  const int V = (GTOP_ESDF_VEC == 4 && g.nz % 4 == 0) ? 4 : 1;   // voxels per lane (16-byte loads need nz % 4 == 0)
-  const int nl = nyz / V;
-  const unsigned yblocks = 8u * (unsigned)((g.nx + 7) / 8) * (unsigned)((nl + 255) / 256);
-  auto x_blocks = [&](int lanes, int block) {   // esdf_x_lane's grid: 8 XCDs x slab blocks x workgroups per XCD
-#ifdef GTOP_ESDF_X_PARTS
-    const int per_xcd = (lanes + 7) >> 3;
-#else
-    const int per_xcd = ((((lanes + 63) >> 6) + 7) >> 3) * 64;
-#endif
-    return 8u * (unsigned)((g.nx + kXB - 1) / kXB) * (unsigned)((per_xcd + block - 1) / block);
-  };
-  const unsigned xblocks = x_blocks(nl, 256);
-  const bool x16 = GTOP_ESDF_X16 && V == 4 && nyz % 8 == 0;   // the packed 16-bit x sweep (8 voxels per lane)
-  uint16_t *y16 = x16 ? f16 : (uint16_t *)nullptr;
-#define GTOP_Y_LAUNCH(VV, LL)                                                                                       \
-  hipLaunchKernelGGL((esdf_y_kernel<VV, LL>), dim3(yblocks), dim3(256), 0, stream, g, (const int *)tmp1, tmp2, y16, \
+  uint16_t *y16 = p.y_writes_16 ? f16 : (uint16_t *)nullptr;   // the packed x sweep's input
+  const dim3 ygrid(p.y_blocks), yblock(kEsdfYBlock);
+#define GTOP_Y_LAUNCH(VV, LL)                                                                              \
+  hipLaunchKernelGGL((esdf_y_kernel<VV, LL>), ygrid, yblock, 0, stream, g, (const int *)tmp1, tmp2, y16, \
                      (const int *)cols, (const int *)rank, (const int *)cnt, (const uint8_t *)colany, cnt)
-  if (y16k) {
-    const unsigned y16blocks = 8u * (unsigned)((g.nx + 7) / 8) * (unsigned)((nyz / 8 + 255) / 256);
+  if (p.y_vox == 8) {
     if (ylocal)
-      hipLaunchKernelGGL(esdf_y16_kernel<true>, dim3(y16blocks), dim3(256), 0, stream, g, (const uint16_t *)z16, (const int *)tmp1,
+      hipLaunchKernelGGL(esdf_y16_kernel<true>, ygrid, yblock, 0, stream, g, (const uint16_t *)z16, (const int *)tmp1,
                          tmp2, y16, (const int *)cols, (const int *)rank, (const int *)cnt, (const uint8_t *)colany, cnt);
     else
-      hipLaunchKernelGGL(esdf_y16_kernel<false>, dim3(y16blocks), dim3(256), 0, stream, g, (const uint16_t *)z16, (const int *)tmp1,
+      hipLaunchKernelGGL(esdf_y16_kernel<false>, ygrid, yblock, 0, stream, g, (const uint16_t *)z16, (const int *)tmp1,
                          tmp2, y16, (const int *)cols, (const int *)rank, (const int *)cnt, (const uint8_t *)colany, cnt);
-  } else if (V == 4) {
+  } else if (p.y_vox == 4) {
     if (ylocal) GTOP_Y_LAUNCH(4, true);
     else GTOP_Y_LAUNCH(4, false);
   } else {
@@ -1250,28 +1200,27 @@ static hipError_t esdf_build_pass(const GtopGrid &g, const uint8_t *occ, int *tm
 #undef GTOP_Y_LAUNCH
   e = hipGetLastError();
   if (e != hipSuccess) return e;
+  const dim3 xgrid(p.x_blocks), xblock(p.x_block);
   if constexpr (FREE) {
-    if (x16) {
-      hipLaunchKernelGGL(esdf_x16_signed_kernel, dim3(x_blocks(nyz >> 3, kX16Block)), dim3(kX16Block), 0, stream, g,
-                         (const uint16_t *)f16, (const int *)tmp2, dist, dist32, (const int *)cnt, occ, neg_depth);
-    } else if (V == 4)
-      hipLaunchKernelGGL(esdf_x_signed_kernel<4>, dim3(xblocks), dim3(256), 0, stream, g, (const int *)tmp2, dist, dist32,
+    if (p.x_vox == 8) {
+      hipLaunchKernelGGL(esdf_x16_signed_kernel, xgrid, xblock, 0, stream, g, (const uint16_t *)f16, (const int *)tmp2, dist,
+                         dist32, (const int *)cnt, occ, neg_depth);
+    } else if (p.x_vox == 4)
+      hipLaunchKernelGGL(esdf_x_signed_kernel<4>, xgrid, xblock, 0, stream, g, (const int *)tmp2, dist, dist32,
                          (const int *)cnt, occ, neg_depth);
     else
-      hipLaunchKernelGGL(esdf_x_signed_kernel<1>, dim3(xblocks), dim3(256), 0, stream, g, (const int *)tmp2, dist, dist32,
+      hipLaunchKernelGGL(esdf_x_signed_kernel<1>, xgrid, xblock, 0, stream, g, (const int *)tmp2, dist, dist32,
                          (const int *)cnt, occ, neg_depth);
     return hipGetLastError();
   }
   (void)neg_depth;
-  if (x16) {
-    hipLaunchKernelGGL(esdf_x16_kernel, dim3(x_blocks(nyz >> 3, kX16Block)), dim3(kX16Block), 0, stream, g, (const uint16_t *)f16,
-                       (const int *)tmp2, dist, dist32, (const int *)cnt);
-  } else if (V == 4)
-    hipLaunchKernelGGL(esdf_x_kernel<4>, dim3(xblocks), dim3(256), 0, stream, g, (const int *)tmp2, dist, dist32,
+  if (p.x_vox == 8) {
+    hipLaunchKernelGGL(esdf_x16_kernel, xgrid, xblock, 0, stream, g, (const uint16_t *)f16, (const int *)tmp2, dist, dist32,
                        (const int *)cnt);
+  } else if (p.x_vox == 4)
+    hipLaunchKernelGGL(esdf_x_kernel<4>, xgrid, xblock, 0, stream, g, (const int *)tmp2, dist, dist32, (const int *)cnt);
   else
-    hipLaunchKernelGGL(esdf_x_kernel<1>, dim3(xblocks), dim3(256), 0, stream, g, (const int *)tmp2, dist, dist32,
-                       (const int *)cnt);
+    hipLaunchKernelGGL(esdf_x_kernel<1>, xgrid, xblock, 0, stream, g, (const int *)tmp2, dist, dist32, (const int *)cnt);
   return hipGetLastError();
 }
 

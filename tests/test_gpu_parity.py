@@ -35,6 +35,28 @@ def test_esdf_bit_exact(scene):
     assert np.array_equal(d, sdf.dist)
 
 
+# What each shape of test_esdf_grid_shapes_bit_exact is there for, as the cell of the builder's launch plan it must land in
+# (tests/esdf_plan.py cell(): z sweep variant, z sweep strided, esdf_rows_kernel runs, voxels per lane of the y sweep, of
+# the x sweep, slab tables possible) — asserted before the build, so a threshold that moves fails the shape instead of
+# quietly uncovering its variant.  The limits themselves: tests/test_gpu_esdf_limits.py.
+ESDF_SHAPE_CELLS = {
+    (40, 24, 16): (1, False, False, 8, 8, True),       # packed 16-bit y and x sweeps (nz % 8 == 0)
+    (300, 8, 8): (1, False, False, 8, 8, True),
+    (100, 16, 16): (1, False, False, 8, 8, True),
+    (64, 64, 12): (1, False, False, 4, 8, True),       # nz % 8 == 4, ny*nz % 8 == 0: 32-bit y sweep, packed x sweep
+    (17, 10, 6): (1, False, False, 1, 1, True),        # nz % 4 != 0: one voxel per lane
+    (20, 5, 4): (1, False, False, 4, 4, True),         # ny*nz % 8 != 0: 32-bit x sweep with four voxels per lane
+    (3, 2, 8): (1, False, False, 8, 8, True),
+    (260, 260, 8): (1, False, False, 8, 8, True),
+    (4, 2056, 8): (1, False, True, 8, 8, True),        # ny past the in-LDS candidate list: esdf_rows_kernel's lists
+    (70, 130, 68): (2, False, False, 4, 8, True),      # two 64-voxel chunks per column
+    (6, 10, 320): (5, False, False, 8, 8, True),       # five chunks per column: the scalar-mask z sweep's upper variants
+    (8, 12, 320): (5, False, False, 8, 8, True),
+    (4, 6, 520): ("lds", False, False, 8, 8, True),    # columns past 512 voxels: the LDS-mask z sweep
+    (40, 300, 16): (1, False, False, 8, 8, True),
+}
+
+
 @pytest.mark.parametrize("grid,kind", [
     ((40, 24, 16), "random"),        # packed 16-bit x sweep (nz % 4 == 0, ny*nz % 8 == 0)
     ((300, 8, 8), "one_end"),        # free space wider than 255 voxels: saturated values -> the 32-bit scan
@@ -53,7 +75,10 @@ def test_esdf_bit_exact(scene):
     ((40, 300, 16), "one_end"),      # the packed y sweep's own saturation: free space wider than 255 voxels along y
 ])
 def test_esdf_grid_shapes_bit_exact(gtop, grid, kind):
-    """The exact EDT on grid shapes that pick each sweep variant, against scipy's exact transform."""
+    """The exact EDT on grid shapes that pick each sweep variant (ESDF_SHAPE_CELLS: asserted against the builder's launch
+    plan), against scipy's exact transform."""
+    from tests import esdf_plan
+    assert esdf_plan.cell(esdf_plan.plan(grid)) == ESDF_SHAPE_CELLS[grid]
     from scipy import ndimage
     nx, ny, nz = grid
     rng = np.random.default_rng(nx * 1000 + ny * 10 + nz)
