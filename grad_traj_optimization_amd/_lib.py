@@ -114,6 +114,9 @@ def load_library():
         "gtop_eval_trajectories_device": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_double, vp, vp]),
         "gtop_trajectory_stats": (C.c_int, [vp, C.c_int, dp, C.c_double, dp, dp]),
         "gtop_set_moving_boxes": (C.c_int, [vp, C.c_int, dp, dp, dp]),
+        "gtop_set_moving_box_polynomials": (C.c_int, [vp, C.c_int, dp, dp, dp]),
+        "gtop_get_moving_box_kind": (C.c_int, [vp, ip, ip]),
+        "gtop_box_polynomial_centres": (C.c_int, [C.c_int, dp, dp, C.c_int, dp, dp]),
         "gtop_set_moving_cost": (C.c_int, [vp, C.c_int]),
         "gtop_get_moving_cost": (C.c_int, [vp, ip]),
         "gtop_set_gradient_mode": (C.c_int, [vp, C.c_int]),
@@ -195,7 +198,8 @@ def load_library():
     since = {"gtop_set_moving_cost": 4, "gtop_get_moving_cost": 4, "gtop_set_start_times": 4,
              "gtop_set_start_times_device": 4, "gtop_validate_trajectories_device": 5, "gtop_select_best_device": 5,
              "gtop_validate_batch": 5, "gtop_set_gradient_mode": 6, "gtop_get_gradient_mode": 6,
-             "gtop_group_set_gradient_mode": 6}
+             "gtop_group_set_gradient_mode": 6, "gtop_set_moving_box_polynomials": 7, "gtop_get_moving_box_kind": 7,
+             "gtop_box_polynomial_centres": 7}
     L.gtop_abi_version.restype = C.c_int
     abi = L.gtop_abi_version() if os.environ.get("GTOP_HIP_LIB") else max(since.values())
     for name, (res, args) in sig.items():
@@ -214,6 +218,24 @@ def _f64(a):
 
 def _p(a):
     return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def box_polynomial_centres(coef, times, t_range=None):
+    """Centres (ntimes, nbox, 3) of polynomial boxes at `times`, by the arithmetic every kernel uses (the clamp into
+    [t1, t2], then Horner in fp64 fmas; include/gtop.h, gtop_box_polynomial_centres).  Host only: no context, no GPU."""
+    L = load_library()
+    coef = _f64(coef).reshape(-1, 3, 6)
+    times = _f64(np.atleast_1d(times)).reshape(-1)
+    tr = None
+    if t_range is not None:
+        tr = _f64(t_range).reshape(-1, 2)
+        assert tr.shape[0] == coef.shape[0]
+    out = np.empty((times.shape[0], coef.shape[0], 3))
+    rc = L.gtop_box_polynomial_centres(coef.shape[0], _p(coef), None if tr is None else _p(tr), times.shape[0], _p(times),
+                                       _p(out))
+    if rc != 0:
+        raise GtopError(rc, "box_polynomial_centres: bad arguments (a non-finite coefficient, t1 > t2, a NaN bound)")
+    return out
 
 
 class GtopContext:
@@ -497,6 +519,28 @@ class GtopContext:
         p0, vel, scale = (_f64(a).reshape(-1, 3) for a in (p0, vel, scale))
         assert p0.shape == vel.shape == scale.shape
         self._chk(self._L.gtop_set_moving_boxes(self._h, p0.shape[0], _p(p0), _p(vel), _p(scale)))
+
+    BOXES_CONST_VEL, BOXES_POLYNOMIAL = 0, 1
+
+    def set_moving_box_polynomials(self, coef, scale, t_range=None):
+        """The box list as polynomial predictions (include/gtop.h, gtop_set_moving_box_polynomials): coef (nbox, 3, 6),
+        axis-major, ascending powers; scale (nbox, 3); t_range (nbox, 2) = {t1, t2} per box, None = unbounded.  Outside
+        [t1, t2] a box stands where its prediction ends.  Replaces whatever list was set, of either kind."""
+        coef = _f64(coef).reshape(-1, 3, 6)
+        scale = _f64(scale).reshape(-1, 3)
+        assert coef.shape[0] == scale.shape[0]
+        tr = None
+        if t_range is not None:
+            tr = _f64(t_range).reshape(-1, 2)
+            assert tr.shape[0] == coef.shape[0]
+        self._chk(self._L.gtop_set_moving_box_polynomials(self._h, coef.shape[0], _p(coef), None if tr is None else _p(tr),
+                                                          _p(scale)))
+
+    def moving_box_kind(self):
+        """(kind, nbox) of the list in force: BOXES_CONST_VEL or BOXES_POLYNOMIAL."""
+        kind, nbox = C.c_int(0), C.c_int(0)
+        self._chk(self._L.gtop_get_moving_box_kind(self._h, C.byref(kind), C.byref(nbox)))
+        return int(kind.value), int(nbox.value)
 
     # -- moving-obstacle cost (include/gtop.h: not in the reference's callback) --
     MOVING_COST_MAX_BOXES = 32

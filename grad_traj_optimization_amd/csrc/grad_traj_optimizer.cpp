@@ -92,6 +92,21 @@ void GradTrajOptimizer::setMovingObstacles(const std::vector<Vec3> &p0, const st
   if (last_status_ == GTOP_OK) last_status_ = gtop_set_moving_cost(ctx_, nbox > 0);
 }
 
+void GradTrajOptimizer::setMovingObstaclePredictions(const std::vector<Poly3> &coef,
+                                                     const std::vector<std::array<double, 2>> &t_range,
+                                                     const std::vector<Vec3> &scale) {
+  if (!ctx_) return;
+  if (coef.size() != scale.size() || (!t_range.empty() && t_range.size() != coef.size())) {
+    last_status_ = GTOP_ERR_INVALID;
+    return;
+  }
+  const int nbox = (int)coef.size();
+  last_status_ = gtop_set_moving_box_polynomials(ctx_, nbox, nbox ? coef[0].data() : nullptr,
+                                                 t_range.empty() ? nullptr : t_range[0].data(),
+                                                 nbox ? scale[0].data() : nullptr);
+  if (last_status_ == GTOP_OK) last_status_ = gtop_set_moving_cost(ctx_, nbox > 0);
+}
+
 void GradTrajOptimizer::setStartTime(double t0) {
   if (!ctx_) return;
   last_status_ = gtop_set_start_times(ctx_, 1, &t0);

@@ -99,6 +99,12 @@ class GradTrajOptimizer {
   // {p0, vel, scale} — centre p0 + vel t, extent +-scale/2 — and the trajectory's start time on their clock.  A
   // non-empty list switches the mode on for costFunc and optimizeTrajectory (both roads), an empty one off.
   void setMovingObstacles(const std::vector<Vec3> &p0, const std::vector<Vec3> &vel, const std::vector<Vec3> &scale);
+  // The same with polynomial predictions (gtop_set_moving_box_polynomials; the reference's PolynomialPrediction,
+  // obj_predictor.h:26-55): coef[b] = axis-major 3 x 6 coefficients in ascending powers, t_range[b] = {t1, t2} (empty
+  // vector = unbounded; outside its interval a box stands where its prediction ends), scale[b] the extent.
+  using Poly3 = std::array<double, 18>;
+  void setMovingObstaclePredictions(const std::vector<Poly3> &coef, const std::vector<std::array<double, 2>> &t_range,
+                                    const std::vector<Vec3> &scale);
   void setStartTime(double t0);
 
   // The safety report of the trajectory at the current Dp (include/gtop.h, gtop_validate_batch; not a method of the

@@ -19,7 +19,8 @@
 #include "gtop_guard.h"
 #include "gtop_kernels.h"
 
-#define GTOP_ABI_VERSION 6   // 6: gtop_set_gradient_mode, gtop_get_gradient_mode, gtop_group_set_gradient_mode
+#define GTOP_ABI_VERSION 7   // 7: gtop_set_moving_box_polynomials, gtop_get_moving_box_kind, gtop_box_polynomial_centres
+                             // 6: gtop_set_gradient_mode, gtop_get_gradient_mode, gtop_group_set_gradient_mode
                              // 5: gtop_validate_trajectories_device, gtop_select_best_device, gtop_validate_batch
                              // 4: gtop_set_moving_cost, gtop_get_moving_cost, gtop_set_start_times, gtop_set_start_times_device
                              // 3: gtop_set_field_sign, gtop_get_field_sign, gtop_group_set_field_sign
@@ -63,12 +64,14 @@ struct gtop_ctx {
   // ESDF construction workspace
   uint8_t *occ = nullptr;
   int *tmp1 = nullptr, *tmp2 = nullptr, *rows = nullptr;
-  double *boxes = nullptr;   // moving boxes: p0 | vel | scale, nbox x 3 each
+  double *boxes = nullptr;   // moving boxes: p0 | vel | scale, nbox x 3 each; a polynomial list: its [nbox][24] rows
   size_t cap_boxes = 0;
   int nbox = 0;
+  int box_kind = GTOP_BOXES_CONST_VEL;   // which of the two the one list is (gtop_set_moving_box_polynomials)
   // the moving-obstacle cost (gtop_set_moving_cost): the box list as the evaluation kernels read it — [nbox][9] rows
-  // p0, vel, scale / 2 in a buffer of GTOP_MOVING_COST_MAX_BOXES rows allocated once (its address is what a captured
-  // launch holds) and rewritten by gtop_set_moving_boxes — and the start times on the boxes' clock
+  // p0, vel, scale / 2, or the [nbox][24] rows of a polynomial list, in a buffer of GTOP_MOVING_COST_MAX_BOXES rows of
+  // the wider form allocated once (its address is what a captured launch holds) and rewritten by
+  // gtop_set_moving_boxes / gtop_set_moving_box_polynomials — and the start times on the boxes' clock
   int moving_cost = 0;
   int grad_mode = GTOP_GRADIENT_REFERENCE;   // gtop_set_gradient_mode: read by every evaluation / optimizer call as it is made
   double *box_rows = nullptr;
@@ -258,10 +261,22 @@ int fp32_records_ready(gtop_ctx *c, hipStream_t s) {
 }
 
 static_assert(GTOP_MOVING_COST_MAX_BOXES == GTOP_MOVING_MAX_BOXES, "the public box limit is the kernels' own");
+constexpr int kBoxRowPolyHost = 24;   // = kBoxRowPoly of gtop_edt_lookup.h (device code): 18 coefficients, 3 half extents, t1, t2, pad
 int ensure_box_rows(gtop_ctx *c) {
   if (c->box_rows) return GTOP_OK;
-  HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->box_rows), (size_t)GTOP_MOVING_COST_MAX_BOXES * 9 * sizeof(double)));
+  HIPCHK(c, hipMalloc(reinterpret_cast<void **>(&c->box_rows), (size_t)GTOP_MOVING_COST_MAX_BOXES * kBoxRowPolyHost * sizeof(double)));
   return GTOP_OK;
+}
+
+// The box list as the query and report launchers take it (gtop_kernels.h): a polynomial list is its rows and no
+// velocity pointer.
+struct BoxList {
+  const double *p0, *vel, *scale;
+};
+BoxList box_list(const gtop_ctx *c) {
+  const size_t n3 = (size_t)c->nbox * 3;
+  if (c->box_kind == GTOP_BOXES_POLYNOMIAL) return {c->boxes, nullptr, nullptr};
+  return {c->boxes, c->boxes + n3, c->boxes + 2 * n3};
 }
 
 template <typename R>
@@ -315,6 +330,7 @@ int moving_args(gtop_ctx *c, int B, int problem_B, GtopMovingArgs *mov) {
   mov->nbox = c->nbox;
   mov->t0 = c->t0_count > 0 ? c->t0_dev : nullptr;
   mov->t0_stride = c->t0_count > 1 ? 1 : 0;
+  mov->poly = c->box_kind == GTOP_BOXES_POLYNOMIAL;
   return GTOP_OK;
 }
 
@@ -1001,6 +1017,7 @@ int gtop_set_moving_boxes(gtop_ctx *c, int nbox, const double *p0, const double 
   if (nbox < 0 || (nbox > 0 && (!p0 || !vel || !scale))) return fail(c, GTOP_ERR_INVALID, "set_moving_boxes: bad box list");
   HIPCHK(c, hipSetDevice(c->device));
   c->nbox = 0;
+  c->box_kind = GTOP_BOXES_CONST_VEL;
   if (nbox == 0) return GTOP_OK;
   int rc;
   const size_t n3 = (size_t)nbox * 3;
@@ -1031,6 +1048,93 @@ int gtop_set_moving_boxes(gtop_ctx *c, int nbox, const double *p0, const double 
   c->nbox = nbox;
   return GTOP_OK;
 } GTOP_CATCH_STATUS(c)
+
+// ---- the polynomial box list (include/gtop.h) ----
+// The checks of gtop_set_moving_box_polynomials / gtop_box_polynomial_centres (scale NULL: not checked); NULL = fine.
+static const char *check_box_polynomials(int nbox, const double *coef, const double *t_range, const double *scale) {
+  for (int b = 0; b < nbox; ++b) {
+    for (int i = 0; i < 18; ++i)
+      if (!std::isfinite(coef[18 * b + i])) return "box polynomials: a coefficient is not finite";
+    if (t_range) {
+      const double t1 = t_range[2 * b], t2 = t_range[2 * b + 1];
+      if (std::isnan(t1) || std::isnan(t2) || t1 > t2) return "box polynomials: need t1 <= t2, neither NaN";
+    }
+    if (scale)
+      for (int k = 0; k < 3; ++k)
+        if (!(std::isfinite(scale[3 * b + k]) && scale[3 * b + k] >= 0.0))
+          return "box polynomials: scale must be finite and >= 0";
+  }
+  return nullptr;
+}
+// The centre's arithmetic, as gtop_edt_lookup.h states it for the device: the clamp, then Horner in explicit fmas.
+static double box_polynomial_centre(const double *c6, double t1, double t2, double tau) {
+  const double tc = std::fmin(std::fmax(tau, t1), t2);
+  double r = c6[5];
+  for (int i = 4; i >= 0; --i) r = std::fma(r, tc, c6[i]);
+  return r;
+}
+
+int gtop_box_polynomial_centres(int nbox, const double *coef, const double *t_range, int ntimes, const double *times,
+                                double *centres) {
+  if (nbox < 0 || ntimes < 0 || (nbox > 0 && !coef) || (ntimes > 0 && !times) || (nbox > 0 && ntimes > 0 && !centres))
+    return GTOP_ERR_INVALID;
+  if (check_box_polynomials(nbox, coef, t_range, nullptr)) return GTOP_ERR_INVALID;
+  for (int i = 0; i < ntimes; ++i)
+    for (int b = 0; b < nbox; ++b) {
+      const double t1 = t_range ? t_range[2 * b] : -INFINITY, t2 = t_range ? t_range[2 * b + 1] : INFINITY;
+      for (int k = 0; k < 3; ++k)
+        centres[((size_t)i * nbox + b) * 3 + k] = box_polynomial_centre(coef + 18 * b + 6 * k, t1, t2, times[i]);
+    }
+  return GTOP_OK;
+}
+
+int gtop_set_moving_box_polynomials(gtop_ctx *c, int nbox, const double *coef, const double *t_range,
+                                    const double *scale) try {
+  if (!c) return GTOP_ERR_INVALID;
+  if (nbox < 0 || (nbox > 0 && (!coef || !scale))) return fail(c, GTOP_ERR_INVALID, "set_moving_box_polynomials: bad box list");
+  // a bad list is refused here and the list in force stays (the cost bodies' slab distance is written for
+  // bmin <= bmax, and a NaN centre would make a box vanish from every min)
+  if (const char *why = check_box_polynomials(nbox, coef, t_range, scale)) return fail(c, GTOP_ERR_INVALID, why);
+  HIPCHK(c, hipSetDevice(c->device));
+  if (nbox == 0) {
+    c->nbox = 0;
+    c->box_kind = GTOP_BOXES_CONST_VEL;
+    return GTOP_OK;
+  }
+  std::vector<double> rows((size_t)nbox * kBoxRowPolyHost);
+  for (int b = 0; b < nbox; ++b) {
+    double *r = &rows[(size_t)b * kBoxRowPolyHost];
+    for (int i = 0; i < 18; ++i) r[i] = coef[18 * b + i];
+    for (int k = 0; k < 3; ++k) r[18 + k] = 0.5 * scale[3 * b + k];
+    r[21] = t_range ? t_range[2 * b] : -INFINITY;
+    r[22] = t_range ? t_range[2 * b + 1] : INFINITY;
+    r[23] = 0.0;
+  }
+  int rc;
+  c->nbox = 0;   // (a failure below leaves no list rather than half of one)
+  c->box_kind = GTOP_BOXES_CONST_VEL;
+  c->box_rows_ok = false;
+  if ((rc = ensure(c, &c->boxes, &c->cap_boxes, rows.size()))) return rc;
+  if ((rc = ensure_box_rows(c))) return rc;
+  HIPCHK(c, hipMemcpyAsync(c->boxes, rows.data(), rows.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  // the same rows where the evaluation kernels read them, in the buffer that never moves; a list too long for the cost
+  // term still serves the queries and the report, and an evaluation in moving mode refuses it
+  if (nbox <= GTOP_MOVING_COST_MAX_BOXES) {
+    HIPCHK(c, hipMemcpyAsync(c->box_rows, rows.data(), rows.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    c->box_rows_ok = true;
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));   // `rows` goes away
+  c->nbox = nbox;
+  c->box_kind = GTOP_BOXES_POLYNOMIAL;
+  return GTOP_OK;
+} GTOP_CATCH_STATUS(c)
+
+int gtop_get_moving_box_kind(const gtop_ctx *c, int *kind, int *nbox) {
+  if (!c || !kind || !nbox) return GTOP_ERR_INVALID;
+  *kind = c->box_kind;
+  *nbox = c->nbox;
+  return GTOP_OK;
+}
 
 int gtop_set_moving_cost(gtop_ctx *c, int enable) try {
   if (!c) return GTOP_ERR_INVALID;
@@ -1103,8 +1207,8 @@ int gtop_edt_query_device(gtop_ctx *c, int N, const void *d_pos, const void *d_t
   if (N == 0) return GTOP_OK;
   if (!d_pos || !d_time || !d_dist || !d_grad) return fail(c, GTOP_ERR_INVALID, "edt_query: NULL buffer");
   HIPCHK(c, hipSetDevice(c->device));
-  const size_t n3 = (size_t)c->nbox * 3;
-  HIPCHK(c, gtop_launch_edt_query(c->grid, c->sdf64, c->rec64, c->nbox, c->boxes, c->boxes + n3, c->boxes + 2 * n3, N,
+  const BoxList bl = box_list(c);
+  HIPCHK(c, gtop_launch_edt_query(c->grid, c->sdf64, c->rec64, c->nbox, bl.p0, bl.vel, bl.scale, N,
                                   static_cast<const double *>(d_pos), static_cast<const double *>(d_time),
                                   static_cast<double *>(d_dist), static_cast<double *>(d_grad),
                                   static_cast<hipStream_t>(hip_stream)));
@@ -1138,8 +1242,8 @@ int gtop_edt_coarse_query_device(gtop_ctx *c, int N, const void *d_pos, const vo
   if (N == 0) return GTOP_OK;
   if (!d_pos || !d_time || !d_dist) return fail(c, GTOP_ERR_INVALID, "edt_coarse_query: NULL buffer");
   HIPCHK(c, hipSetDevice(c->device));
-  const size_t n3 = (size_t)c->nbox * 3;
-  HIPCHK(c, gtop_launch_edt_query(c->grid, c->sdf64, c->rec64, c->nbox, c->boxes, c->boxes + n3, c->boxes + 2 * n3, N,
+  const BoxList bl = box_list(c);
+  HIPCHK(c, gtop_launch_edt_query(c->grid, c->sdf64, c->rec64, c->nbox, bl.p0, bl.vel, bl.scale, N,
                                   static_cast<const double *>(d_pos), static_cast<const double *>(d_time),
                                   static_cast<double *>(d_dist), nullptr, static_cast<hipStream_t>(hip_stream)));
   return GTOP_OK;
@@ -1186,9 +1290,9 @@ static int validate_on_stream(gtop_ctx *c, int B, int m, const void *d_coeff, co
   if (!d_coeff || !d_T || !d_report) return fail(c, GTOP_ERR_INVALID, "validate: NULL buffer");
   HIPCHK(c, hipSetDevice(c->device));
   const int nbox = boxes ? c->nbox : 0;
-  const size_t n3 = (size_t)c->nbox * 3;
+  const BoxList bl = box_list(c);
   const double *t0 = (boxes && c->t0_count > 0) ? c->t0_dev : nullptr;
-  HIPCHK(c, gtop_launch_traj_report(c->grid, c->rec64, nbox, c->boxes, c->boxes + n3, c->boxes + 2 * n3, B, m,
+  HIPCHK(c, gtop_launch_traj_report(c->grid, c->rec64, nbox, bl.p0, bl.vel, bl.scale, B, m,
                                     static_cast<const double *>(d_coeff), static_cast<const double *>(d_T), time_stride,
                                     dt_sample, t0, c->t0_count > 1 ? 1 : 0, lim->margin,
                                     static_cast<double *>(d_report), c->simds, s));

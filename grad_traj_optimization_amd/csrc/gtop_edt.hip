@@ -8,7 +8,9 @@
 // min(static distance, distance to the nearest box at the query's time); a
 // negative time means "static only" (:91-94).  A box is {p0, vel, scale}, its
 // centre at time t the constant-velocity prediction p0 + vel t
-// (obj_predictor.h:57-66).  That file is outside the reference's build and uses
+// (obj_predictor.h:57-66) — or, from gtop_set_moving_box_polynomials, a quintic
+// per axis on a validity interval (obj_predictor.h:26-55; gtop_edt_lookup.h).
+// That file is outside the reference's build and uses
 // an SDFMap API the in-tree class lacks, so the interpolation data are the
 // in-tree ones (sdf_map.cpp:201-219: base index, diff, per-axis clamped corner
 // loads — with time < 0 the result IS getDistWithGradTrilinear), a corner's
@@ -33,10 +35,26 @@
 #include "gtop_edt_lookup.h"
 #include "gtop_kernels.h"
 
+// This file is compiled TWICE (csrc/Makefile), as gtop_kernels.hip and gtop_validate.hip are: as it stands — the query
+// kernels for constant-velocity box lists and the launcher the C-ABI layer calls — and with -DGTOP_EDT_POLY_TU into an
+// object of its own that holds the same two kernels for POLYNOMIAL box lists (gtop_set_moving_box_polynomials; rows of
+// kBoxRowPoly = 24 doubles, gtop_edt_lookup.h) behind a launcher named gtop_launch_edt_query_poly, which the first
+// object's launcher forwards to.  So the kernels of the first object keep their names and their code, and a
+// constant-velocity launch stages the rows it always staged.
+#ifdef GTOP_EDT_POLY_TU
+#define edt_query_kernel edt_query_poly_kernel
+#define gtop_launch_edt_query gtop_launch_edt_query_poly
+constexpr bool kQueryPoly = true;
+#else
+constexpr bool kQueryPoly = false;
+#endif
+
 namespace {
 
-constexpr int kBoxChunk = 128;   // boxes staged in LDS per pass
+// boxes staged in LDS per pass: 9 KiB of rows in either object (constant velocity: rows of 9; polynomial: rows of 24)
+constexpr int kBoxChunk = 128, kBoxChunkPoly = 48;
 
+// (the polynomial object: box_p0 is the list's [nbox][kBoxRowPoly] rows, box_vel and box_scale are not read)
 template <bool COARSE>
 __global__ void __launch_bounds__(256)
 edt_query_kernel(const GtopGrid g, const double *__restrict__ field, const double *__restrict__ rec, int nbox,
@@ -44,7 +62,9 @@ edt_query_kernel(const GtopGrid g, const double *__restrict__ field, const doubl
                  const double *__restrict__ box_vel, const double *__restrict__ box_scale, int N,
                  const double *__restrict__ pos, const double *__restrict__ time, double *__restrict__ dist,
                  double *__restrict__ grad) {
-  __shared__ double bx[kBoxChunk][9];   // p0, vel, scale
+  constexpr bool POLY = kQueryPoly;
+  constexpr int kChunk = POLY ? kBoxChunkPoly : kBoxChunk, kRow = POLY ? kBoxRowPoly : kBoxRowConstVel;
+  __shared__ double bx[kChunk][kRow];   // p0, vel, scale; POLY: the list's rows as they are
   __shared__ double xyz[3 * 256];       // the workgroup's positions, later its gradients, as they lie in HBM
   const int tid = threadIdx.x;
   const size_t row0 = (size_t)blockIdx.x * 256;   // first query of the workgroup
@@ -78,19 +98,23 @@ edt_query_kernel(const GtopGrid g, const double *__restrict__ field, const doubl
   double dbox = 10000000.0;   // :64
   double vmax = 0.0;          // the largest of the 8 corner values so far
   if constexpr (!COARSE) vmax = gtop_edt_vmax(values);
-  for (int b0 = 0; b0 < nbox; b0 += kBoxChunk) {
-    const int nb = min(kBoxChunk, nbox - b0);
+  for (int b0 = 0; b0 < nbox; b0 += kChunk) {
+    const int nb = min(kChunk, nbox - b0);
     __syncthreads();
-    for (int q = tid; q < nb * 9; q += blockDim.x) {
-      const int b = q / 9, f = q - 9 * b;
-      const double *src = f < 3 ? box_p0 : (f < 6 ? box_vel : box_scale);
-      bx[b][f] = src[3 * (size_t)(b0 + b) + (f % 3)];
+    if constexpr (POLY) {
+      for (int q = tid; q < nb * kRow; q += blockDim.x) (&bx[0][0])[q] = box_p0[(size_t)b0 * kRow + q];
+    } else {
+      for (int q = tid; q < nb * 9; q += blockDim.x) {
+        const int b = q / 9, f = q - 9 * b;
+        const double *src = f < 3 ? box_p0 : (f < 6 ? box_vel : box_scale);
+        bx[b][f] = src[3 * (size_t)(b0 + b) + (f % 3)];
+      }
     }
     __syncthreads();
     if (dyn) {
       for (int b = 0; b < nb; ++b) {
         double bmin[3], bmax[3];
-        gtop_edt_box_faces(bx[b], t, bmin, bmax);
+        gtop_edt_box_faces_of<POLY>(bx[b], t, bmin, bmax);
         if constexpr (COARSE) {
           double d2 = 0.0;
           for (int k = 0; k < 3; ++k) {
@@ -141,6 +165,10 @@ hipError_t gtop_launch_edt_query(const GtopGrid &g, const double *field, const d
                                  const double *box_vel, const double *box_scale, int N, const double *pos,
                                  const double *time, double *dist, double *grad, hipStream_t stream) {
   if (N <= 0) return hipSuccess;
+#ifndef GTOP_EDT_POLY_TU
+  if (!box_vel && nbox > 0)   // a polynomial list (box_p0 = its rows): the other object's kernels
+    return gtop_launch_edt_query_poly(g, field, rec, nbox, box_p0, box_vel, box_scale, N, pos, time, dist, grad, stream);
+#endif
   if (grad)
     hipLaunchKernelGGL(edt_query_kernel<false>, dim3((N + 255) / 256), dim3(256), 0, stream, g, field, rec, nbox, box_p0,
                        box_vel, box_scale, N, pos, time, dist, grad);

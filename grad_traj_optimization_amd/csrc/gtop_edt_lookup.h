@@ -6,6 +6,8 @@
 // trilinear value.  The library is built with -ffp-contract=on, so the same source
 // expression rounds the same way wherever it is inlined: both kernels get the same
 // distance, bit for bit.  The gradient stays with the query kernel.
+// The centre of a POLYNOMIAL box (gtop_set_moving_box_polynomials) is stated here once for those two kernels and for
+// the cost bodies (mov_min_boxes, gtop_wave_kernel.h).
 // The STATIC lookup (base index, diff, trilinear value; the gradient in gtop_edt.hip) is unfused, as poly_eval is:
 // it is sdf_map.cpp's arithmetic operation for operation, so a static query returns the bits of the reference's
 // getDistWithGradTrilinear.  Fused, a gradient component that cancels between corners of very different size (free
@@ -65,6 +67,40 @@ __device__ __forceinline__ void gtop_edt_box_faces(const double *bx, double t, d
     bmax[k] = c + 0.5 * bx[6 + k];
     bmin[k] = c - 0.5 * bx[6 + k];
   }
+}
+
+// ---- the polynomial box list (gtop_set_moving_box_polynomials) ----
+// A box's centre is a quintic per axis on a validity interval (PolynomialPrediction, obj_predictor.h:26-55; the call
+// distToBox carries in a comment, edt_environment.cpp:28).  One row of kBoxRowPoly doubles per box, the same for the
+// queries, the report and the cost bodies:
+//   [6 k + i] coefficient of t^i on axis k (18);  [18 + k] half extent scale_k / 2 (3);  [21] t1;  [22] t2;  [23] pad
+// (no t_range: t1 = -inf, t2 = +inf, which clamp nothing).  The arithmetic is fixed by the interface (include/gtop.h):
+// the time clamped into [t1, t2], then Horner in explicit fp64 fmas.  These two functions are its ONE statement on the
+// device — P is whatever pointer the row is read through (LDS in the queries and the report, the constant address
+// space in the cost bodies) — so the three kernels get the same centre, bit for bit.
+constexpr int kBoxRowConstVel = 9, kBoxRowPoly = 24;
+template <typename P> __device__ __forceinline__ double gtop_box_poly_time(P row, double tau) {
+  return fmin(fmax(tau, row[21]), row[22]);
+}
+template <typename P> __device__ __forceinline__ double gtop_box_poly_centre(P row, int k, double tc) {
+  const P c = row + 6 * k;
+  return fma(fma(fma(fma(fma(c[5], tc, c[4]), tc, c[3]), tc, c[2]), tc, c[1]), tc, c[0]);
+}
+// the faces of a polynomial box at time t; the extents are stored halved (0.5 * scale is exact, so c +- that is what
+// gtop_edt_box_faces forms from the full extent)
+__device__ __forceinline__ void gtop_edt_box_faces_poly(const double *row, double t, double bmin[3], double bmax[3]) {
+  const double tc = gtop_box_poly_time(row, t);
+  for (int k = 0; k < 3; ++k) {
+    const double c = gtop_box_poly_centre(row, k, tc);
+    bmax[k] = c + row[18 + k];
+    bmin[k] = c - row[18 + k];
+  }
+}
+// either list form (POLY: a constant of the object the query / report kernel is compiled into)
+template <bool POLY>
+__device__ __forceinline__ void gtop_edt_box_faces_of(const double *row, double t, double bmin[3], double bmax[3]) {
+  if constexpr (POLY) gtop_edt_box_faces_poly(row, t, bmin, bmax);
+  else gtop_edt_box_faces(row, t, bmin, bmax);
 }
 
 // values := min(values, distance from each corner voxel's centre to the box) (edt_environment.cpp:26-73, :96-98)

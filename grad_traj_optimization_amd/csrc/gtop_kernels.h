@@ -76,9 +76,11 @@ hipError_t gtop_launch_eval_consistent(const GtopKernelArgs<R> &args, const Gtop
 #define GTOP_MOVING_MAX_BOXES 32   // = GTOP_MOVING_COST_MAX_BOXES of include/gtop.h (checked in gtop_capi.cpp)
 struct GtopMovingArgs {
   const double *rows;   // [nbox][9]: p0, vel, scale / 2 — wavefront-uniform, read through scalar loads
+                        // (poly: [nbox][24], the rows of gtop_set_moving_box_polynomials, gtop_edt_lookup.h)
   int nbox;             // 1 .. GTOP_MOVING_MAX_BOXES
   const double *t0;     // start times on the boxes' clock; NULL = all zero
   int t0_stride;        // 0 = one shared value, 1 = one per trajectory
+  int poly = 0;         // the list's kind (GTOP_BOXES_POLYNOMIAL): selects the body, so a captured launch keeps it
 };
 hipError_t gtop_launch_eval_moving(const GtopKernelArgs<double> &args, const GtopEvalPlan &plan, bool dyn,
                                    const GtopMovingArgs &mov, hipStream_t stream);
@@ -179,7 +181,14 @@ hipError_t gtop_launch_eval_trajectories(int B, int m, const double *coeff, cons
 
 // ---- static field + moving boxes (gtop_edt.hip) -----------------------------
 // field: the z-fastest fp64 buffer (the coarse query's voxel values); rec: its corner records (the interpolating query)
+// The box list, here and in gtop_launch_traj_report: box_p0 / box_vel / box_scale, nbox x 3 each — or, with box_vel ==
+// NULL, a polynomial list (gtop_set_moving_box_polynomials): box_p0 holds its [nbox][24] rows (gtop_edt_lookup.h) and
+// box_scale is not read.
 hipError_t gtop_launch_edt_query(const GtopGrid &g, const double *field, const double *rec, int nbox, const double *box_p0,
+                                 const double *box_vel, const double *box_scale, int N, const double *pos,
+                                 const double *time, double *dist, double *grad, hipStream_t stream);
+// (the object gtop_edt.hip is compiled into with -DGTOP_EDT_POLY_TU; called by gtop_launch_edt_query only)
+hipError_t gtop_launch_edt_query_poly(const GtopGrid &g, const double *field, const double *rec, int nbox, const double *box_p0,
                                  const double *box_vel, const double *box_scale, int N, const double *pos,
                                  const double *time, double *dist, double *grad, hipStream_t stream);
 
@@ -188,6 +197,12 @@ hipError_t gtop_launch_edt_query(const GtopGrid &g, const double *field, const d
 // report[b] of the trajectories (coeff, T) as include/gtop.h lays it out: the getTraj samples looked up as
 // edt_query_kernel<false> looks (pos, tau) up, tau = t0[b * t0_stride] + eval_t (t0 NULL = 0) — with nbox = 0 static only
 hipError_t gtop_launch_traj_report(const GtopGrid &g, const double *rec, int nbox, const double *box_p0,
+                                   const double *box_vel, const double *box_scale, int B, int m, const double *coeff,
+                                   const double *T, int t_stride, double dt_sample, const double *t0, int t0_stride,
+                                   double margin, double *report, int simds /* of the device: sizes the launch */,
+                                   hipStream_t stream);
+// (the object gtop_validate.hip is compiled into with -DGTOP_REPORT_POLY_TU; called by gtop_launch_traj_report only)
+hipError_t gtop_launch_traj_report_poly(const GtopGrid &g, const double *rec, int nbox, const double *box_p0,
                                    const double *box_vel, const double *box_scale, int B, int m, const double *coeff,
                                    const double *T, int t_stride, double dt_sample, const double *t0, int t0_stride,
                                    double margin, double *report, int simds /* of the device: sizes the launch */,

@@ -111,7 +111,7 @@ static WaveKernelFn<R, MM> pick_geometry(const GtopEvalPlan &p, int B, bool coll
   return pick_body<R, WIDE, 6, 1, 3, MM, false>(colli, dyn);
 }
 
-// The moving-obstacle bodies (MM = GtopMoving<...>; fp64): one sample at a time on the two-wavefront budget, with and without the
+// The moving-obstacle bodies (MM = GtopMoving<...>, or GtopMovingPoly<...> for a polynomial box list; fp64): one sample at a time on the two-wavefront budget, with and without the
 // velocity / acceleration block, for ten lanes per segment (up to 6 segments), five lanes per segment with one
 // trajectory (up to 12) or — plain evaluations — two (up to 6 each), and the chunked body past 12 segments.  Three
 // lanes or one lane per segment and two wavefronts per trajectory have no such body: nullptr (gtop_eval_plan_moving
@@ -139,6 +139,7 @@ constexpr int kMaxGroupsPerLaunch = 1 << 25;
 
 template <typename MM> struct MovingBase { using type = MM; };
 template <typename Base> struct MovingBase<GtopMoving<Base>> { using type = Base; };
+template <typename Base> struct MovingBase<GtopMovingPoly<Base>> { using type = Base; };
 
 // the collision term is in force (:346), as launch_wave decides it
 template <typename R> static bool has_collision_term(const GtopKernelArgs<R> &args) {
@@ -220,9 +221,10 @@ hipError_t GTOP_LAUNCHER(gtop_launch_eval)(const GtopKernelArgs<R> &args, const 
   return launch_wave<R, GtopModeOf<GtopNoMma>>(args, mode_args(GtopNoMma{}), plan, dyn, stream);
 }
 
-template <typename Base>
-static GtopMoving<Base> moving_kernel_args(const Base &st, const GtopMovingArgs &mov) {
-  GtopMoving<Base> mm;
+// (Moving: GtopMoving, or GtopMovingPoly for a polynomial list — mov.poly, a launch argument: the bodies differ)
+template <template <typename> class Moving = GtopMoving, typename Base>
+static Moving<Base> moving_kernel_args(const Base &st, const GtopMovingArgs &mov) {
+  Moving<Base> mm;
   static_cast<Base &>(mm) = st;
   mm.mk = GtopMovK{mov.rows, mov.t0, mov.nbox, mov.t0_stride};
   return mm;
@@ -231,6 +233,8 @@ hipError_t GTOP_LAUNCHER(gtop_launch_eval_moving)(const GtopKernelArgs<double> &
                                                   const GtopMovingArgs &mov, hipStream_t stream) {
   if (!mov.rows || mov.nbox < 1 || mov.nbox > GTOP_MOVING_MAX_BOXES) return hipErrorInvalidValue;
   if (kReferenceObject && plan.consistent && has_collision_term(args)) return gtop_launch_eval_moving_consistent(args, plan, dyn, mov, stream);
+  if (mov.poly)
+    return launch_wave<double, GtopModeOf<GtopMovingPoly<GtopNoMma>>>(args, mode_args(moving_kernel_args<GtopMovingPoly>(GtopNoMma{}, mov)), plan, dyn, stream);
   return launch_wave<double, GtopModeOf<GtopMoving<GtopNoMma>>>(args, mode_args(moving_kernel_args(GtopNoMma{}, mov)), plan, dyn, stream);
 }
 hipError_t GTOP_LAUNCHER(gtop_launch_eval_mma_moving)(const GtopKernelArgs<double> &args, const GtopMmaState &st,
@@ -239,6 +243,8 @@ hipError_t GTOP_LAUNCHER(gtop_launch_eval_mma_moving)(const GtopKernelArgs<doubl
   if (!mov.rows || mov.nbox < 1 || mov.nbox > GTOP_MOVING_MAX_BOXES) return hipErrorInvalidValue;
   if (plan.nt != 1) return hipErrorInvalidValue;
   if (kReferenceObject && plan.consistent && has_collision_term(args)) return gtop_launch_eval_mma_moving_consistent(args, st, plan, dyn, mov, stream);
+  if (mov.poly)
+    return launch_wave<double, GtopModeOf<GtopMovingPoly<GtopMmaState>>>(args, mode_args(moving_kernel_args<GtopMovingPoly>(st, mov)), plan, dyn, stream);
   return launch_wave<double, GtopModeOf<GtopMoving<GtopMmaState>>>(args, mode_args(moving_kernel_args(st, mov)), plan, dyn, stream);
 }
 

@@ -29,10 +29,27 @@
 #include "gtop_edt_lookup.h"
 #include "gtop_kernels.h"
 
+// This file is compiled TWICE (csrc/Makefile), as gtop_kernels.hip is: as it stands — the report kernel for
+// constant-velocity box lists, the selection kernels and the launchers the C-ABI layer calls — and with
+// -DGTOP_REPORT_POLY_TU into an object of its own that holds only the report kernel for POLYNOMIAL box lists
+// (gtop_set_moving_box_polynomials; rows of kBoxRowPoly = 24 doubles, gtop_edt_lookup.h) behind a launcher named
+// gtop_launch_traj_report_poly, which the first object's launcher forwards to.  Two objects so that the kernels of the
+// first keep their names and their code, and a constant-velocity launch stages the rows it always staged.
+#ifdef GTOP_REPORT_POLY_TU
+#define traj_report_kernel traj_report_poly_kernel
+#define gtop_launch_traj_report gtop_launch_traj_report_poly
+constexpr bool kReportPoly = true;
+#else
+constexpr bool kReportPoly = false;
+#endif
+
 namespace {
 
 constexpr int kReportWavesPerSimd = 4;   // traj_report_kernel's occupancy (120 VGPRs; tools/kernel_resources.py)
 constexpr int kValBoxChunk = 64;   // boxes staged in LDS per pass (4.5 KiB: 32 one-wavefront workgroups fit a CU)
+// The polynomial list's object: 32 rows of 24 per pass, the most the cost term takes: 6 KiB — 26 one-wavefront
+// workgroups of LDS per CU, where the kernel's 120 VGPRs admit 16.
+constexpr int kValBoxChunkPoly = 32;
 
 // first and second derivative of sum_j c[j] t^j.  Evaluation order (the quantity is fixed by the interface, the order
 // is this kernel's): the terms from the highest power down, as poly_eval sums the value, each term (j c_j) * t^(j-1)
@@ -63,14 +80,20 @@ __device__ __forceinline__ double wave_max(double v) {
 
 // boxes b0 .. b0 + nb - 1 into LDS as rows of p0, vel, scale, by the whole workgroup.  (With one wavefront per workgroup
 // the barriers order that wavefront's own LDS reads and writes and nothing else.)
-__device__ __forceinline__ void stage_boxes(double (*bx)[9], const double *__restrict__ box_p0,
+// POLY: box_p0 is the list's [nbox][kBoxRowPoly] rows, copied as they are.
+template <bool POLY, int ROW>
+__device__ __forceinline__ void stage_boxes(double (*bx)[ROW], const double *__restrict__ box_p0,
                                             const double *__restrict__ box_vel, const double *__restrict__ box_scale,
                                             int b0, int nb, int tid, int nthreads) {
   __syncthreads();
-  for (int q = tid; q < nb * 9; q += nthreads) {
-    const int bb = q / 9, f = q - 9 * bb, k = f % 3;
-    const size_t e = 3 * (size_t)(b0 + bb) + k;
-    bx[bb][f] = f < 3 ? box_p0[e] : (f < 6 ? box_vel[e] : box_scale[e]);
+  if constexpr (POLY) {
+    for (int q = tid; q < nb * ROW; q += nthreads) (&bx[0][0])[q] = box_p0[(size_t)b0 * ROW + q];
+  } else {
+    for (int q = tid; q < nb * 9; q += nthreads) {
+      const int bb = q / 9, f = q - 9 * bb, k = f % 3;
+      const size_t e = 3 * (size_t)(b0 + bb) + k;
+      bx[bb][f] = f < 3 ? box_p0[e] : (f < 6 ? box_vel[e] : box_scale[e]);
+    }
   }
   __syncthreads();
 }
@@ -100,7 +123,9 @@ traj_report_kernel(const GtopGrid g, const double *__restrict__ rec, int nbox, c
                    const double *__restrict__ coeff, const double *__restrict__ T, int t_stride, double dt_sample,
                    const double *__restrict__ t0, int t0_stride, double margin,
                    double *__restrict__ report /*[B][GTOP_TRAJ_REPORT]*/) {
-  __shared__ double bx[kValBoxChunk][9];   // p0, vel, scale
+  constexpr bool POLY = kReportPoly;
+  constexpr int kChunk = POLY ? kValBoxChunkPoly : kValBoxChunk, kRow = POLY ? kBoxRowPoly : kBoxRowConstVel;
+  __shared__ double bx[kChunk][kRow];   // p0, vel, scale; POLY: the list's rows
   __shared__ ReportPartial part[W];
   const int b = blockIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   if (b >= B) return;
@@ -112,7 +137,7 @@ traj_report_kernel(const GtopGrid g, const double *__restrict__ rec, int nbox, c
   const double start = (use_boxes && t0) ? t0[(size_t)b * t0_stride] : 0.0;
 
   // the one chunk of boxes nearly every list is: staged once
-  if (use_boxes) stage_boxes(bx, box_p0, box_vel, box_scale, 0, min(kValBoxChunk, nbox), threadIdx.x, 64 * W);
+  if (use_boxes) stage_boxes<POLY>(bx, box_p0, box_vel, box_scale, 0, min(kChunk, nbox), threadIdx.x, 64 * W);
 
   double dmin = INFINITY, dmin_t = 0.0, below_t = -1.0;
   int dmin_i = 0x7fffffff, below_i = 0x7fffffff, n_below = 0, n_out = 0;
@@ -155,14 +180,14 @@ traj_report_kernel(const GtopGrid g, const double *__restrict__ rec, int nbox, c
     double diff[3], values[2][2][2];
     gtop_edt_corners(g, rec, p, idx, diff, values);   // (a dead lane looks p = 0 up: clamped indices, memory-safe)
     double vmax = gtop_edt_vmax(values);
-    for (int b0 = 0; b0 < nbox; b0 += kValBoxChunk) {
-      const int nb = min(kValBoxChunk, nbox - b0);
+    for (int b0 = 0; b0 < nbox; b0 += kChunk) {
+      const int nb = min(kChunk, nbox - b0);
       if constexpr (W == 1)
-        if (nbox > kValBoxChunk) stage_boxes(bx, box_p0, box_vel, box_scale, b0, nb, lane, 64);   // wave-uniform
+        if (nbox > kChunk) stage_boxes<POLY>(bx, box_p0, box_vel, box_scale, b0, nb, lane, 64);   // wave-uniform
       if (dyn) {
         for (int q = 0; q < nb; ++q) {
           double bmin[3], bmax[3];
-          gtop_edt_box_faces(bx[q], tau, bmin, bmax);
+          gtop_edt_box_faces_of<POLY>(bx[q], tau, bmin, bmax);
           gtop_edt_box_min(g, bmin, bmax, idx, values, vmax);
         }
       }
@@ -240,6 +265,7 @@ traj_report_kernel(const GtopGrid g, const double *__restrict__ rec, int nbox, c
   }
 }
 
+#ifndef GTOP_REPORT_POLY_TU   // (the selection: the first object's alone)
 // ---- selection ----
 struct SelLimits {
   double max_vel, max_acc;
@@ -321,9 +347,13 @@ select_finish_kernel(int nparts, const SelPartial *__restrict__ part, int *__res
   }
 }
 
+#endif  // GTOP_REPORT_POLY_TU
+
 }  // namespace
 
+#ifndef GTOP_REPORT_POLY_TU
 static_assert(sizeof(SelPartial) == GTOP_SELECT_PARTIAL_BYTES, "the context sizes the selection workspace by this");
+#endif
 
 hipError_t gtop_launch_traj_report(const GtopGrid &g, const double *rec, int nbox, const double *box_p0,
                                    const double *box_vel, const double *box_scale, int B, int m, const double *coeff,
@@ -336,7 +366,12 @@ hipError_t gtop_launch_traj_report(const GtopGrid &g, const double *rec, int nbo
   // wavefronts only queue behind the resident ones, and each pays the 64 W dependent additions per chunk that carry
   // its sample time; see the kernel's comment
   const long long resident = (long long)kReportWavesPerSimd * (simds > 0 ? simds : 1);
-  const int W = nbox > kValBoxChunk ? 1 : (4LL * B <= resident ? 4 : (2LL * B <= resident ? 2 : 1));
+#ifndef GTOP_REPORT_POLY_TU
+  if (nbox > 0 && !box_vel)   // a polynomial list (box_p0 = its rows): the other object's kernel
+    return gtop_launch_traj_report_poly(g, rec, nbox, box_p0, box_vel, box_scale, B, m, coeff, T, t_stride, dt_sample, t0,
+                                        t0_stride, margin, report, simds, stream);
+#endif
+  const int W = nbox > (kReportPoly ? kValBoxChunkPoly : kValBoxChunk) ? 1 : (4LL * B <= resident ? 4 : (2LL * B <= resident ? 2 : 1));
 #define GTOP_REPORT_LAUNCH(W_)                                                                                          \
   hipLaunchKernelGGL(traj_report_kernel<W_>, dim3(B), dim3(64 * W_), 0, stream, g, rec, nbox, box_p0, box_vel, box_scale, \
                      B, m, coeff, T, t_stride, dt_sample, t0, t0_stride, margin, report)
@@ -347,6 +382,7 @@ hipError_t gtop_launch_traj_report(const GtopGrid &g, const double *rec, int nbo
   return hipGetLastError();
 }
 
+#ifndef GTOP_REPORT_POLY_TU
 hipError_t gtop_launch_select_best(int B, const double *report, const double *cost, double max_vel, double max_acc,
                                    int per_axis, int allow_out_of_map, unsigned char *pass, int *best, void *workspace,
                                    hipStream_t stream) {
@@ -361,3 +397,4 @@ hipError_t gtop_launch_select_best(int B, const double *report, const double *co
   hipLaunchKernelGGL(select_finish_kernel, dim3(1), dim3(256), 0, stream, nblocks, part, best);
   return hipGetLastError();
 }
+#endif  // GTOP_REPORT_POLY_TU

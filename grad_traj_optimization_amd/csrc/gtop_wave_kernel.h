@@ -5,6 +5,7 @@
 #include <type_traits>
 
 #include "gtop_device_common.h"
+#include "gtop_edt_lookup.h"
 #include "gtop_kernels.h"
 
 namespace {
@@ -383,6 +384,11 @@ __device__ __forceinline__ double mov_skip_bound(double vmax) {
   // (vmax^2 underflows below 1e-154: such a value — never a voxel distance — lets every box through)
   return vmax < 1e-140 ? (vmax > 0.0 ? __builtin_huge_val() : 0.0) : (vmax * vmax) * 1.000000000000001;
 }
+// POLY: the list is gtop_set_moving_box_polynomials' — rows of kBoxRowPoly = 24 doubles (gtop_edt_lookup.h: 18
+// coefficients, 3 half extents, t1, t2), the centre by that header's clamp and Horner chain: per box and sample two
+// min/max and 15 fp64 fmas where the constant-velocity row costs 3, each with one SGPR operand (a coefficient) — a
+// template argument, so that the constant-velocity bodies are the code they were.
+template <bool POLY>
 __device__ __forceinline__ void mov_min_boxes(SdfTap<double> &tp, const GtopKernelArgs<double> &a, const IndexBox &box,
                                               const double (&p)[3], double tau, const GtopMovK &mk, bool in_map) {
   const bool live = in_map & (tau >= 0.0);
@@ -403,12 +409,21 @@ __device__ __forceinline__ void mov_min_boxes(SdfTap<double> &tp, const GtopKern
   const ConstRows rows = (ConstRows)(uintptr_t)mk.rows;
 #pragma unroll 1
   for (int b = 0; b < mk.nbox; ++b) {
-    const ConstRows r = rows + 9 * b;
+    const ConstRows r = rows + (POLY ? kBoxRowPoly : kBoxRowConstVel) * b;
     double d1[3][2];
+    [[maybe_unused]] double tc = tau;
+    if constexpr (POLY) tc = gtop_box_poly_time(r, tau);
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-      const double c = r[k] + r[3 + k] * tau;   // obj_predictor.h:57-66
-      const double bmax = c + r[6 + k], bmin = c - r[6 + k];
+      double c, h;
+      if constexpr (POLY) {
+        c = gtop_box_poly_centre(r, k, tc);   // obj_predictor.h:46-55
+        h = r[18 + k];
+      } else {
+        c = r[k] + r[3 + k] * tau;   // obj_predictor.h:57-66
+        h = r[6 + k];
+      }
+      const double bmax = c + h, bmin = c - h;
 #pragma unroll
       for (int o = 0; o < 2; ++o) d1[k][o] = fmax(fmax(bmin - pt[k][o], pt[k][o] - bmax), 0.0);
     }
@@ -720,8 +735,16 @@ struct GtopNoMma {};
 template <typename Base> struct GtopMoving : Base {
   GtopMovK mk;
 };
+// the same with a polynomial box list (gtop_set_moving_box_polynomials; mk.rows: rows of 24, mov_min_boxes<true>): a
+// type of its own, so that the constant-velocity bodies keep their template arguments and their names
+template <typename Base> struct GtopMovingPoly : Base {
+  GtopMovK mk;
+};
 template <typename MM> constexpr bool kIsMov = false;
 template <typename Base> constexpr bool kIsMov<GtopMoving<Base>> = true;
+template <typename Base> constexpr bool kIsMov<GtopMovingPoly<Base>> = true;
+template <typename MM> constexpr bool kIsMovPoly = false;
+template <typename Base> constexpr bool kIsMovPoly<GtopMovingPoly<Base>> = true;
 template <typename MM> constexpr bool kIsMma = std::is_base_of<GtopMmaState, MM>::value;
 // CONS, the consistent gradient (gtop_set_gradient_mode(GTOP_GRADIENT_CONSISTENT)): carried by MM as MOV is —
 // GtopConsistent<GtopNoMma>, GtopConsistent<GtopMmaState>, GtopConsistent<GtopMoving<...>>, an empty wrapper — so that
@@ -732,6 +755,7 @@ template <typename Base> struct GtopConsistent : Base {};
 template <typename MM> constexpr bool kIsCons = false;
 template <typename Base> constexpr bool kIsCons<GtopConsistent<Base>> = true;
 template <typename Base> constexpr bool kIsMov<GtopConsistent<Base>> = kIsMov<Base>;
+template <typename Base> constexpr bool kIsMovPoly<GtopConsistent<Base>> = kIsMovPoly<Base>;
 // DYN compiles in the velocity / acceleration penalties the reference has commented out
 // (src/grad_traj_optimizer.cpp:383-407, formulas :517-535; they sit inside the collision sample loop, so DYN needs
 // COLLI; the launcher picks DYN only for enable_dyn at step 2, as the block's own `step == 2` test would).
@@ -748,6 +772,10 @@ template <typename Base> constexpr bool kIsMov<GtopConsistent<Base>> = kIsMov<Ba
 // coordinates live on top of the one-sample body, which alone sits at 166-168 of 168)
 template <typename R, bool WIDE, typename MM, int SPL, int MINW, bool DYN, bool LONG>
 constexpr int gtop_wave_budget() {
+  // (the polynomial box list in the optimizer loop with DYN and the consistent gradient, five lanes per segment: the
+  // constant-velocity body of that combination fills all 256 VGPRs of the two-wavefront budget, and the clamped time
+  // on top of it spilled 8 to scratch — on the one-wavefront budget the allocator parks them in AGPRs instead)
+  if (kIsCons<MM> && kIsMovPoly<MM> && kIsMma<MM> && DYN && SPL == 6 && !LONG) return 1;
   return ((kIsMma<MM> && SPL == 6) || DYN || kIsMov<MM> || ((WIDE || LONG) && sizeof(R) == 8 && SPL >= 6) ||
           (sizeof(R) == 4 && SPL >= 6))   // (packed fp32 with the double coefficients of its exact positions: 190 VGPRs)
              ? 2
@@ -1321,7 +1349,7 @@ gtop_eval_wave_kernel(const R *__restrict__ arg_x, const R *__restrict__ arg_Df,
         const R vn = vns[c], ivn = ivns[c];
         R g3[3];
         if constexpr (MOV)   // the time-aware lookup: the 8 corners min'ed with the boxes at the sample's absolute time
-          mov_min_boxes(taps[c], a, ibox, pos_mov, mov_seg + (double)tt, st.mk, !outs[c]);
+          mov_min_boxes<kIsMovPoly<MM>>(taps[c], a, ibox, pos_mov, mov_seg + (double)tt, st.mk, !outs[c]);
         R dist = sdf_blend(taps[c], g3[0], g3[1], g3[2]);   // g3 per voxel, not per metre
         if constexpr (!kRareOut) {   // dist = -1 (sdf_map.cpp:187); grad := 0 below, through its weight f1
           dist = outs[c] ? (R)-1 : dist;

@@ -83,6 +83,8 @@ const char *gtop_last_error(const gtop_ctx *ctx);
  * trajectory report and selection, gtop_validate_trajectories_device /
  * gtop_select_best_device / gtop_validate_batch; 6: the gradient mode,
  * gtop_set_gradient_mode / gtop_get_gradient_mode / gtop_group_set_gradient_mode;
+ * 7: the polynomial box list, gtop_set_moving_box_polynomials /
+ * gtop_get_moving_box_kind / gtop_box_polynomial_centres;
  * nothing of an earlier version changed meaning). */
 int gtop_abi_version(void);
 
@@ -482,10 +484,60 @@ int gtop_edt_coarse_query_device(gtop_ctx *ctx, int N, const void *d_pos,
 int gtop_edt_coarse_query(gtop_ctx *ctx, int N, const double *pos, const double *time,
                           double *dist);
 
+/* ---- moving obstacles on polynomial predictions ------------------------
+ * The other form of the ONE box list a context holds: each box's centre is a
+ * quintic per axis on a validity interval — the reference's PolynomialPrediction
+ * (polys, t1, t2, evaluate(t); include/grad_traj_optimization/obj_predictor.h:26-55),
+ * the call distToBox carries in a comment above the constant-velocity one
+ * (src/edt_environment.cpp:28-29).  For a turning or braking obstacle, or a peer
+ * flying its own committed quintic segment.
+ *   coef:    nbox x 3 x 6, axis-major per box, ascending powers (polys[k](i))
+ *   t_range: nbox x 2 = {t1, t2} per box, or NULL = unbounded
+ *   scale:   nbox x 3, the extent, as for gtop_set_moving_boxes
+ * Box b at time tau, axis k (fp64; every consumer — the queries, the report, the
+ * cost — computes exactly this, bit for bit):
+ *   tc  = fmin(fmax(tau, t1[b]), t2[b])                    (no clamp without t_range)
+ *   c_k = fma(fma(fma(fma(fma(c5, tc, c4), tc, c3), tc, c2), tc, c1), tc, c0)
+ *   faces c_k +- 0.5 * scale_k; from there on as for a constant-velocity box
+ *   (distToBox, the skip of far boxes, the min with the static corner values).
+ * Outside its interval a box STANDS where its prediction ends (an extrapolated
+ * quintic leaves the map within a second, and a box that vanished would make the
+ * unknown look safe); +-inf bounds are allowed and clamp nothing on their side.
+ * The rule "tau < 0: static only" is taken on tau itself, before the clamp.
+ * gtop_set_moving_boxes and gtop_set_moving_box_polynomials each REPLACE whatever
+ * list was set before, of either kind; nbox = 0 clears the list under either call
+ * (the kind reads GTOP_BOXES_CONST_VEL then).  GTOP_ERR_INVALID at the call, the
+ * list in force unchanged: t1 > t2, a NaN bound, a non-finite coefficient, a
+ * negative or non-finite scale.  A list of more than GTOP_MOVING_COST_MAX_BOXES
+ * boxes is accepted: it serves the queries and the report, and an evaluation in
+ * moving mode refuses it (GTOP_ERR_INVALID there), exactly as a constant-velocity
+ * list of that length.
+ * Every limit of the moving-obstacle cost below holds for this form too: fp64 only,
+ * at most GTOP_MOVING_COST_MAX_BOXES boxes, not forwarded by gtop_group_*, the same
+ * launch-geometry refusals.
+ * Capture: the list's KIND selects the kernel, so it is a launch argument — a
+ * captured evaluation, optimizer run, query or report replays with the kind it was
+ * captured with, and changing the kind needs a re-capture (a replay across a change
+ * of kind would read rows of the other layout as its own; memory-safe, values
+ * meaningless).  Changing the VALUES within a kind is followed at replay for the
+ * evaluations and optimizer runs, as before: they read the one buffer that never
+ * moves.
+ * gtop_box_polynomial_centres: the same arithmetic on the host, no context and no
+ * device (like gtop_default_bounds) — centres is ntimes x nbox x 3; the same
+ * checks (GTOP_ERR_INVALID; NULL pointers too). */
+#define GTOP_BOXES_CONST_VEL 0
+#define GTOP_BOXES_POLYNOMIAL 1
+int gtop_set_moving_box_polynomials(gtop_ctx *ctx, int nbox, const double *coef,
+                                    const double *t_range, const double *scale);
+int gtop_get_moving_box_kind(const gtop_ctx *ctx, int *kind, int *nbox);
+int gtop_box_polynomial_centres(int nbox, const double *coef, const double *t_range,
+                                int ntimes, const double *times, double *centres);
+
 /* ---- moving-obstacle cost (not in the reference's callback) ---------- */
 /* Off (the default), every evaluation looks the collision samples up in the static
  * field, as the reference's callback does (src/grad_traj_optimizer.cpp:363).  On,
- * and with at least one box set (gtop_set_moving_boxes), the lookup of every
+ * and with at least one box set (gtop_set_moving_boxes, or
+ * gtop_set_moving_box_polynomials above), the lookup of every
  * collision sample is the time-aware one the queries above answer: for
  * trajectory b, segment s, sample i, with local time t and position exactly as
  * before (:353, :457-465),
