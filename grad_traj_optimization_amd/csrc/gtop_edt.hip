@@ -161,14 +161,16 @@ edt_query_kernel(const GtopGrid g, const double *__restrict__ field, const doubl
 
 }  // namespace
 
-hipError_t gtop_launch_edt_query(const GtopGrid &g, const double *field, const double *rec, int nbox, const double *box_p0,
-                                 const double *box_vel, const double *box_scale, int N, const double *pos,
-                                 const double *time, double *dist, double *grad, hipStream_t stream) {
+hipError_t gtop_launch_edt_query(const GtopGrid &g, const double *field, const double *rec, const GtopBoxList &boxes, int N,
+                                 const double *pos, const double *time, double *dist, double *grad, hipStream_t stream) {
   if (N <= 0) return hipSuccess;
 #ifndef GTOP_EDT_POLY_TU
-  if (!box_vel && nbox > 0)   // a polynomial list (box_p0 = its rows): the other object's kernels
-    return gtop_launch_edt_query_poly(g, field, rec, nbox, box_p0, box_vel, box_scale, N, pos, time, dist, grad, stream);
+  if (boxes.kind == GTOP_BOX_LIST_POLYNOMIAL && boxes.count > 0)   // the other object's kernels
+    return gtop_launch_edt_query_poly(g, field, rec, boxes, N, pos, time, dist, grad, stream);
 #endif
+  // (the kernels' own parameters: the polynomial object's read the rows through the first pointer and not the others)
+  const int nbox = boxes.count;
+  const double *box_p0 = kQueryPoly ? boxes.rows : boxes.p0, *box_vel = boxes.vel, *box_scale = boxes.scale;
   if (grad)
     hipLaunchKernelGGL(edt_query_kernel<false>, dim3((N + 255) / 256), dim3(256), 0, stream, g, field, rec, nbox, box_p0,
                        box_vel, box_scale, N, pos, time, dist, grad);

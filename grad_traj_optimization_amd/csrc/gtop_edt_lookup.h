@@ -71,14 +71,14 @@ __device__ __forceinline__ void gtop_edt_box_faces(const double *bx, double t, d
 
 // ---- the polynomial box list (gtop_set_moving_box_polynomials) ----
 // A box's centre is a quintic per axis on a validity interval (PolynomialPrediction, obj_predictor.h:26-55; the call
-// distToBox carries in a comment, edt_environment.cpp:28).  One row of kBoxRowPoly doubles per box, the same for the
+// distToBox carries in a comment, edt_environment.cpp:28).  One row of kBoxRowPoly doubles (gtop_kernels.h) per box, the same for the
 // queries, the report and the cost bodies:
 //   [6 k + i] coefficient of t^i on axis k (18);  [18 + k] half extent scale_k / 2 (3);  [21] t1;  [22] t2;  [23] pad
 // (no t_range: t1 = -inf, t2 = +inf, which clamp nothing).  The arithmetic is fixed by the interface (include/gtop.h):
 // the time clamped into [t1, t2], then Horner in explicit fp64 fmas.  These two functions are its ONE statement on the
 // device — P is whatever pointer the row is read through (LDS in the queries and the report, the constant address
 // space in the cost bodies) — so the three kernels get the same centre, bit for bit.
-constexpr int kBoxRowConstVel = 9, kBoxRowPoly = 24;
+constexpr int kBoxRowConstVel = 9;
 template <typename P> __device__ __forceinline__ double gtop_box_poly_time(P row, double tau) {
   return fmin(fmax(tau, row[21]), row[22]);
 }

@@ -14,7 +14,7 @@
 // reference's lower-envelope pass (fillESDF, :266-308) finds; on this data every quantity is an exact integer, so the
 // kernels take that minimum directly in int32 with an INF sentinel (see gtop_esdf.hip, whose whole-grid kernels this
 // file's full-window case hands over to).  Because the sweeps never look outside the window, the update IS the
-// whole-grid transform of the window taken alone: for a window of at least 12 x 12 x 3 voxels gtop_capi.cpp keeps its
+// whole-grid transform of the window taken alone: for a window of at least 12 x 12 x 3 voxels gtop_capi_field.cpp keeps its
 // occupancy as a compact grid beside the map's (window_reset_compact_kernel, window_mark_kernel), runs gtop_esdf.hip's
 // builder on it and writes the result back (window_scatter_kernel).  The plain kernels below — one lane per voxel of the window, lanes along z: the
 // nearest occupied voxel of the column by an outward walk, then two outward scans with the exact cut-off

@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "gtop.h"
+#include "gtop_devbuf.h"
 #include "gtop_guard.h"
 
 namespace {
@@ -68,16 +69,17 @@ struct Member {
   hipStream_t stream = nullptr;
   hipEvent_t done = nullptr;     // this member's slice (and its outgoing copies) is complete
   hipEvent_t ready = nullptr;    // everything enqueued so far that may still read its gathered buffers has run
-  double *pts = nullptr;         // obstacle points of the last map update
-  size_t pts_cap = 0;            // (doubles)
   int first = 0, count = 0;      // its slice of the batch
-  double *x = nullptr, *Df = nullptr, *T = nullptr, *cost = nullptr, *grad = nullptr;   // slice buffers, `per` rows
-  double *cost_all = nullptr, *grad_all = nullptr;                                      // gathered: n * per rows
-  double *lb = nullptr, *ub = nullptr;
-  int32_t *nev = nullptr, *code = nullptr;
-  // capacities (bytes) of the buffers above, in free_slices' order: a new problem reuses what is large enough, so a
-  // caller that walks through problems of different sizes (GradTrajBatch: one per segment count) does not reallocate
-  size_t cap[11] = {0};
+  // Device memory (`d`), the member's device current wherever it is touched.  Grow-only: a new problem reuses what is
+  // large enough, so a caller that walks through problems of different sizes (GradTrajBatch: one per segment count)
+  // does not reallocate.
+  struct Buffers {
+    GtopDevBuf<double> pts;                    // obstacle points of the last map update
+    GtopDevBuf<double> x, Df, T, cost, grad;   // slice buffers, `per` rows
+    GtopDevBuf<double> cost_all, grad_all;     // gathered: n * per rows
+    GtopDevBuf<double> lb, ub;
+    GtopDevBuf<int32_t> nev, code;
+  } d;
   ncclComm_t comm = nullptr;
 };
 
@@ -129,27 +131,6 @@ void note_exception(gtop_group *g, const char *what) noexcept {
       return gfail(g, rc_, std::string(#call) + " on device " + std::to_string((mb).device) + ": " + gtop_last_error((mb).ctx)); \
   } while (0)
 
-void free_slices(Member &mb) {
-  (void)hipSetDevice(mb.device);
-  for (void *p : {(void *)mb.x, (void *)mb.Df, (void *)mb.T, (void *)mb.cost, (void *)mb.grad, (void *)mb.cost_all,
-                  (void *)mb.grad_all, (void *)mb.lb, (void *)mb.ub, (void *)mb.nev, (void *)mb.code})
-    if (p) (void)hipFree(p);
-  mb.x = mb.Df = mb.T = mb.cost = mb.grad = mb.cost_all = mb.grad_all = mb.lb = mb.ub = nullptr;
-  mb.nev = mb.code = nullptr;
-  for (size_t &c : mb.cap) c = 0;
-}
-
-// grow-only device buffer (the member's device is current)
-template <typename P> hipError_t ensure(P *&p, size_t &cap, size_t bytes) {
-  if (bytes <= cap && p) return hipSuccess;
-  if (p) (void)hipFree(p);
-  p = nullptr;
-  cap = 0;
-  const hipError_t e = hipMalloc(reinterpret_cast<void **>(&p), bytes ? bytes : 8);
-  if (e == hipSuccess) cap = bytes ? bytes : 8;
-  return e;
-}
-
 // results of every slice to every member.  RCCL: one all-gather per member inside a group call (the slices are
 // padded to `per` rows, so the gathered layout [rank][per] IS the batch order).  Copies: each member sends its slice
 // to every member's gathered buffer on its own stream, then every stream waits for every sender.
@@ -160,9 +141,9 @@ int all_gather(gtop_group *g, bool grads) {
     ncclResult_t r = g->rccl.GroupStart();
     for (int i = 0; i < n && r == ncclSuccess; ++i) {
       Member &mb = g->mem[i];
-      r = g->rccl.AllGather(mb.cost, mb.cost_all, (size_t)g->per, ncclDouble, mb.comm, mb.stream);
+      r = g->rccl.AllGather(mb.d.cost.data(), mb.d.cost_all.data(), (size_t)g->per, ncclDouble, mb.comm, mb.stream);
       if (r == ncclSuccess && grads)
-        r = g->rccl.AllGather(mb.grad, mb.grad_all, (size_t)g->per * nvar, ncclDouble, mb.comm, mb.stream);
+        r = g->rccl.AllGather(mb.d.grad.data(), mb.d.grad_all.data(), (size_t)g->per * nvar, ncclDouble, mb.comm, mb.stream);
     }
     const ncclResult_t r2 = g->rccl.GroupEnd();
     if (r != ncclSuccess || r2 != ncclSuccess)
@@ -182,10 +163,10 @@ int all_gather(gtop_group *g, bool grads) {
       if (j != i) GHIP(g, hipStreamWaitEvent(src.stream, g->mem[j].ready, 0));
     for (int j = 0; j < n; ++j) {
       Member &dst = g->mem[j];
-      GHIP(g, hipMemcpyPeerAsync(dst.cost_all + src.first, dst.device, src.cost, src.device,
+      GHIP(g, hipMemcpyPeerAsync(dst.d.cost_all.data() + src.first, dst.device, src.d.cost.data(), src.device,
                                  (size_t)src.count * sizeof(double), src.stream));
       if (grads)
-        GHIP(g, hipMemcpyPeerAsync(dst.grad_all + (size_t)src.first * nvar, dst.device, src.grad, src.device,
+        GHIP(g, hipMemcpyPeerAsync(dst.d.grad_all.data() + (size_t)src.first * nvar, dst.device, src.d.grad.data(), src.device,
                                    (size_t)src.count * nvar * sizeof(double), src.stream));
     }
     GHIP(g, hipEventRecord(src.done, src.stream));
@@ -293,8 +274,8 @@ int gtop_group_destroy(gtop_group *g) try {
   for (Member &mb : g->mem) {
     if (!mb.ctx) continue;   // (a member whose creation failed: its device ordinal may not even exist)
     if (mb.comm && g->rccl.CommDestroy) (void)g->rccl.CommDestroy(mb.comm);
-    free_slices(mb);
-    if (mb.pts) (void)hipFree(mb.pts);
+    (void)hipSetDevice(mb.device);
+    mb.d = Member::Buffers();   // freed with their device current
     if (mb.done) (void)hipEventDestroy(mb.done);
     if (mb.ready) (void)hipEventDestroy(mb.ready);
     if (mb.stream) (void)hipStreamDestroy(mb.stream);
@@ -344,15 +325,9 @@ int gtop_group_update_sdf_map(gtop_group *g, const double *pts, int npts) try {
   const size_t need = (size_t)npts * 3;
   for (Member &mb : g->mem) {
     GHIP(g, hipSetDevice(mb.device));
-    if (need > mb.pts_cap) {
-      if (mb.pts) GHIP(g, hipFree(mb.pts));
-      mb.pts = nullptr;
-      mb.pts_cap = 0;
-      GHIP(g, hipMalloc(reinterpret_cast<void **>(&mb.pts), need * sizeof(double)));
-      mb.pts_cap = need;
-    }
-    if (need) GHIP(g, hipMemcpyAsync(mb.pts, pts, need * sizeof(double), hipMemcpyHostToDevice, mb.stream));
-    GCTX(g, mb, gtop_update_sdf_map_device(mb.ctx, mb.pts, npts, mb.stream));
+    if (need) GHIP(g, mb.d.pts.reserve(need));
+    if (need) GHIP(g, hipMemcpyAsync(mb.d.pts.data(), pts, need * sizeof(double), hipMemcpyHostToDevice, mb.stream));
+    GCTX(g, mb, gtop_update_sdf_map_device(mb.ctx, mb.d.pts.data(), npts, mb.stream));
   }
   return sync_all(g);
 } GTOP_CATCH_STATUS(g)
@@ -365,15 +340,9 @@ int gtop_group_update_sdf_map_window(gtop_group *g, const double min_pos[3], con
   const size_t need = (size_t)npts * 3;
   for (Member &mb : g->mem) {
     GHIP(g, hipSetDevice(mb.device));
-    if (need > mb.pts_cap) {
-      if (mb.pts) GHIP(g, hipFree(mb.pts));
-      mb.pts = nullptr;
-      mb.pts_cap = 0;
-      GHIP(g, hipMalloc(reinterpret_cast<void **>(&mb.pts), need * sizeof(double)));
-      mb.pts_cap = need;
-    }
-    if (need) GHIP(g, hipMemcpyAsync(mb.pts, pts, need * sizeof(double), hipMemcpyHostToDevice, mb.stream));
-    GCTX(g, mb, gtop_update_sdf_map_window_device(mb.ctx, min_pos, max_pos, mb.pts, npts, mb.stream));
+    if (need) GHIP(g, mb.d.pts.reserve(need));
+    if (need) GHIP(g, hipMemcpyAsync(mb.d.pts.data(), pts, need * sizeof(double), hipMemcpyHostToDevice, mb.stream));
+    GCTX(g, mb, gtop_update_sdf_map_window_device(mb.ctx, min_pos, max_pos, mb.d.pts.data(), npts, mb.stream));
   }
   return sync_all(g);
 } GTOP_CATCH_STATUS(g)
@@ -403,24 +372,24 @@ int gtop_group_set_problem(gtop_group *g, int B, int m, const double *segment_ti
     mb.count = std::min(B, mb.first + per) - mb.first;
     GHIP(g, hipSetDevice(mb.device));
     // slices padded to `per` rows (RCCL's all-gather sends equal counts); the padding is never read as a result
-    GHIP(g, ensure(mb.x, mb.cap[0], (size_t)per * nvar * sizeof(double)));
-    GHIP(g, ensure(mb.Df, mb.cap[1], (size_t)per * 18 * sizeof(double)));
-    GHIP(g, ensure(mb.T, mb.cap[2], (time_stride ? (size_t)per * m : (size_t)m) * sizeof(double)));
-    GHIP(g, ensure(mb.cost, mb.cap[3], (size_t)per * sizeof(double)));
-    GHIP(g, ensure(mb.grad, mb.cap[4], (size_t)per * nvar * sizeof(double)));
-    GHIP(g, ensure(mb.cost_all, mb.cap[5], (size_t)n * per * sizeof(double)));
-    GHIP(g, ensure(mb.grad_all, mb.cap[6], (size_t)n * per * nvar * sizeof(double)));
-    GHIP(g, hipMemsetAsync(mb.cost, 0, (size_t)per * sizeof(double), mb.stream));
-    GHIP(g, hipMemsetAsync(mb.grad, 0, (size_t)per * nvar * sizeof(double), mb.stream));
+    GHIP(g, mb.d.x.reserve((size_t)per * nvar));
+    GHIP(g, mb.d.Df.reserve((size_t)per * 18));
+    GHIP(g, mb.d.T.reserve(time_stride ? (size_t)per * m : (size_t)m));
+    GHIP(g, mb.d.cost.reserve((size_t)per));
+    GHIP(g, mb.d.grad.reserve((size_t)per * nvar));
+    GHIP(g, mb.d.cost_all.reserve((size_t)n * per));
+    GHIP(g, mb.d.grad_all.reserve((size_t)n * per * nvar));
+    GHIP(g, hipMemsetAsync(mb.d.cost.data(), 0, (size_t)per * sizeof(double), mb.stream));
+    GHIP(g, hipMemsetAsync(mb.d.grad.data(), 0, (size_t)per * nvar * sizeof(double), mb.stream));
     if (mb.count > 0) {
-      GHIP(g, hipMemcpyAsync(mb.Df, Df + (size_t)mb.first * 18, (size_t)mb.count * 18 * sizeof(double),
+      GHIP(g, hipMemcpyAsync(mb.d.Df.data(), Df + (size_t)mb.first * 18, (size_t)mb.count * 18 * sizeof(double),
                              hipMemcpyHostToDevice, mb.stream));
       if (time_stride)
-        GHIP(g, hipMemcpyAsync(mb.T, segment_time + (size_t)mb.first * m, (size_t)mb.count * m * sizeof(double),
+        GHIP(g, hipMemcpyAsync(mb.d.T.data(), segment_time + (size_t)mb.first * m, (size_t)mb.count * m * sizeof(double),
                                hipMemcpyHostToDevice, mb.stream));
     }
     if (!time_stride)
-      GHIP(g, hipMemcpyAsync(mb.T, segment_time, (size_t)m * sizeof(double), hipMemcpyHostToDevice, mb.stream));
+      GHIP(g, hipMemcpyAsync(mb.d.T.data(), segment_time, (size_t)m * sizeof(double), hipMemcpyHostToDevice, mb.stream));
   }
   int rc = sync_all(g);
   if (rc) return rc;
@@ -440,8 +409,8 @@ int gtop_group_shard(const gtop_group *g, int i, int *first, int *count) {
 static int launch_slices(gtop_group *g) {
   for (Member &mb : g->mem) {
     if (mb.count == 0) continue;
-    GCTX(g, mb, gtop_eval_device(mb.ctx, GTOP_F64, mb.count, g->m, mb.x, mb.Df, mb.T, g->t_stride, mb.cost, mb.grad,
-                                 mb.stream));
+    GCTX(g, mb, gtop_eval_device(mb.ctx, GTOP_F64, mb.count, g->m, mb.d.x.data(), mb.d.Df.data(), mb.d.T.data(), g->t_stride,
+                                 mb.d.cost.data(), mb.d.grad.data(), mb.stream));
   }
   return GTOP_OK;
 }
@@ -454,7 +423,7 @@ int gtop_group_eval_batch(gtop_group *g, int B, const double *x, double *cost, d
   for (Member &mb : g->mem) {
     if (mb.count == 0) continue;
     GHIP(g, hipSetDevice(mb.device));
-    GHIP(g, hipMemcpyAsync(mb.x, x + (size_t)mb.first * nvar, (size_t)mb.count * nvar * sizeof(double),
+    GHIP(g, hipMemcpyAsync(mb.d.x.data(), x + (size_t)mb.first * nvar, (size_t)mb.count * nvar * sizeof(double),
                            hipMemcpyHostToDevice, mb.stream));
   }
   int rc = launch_slices(g);
@@ -462,8 +431,8 @@ int gtop_group_eval_batch(gtop_group *g, int B, const double *x, double *cost, d
   for (Member &mb : g->mem) {
     if (mb.count == 0) continue;
     GHIP(g, hipSetDevice(mb.device));
-    GHIP(g, hipMemcpyAsync(cost + mb.first, mb.cost, (size_t)mb.count * sizeof(double), hipMemcpyDeviceToHost, mb.stream));
-    GHIP(g, hipMemcpyAsync(grad + (size_t)mb.first * nvar, mb.grad, (size_t)mb.count * nvar * sizeof(double),
+    GHIP(g, hipMemcpyAsync(cost + mb.first, mb.d.cost.data(), (size_t)mb.count * sizeof(double), hipMemcpyDeviceToHost, mb.stream));
+    GHIP(g, hipMemcpyAsync(grad + (size_t)mb.first * nvar, mb.d.grad.data(), (size_t)mb.count * nvar * sizeof(double),
                            hipMemcpyDeviceToHost, mb.stream));
   }
   g->x_resident = true;
@@ -478,7 +447,7 @@ int gtop_group_upload_x(gtop_group *g, int B, const double *x) try {
   for (Member &mb : g->mem) {
     if (mb.count == 0) continue;
     GHIP(g, hipSetDevice(mb.device));
-    GHIP(g, hipMemcpyAsync(mb.x, x + (size_t)mb.first * nvar, (size_t)mb.count * nvar * sizeof(double),
+    GHIP(g, hipMemcpyAsync(mb.d.x.data(), x + (size_t)mb.first * nvar, (size_t)mb.count * nvar * sizeof(double),
                            hipMemcpyHostToDevice, mb.stream));
   }
   g->x_resident = true;
@@ -502,9 +471,9 @@ int gtop_group_read_gathered(gtop_group *g, int member, double *cost, double *gr
   Member &mb = g->mem[member];
   const size_t nvar = 9 * (size_t)(g->m - 1);
   GHIP(g, hipSetDevice(mb.device));
-  if (cost) GHIP(g, hipMemcpyAsync(cost, mb.cost_all, (size_t)g->B * sizeof(double), hipMemcpyDeviceToHost, mb.stream));
+  if (cost) GHIP(g, hipMemcpyAsync(cost, mb.d.cost_all.data(), (size_t)g->B * sizeof(double), hipMemcpyDeviceToHost, mb.stream));
   if (grad)
-    GHIP(g, hipMemcpyAsync(grad, mb.grad_all, (size_t)g->B * nvar * sizeof(double), hipMemcpyDeviceToHost, mb.stream));
+    GHIP(g, hipMemcpyAsync(grad, mb.d.grad_all.data(), (size_t)g->B * nvar * sizeof(double), hipMemcpyDeviceToHost, mb.stream));
   GHIP(g, hipStreamSynchronize(mb.stream));
   return GTOP_OK;
 } GTOP_CATCH_STATUS(g)
@@ -513,11 +482,11 @@ int gtop_group_device_buffers(gtop_group *g, int member, void **d_x, void **d_co
                               void **d_grad_all, void **hip_stream) try {
   if (!g || !g->have_problem || member < 0 || member >= (int)g->mem.size()) return GTOP_ERR_INVALID;
   Member &mb = g->mem[member];
-  if (d_x) *d_x = mb.x;
-  if (d_cost) *d_cost = mb.cost;
-  if (d_grad) *d_grad = mb.grad;
-  if (d_cost_all) *d_cost_all = mb.cost_all;
-  if (d_grad_all) *d_grad_all = mb.grad_all;
+  if (d_x) *d_x = mb.d.x.data();
+  if (d_cost) *d_cost = mb.d.cost.data();
+  if (d_grad) *d_grad = mb.d.grad.data();
+  if (d_cost_all) *d_cost_all = mb.d.cost_all.data();
+  if (d_grad_all) *d_grad_all = mb.d.grad_all.data();
   if (hip_stream) *hip_stream = mb.stream;
   g->x_resident = true;   // the caller writes x where it lives
   return GTOP_OK;
@@ -533,30 +502,31 @@ int gtop_group_optimize_batch_ex(gtop_group *g, int B, double *x, const double *
     if (mb.count == 0) continue;
     GHIP(g, hipSetDevice(mb.device));
     const size_t bytes = (size_t)mb.count * nvar * sizeof(double);
-    GHIP(g, ensure(mb.lb, mb.cap[7], (size_t)g->per * nvar * sizeof(double)));
-    GHIP(g, ensure(mb.ub, mb.cap[8], (size_t)g->per * nvar * sizeof(double)));
-    GHIP(g, ensure(mb.nev, mb.cap[9], (size_t)g->per * sizeof(int32_t)));
-    GHIP(g, ensure(mb.code, mb.cap[10], (size_t)g->per * sizeof(int32_t)));
-    GHIP(g, hipMemcpyAsync(mb.x, x + (size_t)mb.first * nvar, bytes, hipMemcpyHostToDevice, mb.stream));
-    GHIP(g, hipMemcpyAsync(mb.lb, lb + (size_t)mb.first * nvar, bytes, hipMemcpyHostToDevice, mb.stream));
-    GHIP(g, hipMemcpyAsync(mb.ub, ub + (size_t)mb.first * nvar, bytes, hipMemcpyHostToDevice, mb.stream));
+    GHIP(g, mb.d.lb.reserve((size_t)g->per * nvar));
+    GHIP(g, mb.d.ub.reserve((size_t)g->per * nvar));
+    GHIP(g, mb.d.nev.reserve((size_t)g->per));
+    GHIP(g, mb.d.code.reserve((size_t)g->per));
+    GHIP(g, hipMemcpyAsync(mb.d.x.data(), x + (size_t)mb.first * nvar, bytes, hipMemcpyHostToDevice, mb.stream));
+    GHIP(g, hipMemcpyAsync(mb.d.lb.data(), lb + (size_t)mb.first * nvar, bytes, hipMemcpyHostToDevice, mb.stream));
+    GHIP(g, hipMemcpyAsync(mb.d.ub.data(), ub + (size_t)mb.first * nvar, bytes, hipMemcpyHostToDevice, mb.stream));
   }
   for (Member &mb : g->mem) {   // every device's whole optimisation is one launch; none waits for another
     if (mb.count == 0) continue;
-    GCTX(g, mb, gtop_optimize_device_ex(mb.ctx, mb.count, g->m, mb.x, mb.Df, mb.T, g->t_stride, mb.lb, mb.ub, stop,
-                                        mb.cost, mb.nev, mb.code, mb.stream));
+    GCTX(g, mb, gtop_optimize_device_ex(mb.ctx, mb.count, g->m, mb.d.x.data(), mb.d.Df.data(), mb.d.T.data(), g->t_stride,
+                                        mb.d.lb.data(), mb.d.ub.data(), stop, mb.d.cost.data(), mb.d.nev.data(),
+                                        mb.d.code.data(), mb.stream));
   }
   for (Member &mb : g->mem) {
     if (mb.count == 0) continue;
     GHIP(g, hipSetDevice(mb.device));
-    GHIP(g, hipMemcpyAsync(x + (size_t)mb.first * nvar, mb.x, (size_t)mb.count * nvar * sizeof(double),
+    GHIP(g, hipMemcpyAsync(x + (size_t)mb.first * nvar, mb.d.x.data(), (size_t)mb.count * nvar * sizeof(double),
                            hipMemcpyDeviceToHost, mb.stream));
     if (min_cost)
-      GHIP(g, hipMemcpyAsync(min_cost + mb.first, mb.cost, (size_t)mb.count * sizeof(double), hipMemcpyDeviceToHost, mb.stream));
+      GHIP(g, hipMemcpyAsync(min_cost + mb.first, mb.d.cost.data(), (size_t)mb.count * sizeof(double), hipMemcpyDeviceToHost, mb.stream));
     if (nevals)
-      GHIP(g, hipMemcpyAsync(nevals + mb.first, mb.nev, (size_t)mb.count * sizeof(int32_t), hipMemcpyDeviceToHost, mb.stream));
+      GHIP(g, hipMemcpyAsync(nevals + mb.first, mb.d.nev.data(), (size_t)mb.count * sizeof(int32_t), hipMemcpyDeviceToHost, mb.stream));
     if (code)
-      GHIP(g, hipMemcpyAsync(code + mb.first, mb.code, (size_t)mb.count * sizeof(int32_t), hipMemcpyDeviceToHost, mb.stream));
+      GHIP(g, hipMemcpyAsync(code + mb.first, mb.d.code.data(), (size_t)mb.count * sizeof(int32_t), hipMemcpyDeviceToHost, mb.stream));
   }
   g->x_resident = true;
   return sync_all(g);

@@ -1,4 +1,4 @@
-// gtop_kernels.h — launch interface between the C-ABI layer (gtop_capi.cpp)
+// gtop_kernels.h — launch interface between the C-ABI layer (gtop_capi*.cpp)
 // and the gfx950 kernels (the launchers of gtop_kernels.hip, gtop_esdf.hip, ...); the launch rule and its
 // GtopEvalPlan are gtop_launch_rule.h's, included here.  Internal; the public boundary is include/gtop.h.
 #ifndef GTOP_KERNELS_H_
@@ -73,7 +73,7 @@ hipError_t gtop_launch_eval_consistent(const GtopKernelArgs<R> &args, const Gtop
 // ---- the moving-obstacle term (gtop_set_moving_cost): the lookup of every collision sample becomes
 // evaluateEDTWithGrad(pos, tau), the 8 corner values min'ed with the distance to the nearest box at the sample's
 // absolute time (fp64 bodies only) ----
-#define GTOP_MOVING_MAX_BOXES 32   // = GTOP_MOVING_COST_MAX_BOXES of include/gtop.h (checked in gtop_capi.cpp)
+#define GTOP_MOVING_MAX_BOXES 32   // = GTOP_MOVING_COST_MAX_BOXES of include/gtop.h (checked in gtop_capi_boxes.cpp)
 struct GtopMovingArgs {
   const double *rows;   // [nbox][9]: p0, vel, scale / 2 — wavefront-uniform, read through scalar loads
                         // (poly: [nbox][24], the rows of gtop_set_moving_box_polynomials, gtop_edt_lookup.h)
@@ -180,33 +180,35 @@ hipError_t gtop_launch_eval_trajectories(int B, int m, const double *coeff, cons
                                          hipStream_t stream);
 
 // ---- static field + moving boxes (gtop_edt.hip) -----------------------------
-// field: the z-fastest fp64 buffer (the coarse query's voxel values); rec: its corner records (the interpolating query)
-// The box list, here and in gtop_launch_traj_report: box_p0 / box_vel / box_scale, nbox x 3 each — or, with box_vel ==
-// NULL, a polynomial list (gtop_set_moving_box_polynomials): box_p0 holds its [nbox][24] rows (gtop_edt_lookup.h) and
-// box_scale is not read.
-hipError_t gtop_launch_edt_query(const GtopGrid &g, const double *field, const double *rec, int nbox, const double *box_p0,
-                                 const double *box_vel, const double *box_scale, int N, const double *pos,
-                                 const double *time, double *dist, double *grad, hipStream_t stream);
-// (the object gtop_edt.hip is compiled into with -DGTOP_EDT_POLY_TU; called by gtop_launch_edt_query only)
-hipError_t gtop_launch_edt_query_poly(const GtopGrid &g, const double *field, const double *rec, int nbox, const double *box_p0,
-                                 const double *box_vel, const double *box_scale, int N, const double *pos,
-                                 const double *time, double *dist, double *grad, hipStream_t stream);
+// The box list the query and the report take: one of two kinds, with the pointers of that kind (the other kind's stay
+// NULL); count 0 = no boxes, whatever the kind.
+constexpr int kBoxRowPoly = 24;   // doubles per row of a polynomial list: device code (gtop_edt_lookup.h) and host alike
+enum GtopBoxKind { GTOP_BOX_LIST_CONST_VEL = 0, GTOP_BOX_LIST_POLYNOMIAL = 1 };
+struct GtopBoxList {
+  GtopBoxKind kind;
+  int count;
+  const double *p0, *vel, *scale;   // constant velocity: count x 3 each
+  const double *rows;               // polynomial (gtop_set_moving_box_polynomials): [count][kBoxRowPoly], gtop_edt_lookup.h
+};
+// field: the z-fastest fp64 buffer (the coarse query's voxel values); rec: its corner records (the interpolating query);
+// grad NULL: the coarse query.  gtop_edt.hip is compiled into two objects: the second (-DGTOP_EDT_POLY_TU) holds the
+// kernels for polynomial lists behind the _poly launcher, which gtop_launch_edt_query forwards to on `kind` and nobody
+// else calls.
+using GtopEdtQueryLauncher = hipError_t(const GtopGrid &g, const double *field, const double *rec, const GtopBoxList &boxes,
+                                        int N, const double *pos, const double *time, double *dist, double *grad,
+                                        hipStream_t stream);
+GtopEdtQueryLauncher gtop_launch_edt_query, gtop_launch_edt_query_poly;
 
 // ---- trajectory report + selection (gtop_validate.hip), fp64 -----------------
 #define GTOP_TRAJ_REPORT 12   // = include/gtop.h
 // report[b] of the trajectories (coeff, T) as include/gtop.h lays it out: the getTraj samples looked up as
-// edt_query_kernel<false> looks (pos, tau) up, tau = t0[b * t0_stride] + eval_t (t0 NULL = 0) — with nbox = 0 static only
-hipError_t gtop_launch_traj_report(const GtopGrid &g, const double *rec, int nbox, const double *box_p0,
-                                   const double *box_vel, const double *box_scale, int B, int m, const double *coeff,
-                                   const double *T, int t_stride, double dt_sample, const double *t0, int t0_stride,
-                                   double margin, double *report, int simds /* of the device: sizes the launch */,
-                                   hipStream_t stream);
-// (the object gtop_validate.hip is compiled into with -DGTOP_REPORT_POLY_TU; called by gtop_launch_traj_report only)
-hipError_t gtop_launch_traj_report_poly(const GtopGrid &g, const double *rec, int nbox, const double *box_p0,
-                                   const double *box_vel, const double *box_scale, int B, int m, const double *coeff,
-                                   const double *T, int t_stride, double dt_sample, const double *t0, int t0_stride,
-                                   double margin, double *report, int simds /* of the device: sizes the launch */,
-                                   hipStream_t stream);
+// edt_query_kernel<false> looks (pos, tau) up, tau = t0[b * t0_stride] + eval_t (t0 NULL = 0) — with no boxes static only
+// (gtop_validate.hip's second object, -DGTOP_REPORT_POLY_TU, holds the _poly launcher: forwarded to on `kind` as above)
+using GtopTrajReportLauncher = hipError_t(const GtopGrid &g, const double *rec, const GtopBoxList &boxes, int B, int m,
+                                          const double *coeff, const double *T, int t_stride, double dt_sample,
+                                          const double *t0, int t0_stride, double margin, double *report,
+                                          int simds /* of the device: sizes the launch */, hipStream_t stream);
+GtopTrajReportLauncher gtop_launch_traj_report, gtop_launch_traj_report_poly;
 // pass[b] (may be NULL) and best[2] = {passing row of least cost (lowest index on a tie, -1 if none), passing rows};
 // two launches; workspace: GTOP_SELECT_PARTIALS x GTOP_SELECT_PARTIAL_BYTES bytes of device memory
 #define GTOP_SELECT_PARTIALS 256

@@ -355,10 +355,9 @@ select_finish_kernel(int nparts, const SelPartial *__restrict__ part, int *__res
 static_assert(sizeof(SelPartial) == GTOP_SELECT_PARTIAL_BYTES, "the context sizes the selection workspace by this");
 #endif
 
-hipError_t gtop_launch_traj_report(const GtopGrid &g, const double *rec, int nbox, const double *box_p0,
-                                   const double *box_vel, const double *box_scale, int B, int m, const double *coeff,
-                                   const double *T, int t_stride, double dt_sample, const double *t0, int t0_stride,
-                                   double margin, double *report, int simds, hipStream_t stream) {
+hipError_t gtop_launch_traj_report(const GtopGrid &g, const double *rec, const GtopBoxList &boxes, int B, int m,
+                                   const double *coeff, const double *T, int t_stride, double dt_sample, const double *t0,
+                                   int t0_stride, double margin, double *report, int simds, hipStream_t stream) {
   if (B <= 0) return hipSuccess;
   // wavefronts per trajectory: the most of 4, 2, 1 with which the whole launch is still resident at once — B W
   // wavefronts within the kernel's kReportWavesPerSimd on each of the device's SIMDs (`simds`, four per compute unit:
@@ -367,10 +366,13 @@ hipError_t gtop_launch_traj_report(const GtopGrid &g, const double *rec, int nbo
   // its sample time; see the kernel's comment
   const long long resident = (long long)kReportWavesPerSimd * (simds > 0 ? simds : 1);
 #ifndef GTOP_REPORT_POLY_TU
-  if (nbox > 0 && !box_vel)   // a polynomial list (box_p0 = its rows): the other object's kernel
-    return gtop_launch_traj_report_poly(g, rec, nbox, box_p0, box_vel, box_scale, B, m, coeff, T, t_stride, dt_sample, t0,
-                                        t0_stride, margin, report, simds, stream);
+  if (boxes.kind == GTOP_BOX_LIST_POLYNOMIAL && boxes.count > 0)   // the other object's kernel
+    return gtop_launch_traj_report_poly(g, rec, boxes, B, m, coeff, T, t_stride, dt_sample, t0, t0_stride, margin, report,
+                                        simds, stream);
 #endif
+  // (the kernel's own parameters: the polynomial object's reads the rows through the first pointer and not the others)
+  const int nbox = boxes.count;
+  const double *box_p0 = kReportPoly ? boxes.rows : boxes.p0, *box_vel = boxes.vel, *box_scale = boxes.scale;
   const int W = nbox > (kReportPoly ? kValBoxChunkPoly : kValBoxChunk) ? 1 : (4LL * B <= resident ? 4 : (2LL * B <= resident ? 2 : 1));
 #define GTOP_REPORT_LAUNCH(W_)                                                                                          \
   hipLaunchKernelGGL(traj_report_kernel<W_>, dim3(B), dim3(64 * W_), 0, stream, g, rec, nbox, box_p0, box_vel, box_scale, \

@@ -161,7 +161,7 @@ def test_z_sweep_covers_every_column(table):
 
 def test_workspace_is_monotone(table):
     """gtop_esdf_rows_ints never shrinks when an axis grows: the window path builds sub-grids in a workspace sized for
-    the whole grid (gtop_capi.cpp update_window_on_stream)."""
+    the whole grid (gtop_capi_field.cpp update_window_on_stream)."""
     grids = list(table)
     for a in grids:
         for b in grids:

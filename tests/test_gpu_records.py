@@ -1,8 +1,9 @@
 """The corner records (csrc/gtop_records.hip) densely: every cell of the map after every way of building
 them.  Every lookup of the library reads the records, a derived copy of the field with clamped border copies and two
 padding levels, maintained by five builder forms (whole map fp64, whole map both precisions two rows per lane, the two
-restricted to a voxel box, <double,float> and <float,float>) chosen by the context's history (gtop_capi.cpp: rec64_ok,
-rec32_ok, rec32_stale, fp32_in_use, fp32_wanted, the grow-only buffers).  The rest of the suite sees them only where a
+restricted to a voxel box, <double,float> and <float,float>) chosen by the context's history (GtopField in
+csrc/gtop_ctx.h and gtop_capi_field.cpp: the fp64 records current or not, the fp32 ones absent / stale / current, fp32 in
+use, fp32 wanted, the grow-only buffers).  The rest of the suite sees them only where a
 random batch happens to pass; here one probe row per cell (tests/records_probe.py; its soundness:
 tests/test_records_probe.py) reads every record, the border and padding ones included, after every step.
 
