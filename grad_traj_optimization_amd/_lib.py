@@ -110,6 +110,8 @@ def load_library():
         "gtop_set_paths": (C.c_int, [vp, C.c_int, C.c_int, dp, C.c_double, C.c_double, dp]),
         "gtop_setup_paths_device": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_double, C.c_double, vp, vp, vp, vp]),
         "gtop_get_problem": (C.c_int, [vp, dp, dp]),
+        "gtop_min_jerk_start_device": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp]),
+        "gtop_min_jerk_start": (C.c_int, [vp, C.c_int, dp]),
         "gtop_coefficients_device": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp]),
         "gtop_eval_trajectories_device": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_double, vp, vp]),
         "gtop_trajectory_stats": (C.c_int, [vp, C.c_int, dp, C.c_double, dp, dp]),
@@ -199,7 +201,7 @@ def load_library():
              "gtop_set_start_times_device": 4, "gtop_validate_trajectories_device": 5, "gtop_select_best_device": 5,
              "gtop_validate_batch": 5, "gtop_set_gradient_mode": 6, "gtop_get_gradient_mode": 6,
              "gtop_group_set_gradient_mode": 6, "gtop_set_moving_box_polynomials": 7, "gtop_get_moving_box_kind": 7,
-             "gtop_box_polynomial_centres": 7}
+             "gtop_box_polynomial_centres": 7, "gtop_min_jerk_start_device": 8, "gtop_min_jerk_start": 8}
     L.gtop_abi_version.restype = C.c_int
     abi = L.gtop_abi_version() if os.environ.get("GTOP_HIP_LIB") else max(since.values())
     for name, (res, args) in sig.items():
@@ -492,6 +494,34 @@ class GtopContext:
         Df = np.empty((self.B, 3, 6))
         self._chk(self._L.gtop_get_problem(self._h, _p(T), _p(Df)))
         return T, Df
+
+    def min_jerk_start(self, x):
+        """The minimum-jerk start point of the first B rows of the context's problem (include/gtop.h,
+        gtop_min_jerk_start): a NEW array (B, n) with the positions of x and, in the velocity and acceleration entries,
+        the minimiser of the smoothness term at those positions."""
+        out = _f64(x).copy()
+        assert out.ndim == 2 and out.shape[1] == 9 * (self.m - 1)
+        self._chk(self._L.gtop_min_jerk_start(self._h, out.shape[0], _p(out)))
+        return out
+
+    def min_jerk_start_device(self, x, Df, T, stream=None):
+        """The same IN PLACE on a torch fp64 CUDA tensor x (B, n), with Df (B, 18) and T (B, m) or (m,): overwrites
+        the velocity and acceleration entries of x; asynchronous, capturable.  Returns x."""
+        import torch
+        B, n = x.shape
+        m = n // 9 + 1
+        assert n == 9 * (m - 1) and Df.numel() == B * 18
+        stride = m if T.dim() == 2 else 0
+        assert T.numel() == (B * m if stride else m)
+        for t in (x, Df, T):
+            assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float64
+        if stream is None:
+            stream = torch.cuda.current_stream(x.device).cuda_stream
+        elif hasattr(stream, "cuda_stream"):
+            stream = stream.cuda_stream
+        self._chk(self._L.gtop_min_jerk_start_device(self._h, B, m, C.c_void_p(x.data_ptr()), C.c_void_p(Df.data_ptr()),
+                                                     C.c_void_p(T.data_ptr()), stride, C.c_void_p(stream)))
+        return x
 
     def trajectory_stats(self, x, dt_sample=0.01):
         """(coefficients (B, m, 18), stats (B, 9)) for the context's problem at free variables x."""

@@ -177,6 +177,10 @@ void GradTrajOptimizer::setupProblem(const std::vector<double> &path_flat, int n
   }
   if (!ctx_) return;
   last_status_ = gtop_set_problem(ctx_, 1, m_, segment_time_.data(), m_, df_.data());
+  if (cfg_.initial_guess == 1 && last_status_ == GTOP_OK) {
+    last_status_ = gtop_min_jerk_start(ctx_, 1, dp_.data());
+    if (last_status_ == GTOP_OK) coefficientsFromDerivatives(dp_);
+  }
 }
 
 void GradTrajOptimizer::setPath(const std::vector<Vec3> &way_points) {
@@ -401,6 +405,32 @@ void GradTrajBatch::setPaths(const std::vector<std::vector<Vec3>> &way_points) {
   min_cost_.assign(B, 0.0);
   nevals_.assign(B, 0);
   last_status_ = GTOP_OK;
+  if (cfg_.initial_guess != 1) return;
+  // the minimum-jerk start: one call per distinct segment count on the first member's context (its problem is set anew
+  // by every optimizeTrajectories)
+  gtop_ctx *ctx = gtop_group_context(grp_, 0);
+  std::vector<int> order(B);
+  for (int b = 0; b < B; ++b) order[b] = b;
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return m_of_[a] < m_of_[b]; });
+  std::vector<double> T, Df, x;
+  for (int lo = 0; lo < B;) {
+    const int m = m_of_[order[lo]];
+    int hi = lo;
+    while (hi < B && m_of_[order[hi]] == m) ++hi;
+    const int nb = hi - lo;
+    const size_t n = 9 * (size_t)(m - 1);
+    T.resize((size_t)nb * m); Df.resize((size_t)nb * 18); x.resize(nb * n);
+    for (int k = 0; k < nb; ++k) {
+      const int b = order[lo + k];
+      std::copy_n(&T_[T_at_[b]], m, &T[(size_t)k * m]);
+      std::copy_n(&Df_[(size_t)b * 18], 18, &Df[(size_t)k * 18]);
+      std::copy_n(&x_[x_at_[b]], n, &x[k * n]);
+    }
+    if ((last_status_ = gtop_set_problem(ctx, nb, m, T.data(), m, Df.data())) != GTOP_OK) return;
+    if ((last_status_ = gtop_min_jerk_start(ctx, nb, x.data())) != GTOP_OK) return;
+    for (int k = 0; k < nb; ++k) std::copy_n(&x[k * n], n, &x_[x_at_[order[lo + k]]]);
+    lo = hi;
+  }
 }
 
 bool GradTrajBatch::optimizeTrajectories(int step) {

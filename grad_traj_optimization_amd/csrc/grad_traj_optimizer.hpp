@@ -73,6 +73,12 @@ class GradTrajOptimizer {
     // 0 = GTOP_GRADIENT_REFERENCE, the reference's callback line by line (its iterates); 1 = GTOP_GRADIENT_CONSISTENT,
     // the gradient of the cost as returned — the one to optimise with
     int gradient_mode = 0;
+    // the start point setPath / setKinoPath leave in Dp (GradTrajBatch::setPaths too): 0 = the reference's — the
+    // straight line of PolyQPGeneration(type = 2) in setPath (zero velocity and acceleration at every waypoint), the
+    // given derivatives in setKinoPath; 1 = positions, Df and segment times as they are, the interior velocities and
+    // accelerations replaced by the minimiser of the smoothness term (include/gtop.h, gtop_min_jerk_start: the
+    // reference's type == 1, src/qp_generator.cpp:242-315), the coefficients refreshed from it
+    int initial_guess = 0;
   };
 
   GradTrajOptimizer();

@@ -3,6 +3,7 @@
 #include <cmath>
 
 #include "gtop_ctx.h"
+#include "gtop_minjerk_plan.h"
 
 extern "C" {
 
@@ -72,6 +73,37 @@ int gtop_set_paths(gtop_ctx *c, int B, int m, const double *waypoints, double me
   if (x0) HIPCHK(c, hipMemcpyAsync(x0, c->d_x.data(), (size_t)B * n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->B = B; c->m = m; c->t_stride = m;
+  return GTOP_OK;
+} GTOP_CATCH_STATUS(c)
+
+// ---- the minimum-jerk start point (gtop_minjerk.hip) ----
+int gtop_min_jerk_start_device(gtop_ctx *c, int B, int m, void *d_x, const void *d_Df, const void *d_T, int time_stride,
+                               void *hip_stream) try {
+  if (!c) return GTOP_ERR_INVALID;
+  GtopMinJerkPlan plan;
+  if (!gtop_minjerk_plan(B, m, &plan) || (time_stride != 0 && time_stride != m))
+    return fail(c, GTOP_ERR_INVALID, "min_jerk_start: need B >= 0, 2 <= m <= 227, time_stride in {0, m}");
+  if (!d_x || !d_Df || !d_T) return fail(c, GTOP_ERR_INVALID, "min_jerk_start: NULL buffer");
+  if (B == 0) return GTOP_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, gtop_launch_min_jerk_start(B, m, static_cast<double *>(d_x), static_cast<const double *>(d_Df),
+                                       static_cast<const double *>(d_T), time_stride,
+                                       static_cast<hipStream_t>(hip_stream)));
+  return GTOP_OK;
+} GTOP_CATCH_STATUS(c)
+
+int gtop_min_jerk_start(gtop_ctx *c, int B, double *x) try {
+  if (!c) return GTOP_ERR_INVALID;
+  if (c->B == 0) return fail(c, GTOP_ERR_STATE, "gtop_set_problem / gtop_set_paths has not been called");
+  if (B < 1 || B > c->B || !x) return fail(c, GTOP_ERR_INVALID, "min_jerk_start: 1 <= B <= problem batch, x required");
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t bytes = (size_t)B * 9 * (size_t)(c->m - 1) * sizeof(double);
+  int rc;
+  HIPCHK(c, hipMemcpyAsync(c->d_x.data(), x, bytes, hipMemcpyHostToDevice, c->stream));
+  if ((rc = gtop_min_jerk_start_device(c, B, c->m, c->d_x.data(), c->d_Df.data(), c->d_T.data(), c->t_stride, c->stream)))
+    return rc;
+  HIPCHK(c, hipMemcpyAsync(x, c->d_x.data(), bytes, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
   return GTOP_OK;
 } GTOP_CATCH_STATUS(c)
 

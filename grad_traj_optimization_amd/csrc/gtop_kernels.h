@@ -179,6 +179,12 @@ hipError_t gtop_launch_eval_trajectories(int B, int m, const double *coeff, cons
                                          double dt_sample, double *out, double *samples, int max_samples,
                                          hipStream_t stream);
 
+// ---- the minimum-jerk start point (gtop_minjerk.hip; its launch plan: gtop_minjerk_plan.h), fp64 ----
+// Overwrites the velocity and acceleration entries of x [B][9 (m - 1)] with the minimiser of the smoothness term at the
+// positions x holds; hipErrorInvalidValue where the plan refuses (m outside 2 .. 227, B < 0)
+hipError_t gtop_launch_min_jerk_start(int B, int m, double *x, const double *Df, const double *T, int t_stride,
+                                      hipStream_t stream);
+
 // ---- static field + moving boxes (gtop_edt.hip) -----------------------------
 // The box list the query and the report take: one of two kinds, with the pointers of that kind (the other kind's stay
 // NULL); count 0 = no boxes, whatever the kind.

@@ -84,7 +84,8 @@ const char *gtop_last_error(const gtop_ctx *ctx);
  * gtop_select_best_device / gtop_validate_batch; 6: the gradient mode,
  * gtop_set_gradient_mode / gtop_get_gradient_mode / gtop_group_set_gradient_mode;
  * 7: the polynomial box list, gtop_set_moving_box_polynomials /
- * gtop_get_moving_box_kind / gtop_box_polynomial_centres;
+ * gtop_get_moving_box_kind / gtop_box_polynomial_centres; 8: the minimum-jerk
+ * start point, gtop_min_jerk_start_device / gtop_min_jerk_start;
  * nothing of an earlier version changed meaning). */
 int gtop_abi_version(void);
 
@@ -226,6 +227,65 @@ int gtop_setup_paths_device(gtop_ctx *ctx, int B, int m, const void *d_waypoints
                             double mean_v, double init_time, void *d_T,
                             void *d_Df, void *d_x0, void *hip_stream);
 int gtop_get_problem(gtop_ctx *ctx, double *segment_time, double *Df);
+
+/* ---- the minimum-jerk start point -------------------------------------
+ * The start point above is the reference's PolyQPGeneration(type = 2)
+ * (src/qp_generator.cpp:317-345, :433-439): zero velocity and acceleration at
+ * every interior waypoint, a stop-and-go trajectory.  This is the alternative of
+ * the same function, type == 1 (:242-315), which setPath never selects
+ * (src/grad_traj_optimizer.cpp:86): the waypoint positions stay fixed and the
+ * interior (v_k, a_k), k = 1 .. m-1, become the minimiser of the smoothness term
+ * the evaluations return, sum over the axes of d' R d (StackOptiDep, :357-403) —
+ * generalised to any boundary velocity and acceleration (type == 1 has the end
+ * pair at 0; Df carries all four).  R is never formed.  In the segment-local order
+ * [p(0), p(T), v(0), v(T), a(0), a(T)] the jerk integral of one quintic segment of
+ * duration T is d' M(T) d,
+ *   M(1) = [  720 -720  360  360   60  -60 ]   M(T)(i,j) = M(1)(i,j) / T^(5 - o_i - o_j),
+ *          [ -720  720 -360 -360  -60   60 ]   o = 0 for a position row / column,
+ *          [  360 -360  192  168   36  -24 ]   1 for a velocity, 2 for an acceleration
+ *          [  360 -360  168  192   24  -36 ]
+ *          [   60  -60   36   24    9   -3 ]
+ *          [  -60   60  -24  -36   -3    9 ]
+ * and the normal equations are block tridiagonal with 2 x 2 blocks, symmetric
+ * positive definite, one matrix for the three axes.  With u_k = (v_k, a_k),
+ * Ta = T[k-1], Tb = T[k]:
+ *   D_k = [ 192/Ta^3 + 192/Tb^3   -36/Ta^2 + 36/Tb^2 ]    U_k = [ 168/Tb^3  -24/Tb^2 ]
+ *         [ -36/Ta^2 + 36/Tb^2      9/Ta   +  9/Tb   ]          [  24/Tb^2   -3/Tb   ]
+ *   D_k u_k + U_{k-1}' u_{k-1} + U_k u_{k+1} = -g_k
+ *   g_k(v) = 360 (p_{k-1} - p_k)/Ta^4 + 360 (p_k - p_{k+1})/Tb^4
+ *   g_k(a) = -60 (p_{k-1} - p_k)/Ta^3 +  60 (p_k - p_{k+1})/Tb^3
+ * u_0 is the start pair of Df, u_m the end pair; both move to the right-hand
+ * side; m = 2 is a single 2 x 2 system.  Solved by block elimination, O(m) per
+ * trajectory, one lane each (csrc/gtop_minjerk.hip).
+ *
+ * x: B*n, the free variables in the usual layout x[i + axis*(3m-3)],
+ * i = 3(k-1) + {0: p, 1: v, 2: a}.  The call reads the position entries, Df and T,
+ * OVERWRITES the velocity and acceleration entries with the minimiser and writes
+ * nothing else — so it composes with everything that makes an x: the output of
+ * gtop_setup_paths_device / gtop_set_paths (which stay what they are), or a
+ * caller's own waypoints with gtop_set_problem.  The straight-line start and the
+ * minimum-jerk start of one waypoint list are two natural candidates of one batch
+ * for gtop_optimize_device_ex, gtop_validate_trajectories_device and
+ * gtop_select_best_device.
+ * The device form only enqueues on hip_stream: no allocation, no synchronisation,
+ * capturable; it needs no distance field and no parameters.  fp64 only.
+ * time_stride is m or 0; 2 <= m <= 227, the evaluation's own limit; B = 0 launches
+ * nothing and returns GTOP_OK.  GTOP_ERR_INVALID, nothing launched: a NULL
+ * pointer, B < 0, m out of range, another time_stride; in the host form B < 1 or B
+ * above the problem's batch.  The host form serves the first B rows of the
+ * context's problem (GTOP_ERR_STATE when none is set) and stages through the
+ * context's buffers.
+ * The device form cannot inspect T, as gtop_setup_paths_device cannot: a
+ * trajectory with a zero segment time gets non-finite v, a in its own row — every
+ * loop is bounded by m, nothing else is touched.
+ * A row's result depends on that row's inputs only: not on its index, on B, or on
+ * whether the times are shared.  Two rows with equal inputs get equal bits.
+ * The minimiser knows no bounds: a velocity beyond +-vos (an acceleration beyond
+ * +-aos) is legal input to the optimizer, which clamps its start point into the
+ * box before the first evaluation (csrc/gtop_mma.hip, csrc/mma.hpp). */
+int gtop_min_jerk_start_device(gtop_ctx *ctx, int B, int m, void *d_x, const void *d_Df,
+                               const void *d_T, int time_stride, void *hip_stream);
+int gtop_min_jerk_start(gtop_ctx *ctx, int B, double *x);
 
 /* ---- evaluation ----------------------------------------------------- */
 
