@@ -149,9 +149,9 @@ int update_sdf_map_on_stream(gtop_ctx *c, const double *d_pts, int npts, hipStre
   HIPCHK(c, gtop_launch_esdf_reset(occ, nullptr, nvox, s));
   HIPCHK(c, gtop_launch_esdf_mark(g, d_pts, npts, occ, s));         // setOccupancy
   if (f.sign_next)   // the signed field (gtop_set_field_sign): a second transform fills the occupied voxels
-    HIPCHK(c, gtop_launch_esdf_build_signed(g, occ, tmp1, tmp2, rows, f.sdf64, nullptr, field_depth(f.depth_next), s));
+    HIPCHK(c, gtop_launch_esdf_build_signed(g, occ, tmp1, tmp2, rows, f.sdf64, field_depth(f.depth_next), s));
   else
-    HIPCHK(c, gtop_launch_esdf_build(g, occ, tmp1, tmp2, rows, f.sdf64, nullptr, s));   // updateESDF3d
+    HIPCHK(c, gtop_launch_esdf_build(g, occ, tmp1, tmp2, rows, f.sdf64, s));   // updateESDF3d
   // the corner records behind it, on the same stream (device-side: holds for graph replays too); the fp32 ones now
   // when they are wanted now, otherwise at the first fp32 evaluation (host-synchronous caller only, see GtopField)
   return f.arrived(c, s, convert_now);
@@ -206,9 +206,9 @@ int update_window_on_stream(gtop_ctx *c, const double min_pos[3], const double m
     // need no reset: the scatter below rewrites every voxel of it
     HIPCHK(c, gtop_launch_esdf_window_reset_mark_compact(g, lo, hi, d_pts, npts, occ, win_occ, s));
     if (f.sign)
-      HIPCHK(c, gtop_launch_esdf_build_signed(sub, win_occ, tmp1, tmp2, rows, win_dist, nullptr, field_depth(f.depth), s));
+      HIPCHK(c, gtop_launch_esdf_build_signed(sub, win_occ, tmp1, tmp2, rows, win_dist, field_depth(f.depth), s));
     else
-      HIPCHK(c, gtop_launch_esdf_build(sub, win_occ, tmp1, tmp2, rows, win_dist, nullptr, s));
+      HIPCHK(c, gtop_launch_esdf_build(sub, win_occ, tmp1, tmp2, rows, win_dist, s));
     HIPCHK(c, gtop_launch_esdf_window_scatter(g, lo, hi, win_dist, f.sdf64, s));
   } else {   // a sliver
     HIPCHK(c, gtop_launch_esdf_window_reset(g, lo, hi, occ, f.sdf64, s));

@@ -24,8 +24,8 @@
 //             obstacle-free stretches cost nothing;
 //   x sweep : outward scan v = q-1, q+1, q-2, ... with the same cut-off (in(v) >= 0);
 //             it also applies the final res*sqrt(.) (exactly rounded fp64, as the
-//             reference's).  (Round 4: the GTOP_F32 path reads fp32 corner records, gtop_records.hip; dist32 is NULL.)  The fp32 copy used by the GTOP_F32 path was made by the
-//             caller on first use (a third of the sweep's writes).
+//             reference's).  The field is stored in fp64 only: the GTOP_F32 path reads fp32 corner records, which
+//             gtop_records.hip makes from it.
 // What bounds the scans, and what this file does about it (measured, profiles/r2/esdf_kernels.txt):
 //   * the texture-address unit takes 16 cycles per wave64 load whatever its width, so a lane owns 4 voxels
 //     adjacent in z and every load is 16 bytes (y sweep 46 -> 22 us at 200^3);
@@ -297,6 +297,58 @@ struct __attribute__((aligned(16))) PkV { gtop_u16x2 p[4]; };
 // kEsdfYLocalMax) — no esdf_rows_kernel launch between the sweeps (5 us of a 110 us build at 200^3), and the list is
 // then read from LDS instead of global memory.
 
+// The LOCAL list of slab x, by the workgroup's first wavefront: ballots over the slab's column flags, 64 columns at a
+// time.  s_cols[0 .. c) = the y of the columns that hold an obstacle, ascending; s_mask[k] = the flags of columns
+// 64k .. 64k + 63; s_pref[k] = the number of candidates below column 64k, s_pref[ceil(ny / 64)] = c.  The slab's first
+// workgroup also leaves c in cnt_out[x] (0: the x sweep jumps over the slab's rows) and counts the empty slabs in
+// cnt_out[nx].  Ends with the workgroup's barrier.
+__device__ __forceinline__ void esdf_stage_candidates(const uint8_t *__restrict__ colany, const int x, const int nx,
+                                                      const int ny, const bool first_of_slab, unsigned short *s_cols,
+                                                      unsigned long long *s_mask, int *s_pref, int *__restrict__ cnt_out) {
+  if (threadIdx.x < 64) {
+    const int lane = threadIdx.x;
+    const uint8_t *ca = colany + x * ny;
+    constexpr int kPre = 4;   // flag loads in flight
+    int base = 0;
+    for (int y0 = 0; y0 < ny; y0 += 64 * kPre) {
+      bool f[kPre];
+#pragma unroll
+      for (int u = 0; u < kPre; ++u) {
+        const int y = y0 + 64 * u + lane;
+        f[u] = (y < ny) && ca[y];
+      }
+#pragma unroll
+      for (int u = 0; u < kPre; ++u) {
+        const int y = y0 + 64 * u + lane;
+        if (y0 + 64 * u >= ny) break;
+        const unsigned long long mk = __ballot(f[u]);
+        if (f[u]) s_cols[base + __popcll(mk & ((1ull << lane) - 1ull))] = (unsigned short)y;
+        if (lane == 0) {
+          s_mask[(y0 >> 6) + u] = mk;
+          s_pref[(y0 >> 6) + u] = base;
+        }
+        base += __popcll(mk);
+      }
+    }
+    if (lane == 0) {
+      s_pref[(ny + 63) >> 6] = base;
+      if (first_of_slab) {
+        cnt_out[x] = base;
+        if (base == 0) atomicAdd(cnt_out + nx, 1);
+      }
+    }
+  }
+  __syncthreads();
+}
+
+// four minima as two pairs of 16-bit words, min(value, 0xFFFF) each: the packed sweeps' form of them
+__device__ __forceinline__ uint2 esdf_pack_sat16(const IntV<4> &b) {
+  uint2 pk;
+  pk.x = (unsigned)min(b.v[0], 0xFFFF) | ((unsigned)min(b.v[1], 0xFFFF) << 16);
+  pk.y = (unsigned)min(b.v[2], 0xFFFF) | ((unsigned)min(b.v[3], 0xFFFF) << 16);
+  return pk;
+}
+
 template <int V, bool LOCAL>
 __global__ void __launch_bounds__(256)
 esdf_y_kernel(const GtopGrid g, const int *__restrict__ fin, int *__restrict__ fout, uint16_t *__restrict__ fout16,
@@ -317,40 +369,7 @@ esdf_y_kernel(const GtopGrid g, const int *__restrict__ fin, int *__restrict__ f
   __shared__ int s_pref[LOCAL ? kEsdfYLocalMax / 64 + 1 : 1];
   if constexpr (LOCAL) {
     if (x >= g.nx) return;   // (workgroup-uniform)
-    if (threadIdx.x < 64) {  // one wavefront: ballots over the slab's column flags, 64 columns at a time
-      const int lane = threadIdx.x;
-      const uint8_t *ca = colany + x * ny;
-      constexpr int kPre = 4;   // flag loads in flight
-      int base = 0;
-      for (int y0 = 0; y0 < ny; y0 += 64 * kPre) {
-        bool f[kPre];
-#pragma unroll
-        for (int u = 0; u < kPre; ++u) {
-          const int y = y0 + 64 * u + lane;
-          f[u] = (y < ny) && ca[y];
-        }
-#pragma unroll
-        for (int u = 0; u < kPre; ++u) {
-          const int y = y0 + 64 * u + lane;
-          if (y0 + 64 * u >= ny) break;
-          const unsigned long long mk = __ballot(f[u]);
-          if (f[u]) s_cols[base + __popcll(mk & ((1ull << lane) - 1ull))] = (unsigned short)y;
-          if (lane == 0) {
-            s_mask[(y0 >> 6) + u] = mk;
-            s_pref[(y0 >> 6) + u] = base;
-          }
-          base += __popcll(mk);
-        }
-      }
-      if (lane == 0) {
-        s_pref[(ny + 63) >> 6] = base;
-        if (yl.first) {   // the slab's number of obstacle columns (0: the x sweep jumps over its rows)
-          cnt_out[x] = base;
-          if (base == 0) atomicAdd(cnt_out + g.nx, 1);
-        }
-      }
-    }
-    __syncthreads();
+    esdf_stage_candidates(colany, x, g.nx, ny, yl.first, s_cols, s_mask, s_pref, cnt_out);
     if (r >= nyz) return;
   } else {
     if (x >= g.nx || r >= nyz) return;
@@ -426,12 +445,8 @@ esdf_y_kernel(const GtopGrid g, const int *__restrict__ fin, int *__restrict__ f
   for (int e = 0; e < V; ++e) best.v[e] = best.v[e] > kInf ? kInf : best.v[e];
   *reinterpret_cast<IntV<V> *>(fout + i) = best;
   if constexpr (V == 4) {
-    if (fout16) {   // the x sweep's packed 16-bit form: min(value, 0xFFFF) (wave-uniform branch)
-      uint2 pk;
-      pk.x = (unsigned)min(best.v[0], 0xFFFF) | ((unsigned)min(best.v[1], 0xFFFF) << 16);
-      pk.y = (unsigned)min(best.v[2], 0xFFFF) | ((unsigned)min(best.v[3], 0xFFFF) << 16);
-      *reinterpret_cast<uint2 *>(fout16 + i) = pk;
-    }
+    // the x sweep's packed 16-bit form (wave-uniform branch)
+    if (fout16) *reinterpret_cast<uint2 *>(fout16 + i) = esdf_pack_sat16(best);
   }
 #ifdef GTOP_ESDF_STAMPS
   if (getenv_stamp_y) {
@@ -465,42 +480,7 @@ esdf_y16_kernel(const GtopGrid g, const uint16_t *__restrict__ fin16, const int 
   __shared__ unsigned long long s_mask[LOCAL ? kEsdfYLocalMax / 64 : 1];
   __shared__ int s_pref[LOCAL ? kEsdfYLocalMax / 64 + 1 : 1];
   if (x >= g.nx) return;   // (workgroup-uniform)
-  if constexpr (LOCAL) {
-    if (threadIdx.x < 64) {  // one wavefront: ballots over the slab's column flags (as esdf_y_kernel)
-      const int lane = threadIdx.x;
-      const uint8_t *ca = colany + x * ny;
-      constexpr int kPre = 4;
-      int base = 0;
-      for (int y0 = 0; y0 < ny; y0 += 64 * kPre) {
-        bool f[kPre];
-#pragma unroll
-        for (int u = 0; u < kPre; ++u) {
-          const int y = y0 + 64 * u + lane;
-          f[u] = (y < ny) && ca[y];
-        }
-#pragma unroll
-        for (int u = 0; u < kPre; ++u) {
-          const int y = y0 + 64 * u + lane;
-          if (y0 + 64 * u >= ny) break;
-          const unsigned long long mk = __ballot(f[u]);
-          if (f[u]) s_cols[base + __popcll(mk & ((1ull << lane) - 1ull))] = (unsigned short)y;
-          if (lane == 0) {
-            s_mask[(y0 >> 6) + u] = mk;
-            s_pref[(y0 >> 6) + u] = base;
-          }
-          base += __popcll(mk);
-        }
-      }
-      if (lane == 0) {
-        s_pref[(ny + 63) >> 6] = base;
-        if (yl.first) {
-          cnt_out[x] = base;
-          if (base == 0) atomicAdd(cnt_out + g.nx, 1);
-        }
-      }
-    }
-    __syncthreads();
-  }
+  if constexpr (LOCAL) esdf_stage_candidates(colany, x, g.nx, ny, yl.first, s_cols, s_mask, s_pref, cnt_out);
   // whole wavefronts only (the fallback below is decided per wavefront): lanes past the slab's end shadow its last
   // lane with work and store nothing
   const int wave_first = r_raw - ((int)threadIdx.x & 63) * V;
@@ -618,12 +598,7 @@ esdf_y16_kernel(const GtopGrid g, const uint16_t *__restrict__ fin16, const int 
       for (int e = 0; e < 4; ++e) b32.v[e] = b32.v[e] > kInf ? kInf : b32.v[e];
       if (has_work) {
         *reinterpret_cast<IntV<4> *>(fout + ih) = b32;
-        if (fout16) {
-          uint2 pk;
-          pk.x = (unsigned)min(b32.v[0], 0xFFFF) | ((unsigned)min(b32.v[1], 0xFFFF) << 16);
-          pk.y = (unsigned)min(b32.v[2], 0xFFFF) | ((unsigned)min(b32.v[3], 0xFFFF) << 16);
-          *reinterpret_cast<uint2 *>(fout16 + ih) = pk;
-        }
+        if (fout16) *reinterpret_cast<uint2 *>(fout16 + ih) = esdf_pack_sat16(b32);
       }
     }
     return;
@@ -719,8 +694,8 @@ __device__ __forceinline__ double esdf_interior(double res, double neg_depth, do
 // the scan of one lane's block: V voxels from `first` (slab 0) times the kEsdfXB slabs from q0
 template <int V, bool SIGNED = false>
 __device__ __forceinline__ void esdf_x_scan_block(const GtopGrid &g, const int *__restrict__ fin, double *__restrict__ dist,
-                                                  float *__restrict__ dist32, const int first, const int q0,
-                                                  const EsdfSlabRuns *sr, const uint16_t *__restrict__ f16 = nullptr,
+                                                  const int first, const int q0, const EsdfSlabRuns *sr,
+                                                  const uint16_t *__restrict__ f16 = nullptr,
                                                   const uint8_t *__restrict__ occ = nullptr, double neg_depth = 0.0) {
   constexpr int kScanBatch = 4;   // steps per round trip
   // f16 set (the packed x sweep's exact fallback, V = 4): the packed y sweep stores its int32 output only where the
@@ -829,7 +804,6 @@ __device__ __forceinline__ void esdf_x_scan_block(const GtopGrid &g, const int *
         double dv = neg_depth;
         if (best[e].v[v] < kInf) dv = esdf_interior(g.res, neg_depth, sqrt((double)best[e].v[v]));
         dist[row[e] + v] = dv;
-        if (dist32) dist32[row[e] + v] = (float)dv;
         continue;
       }
       double dv = 10000.0;
@@ -838,7 +812,6 @@ __device__ __forceinline__ void esdf_x_scan_block(const GtopGrid &g, const int *
         dv = r < dv ? r : dv;
       }
       dist[row[e] + v] = dv;
-      if (dist32) dist32[row[e] + v] = (float)dv;   // (wave-uniform; the caller may make the fp32 copy later)
     }
   }
 }
@@ -849,25 +822,15 @@ __device__ __forceinline__ void esdf_x_scan_block(const GtopGrid &g, const int *
 // lane without work.
 template <int BLOCK = kEsdfXBlock, bool SHADOW = false>
 __device__ __forceinline__ bool esdf_x_lane(const int nl, int *fl, int *q0) {
-#ifdef GTOP_ESDF_X_PARTS   // tuning, round 2's first form: XCD c owns the c-th eighth of the plane (one contiguous part)
-  const int part = (nl + 7) >> 3, bpp = (part + BLOCK - 1) / BLOCK;
-  const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
-  const int li = (j % bpp) * BLOCK + (int)threadIdx.x;
-  *q0 = (j / bpp) * kEsdfXB;
-  *fl = xcd * part + li;
-  return li < part && *fl < nl;
-#else
   const GtopEsdfXLane l = gtop_esdf_x_lane(blockIdx.x, (int)threadIdx.x, nl, BLOCK, SHADOW);
   *q0 = l.q0;
   *fl = l.fl;
   return l.work;
-#endif
 }
 
 template <int V>
 __global__ void __launch_bounds__(256)
-esdf_x_kernel(const GtopGrid g, const int *__restrict__ fin, double *__restrict__ dist, float *__restrict__ dist32,
-              const int *__restrict__ cnt) {
+esdf_x_kernel(const GtopGrid g, const int *__restrict__ fin, double *__restrict__ dist, const int *__restrict__ cnt) {
   __shared__ EsdfSlabRuns s_runs;
   const EsdfSlabRuns *sr = esdf_stage_slab_runs(&s_runs, cnt, g.nx) ? &s_runs : nullptr;
   int fl, q0;
@@ -875,7 +838,7 @@ esdf_x_kernel(const GtopGrid g, const int *__restrict__ fin, double *__restrict_
   const unsigned long long t0 = wall_clock64();
 #endif
   if (!esdf_x_lane(g.ny * g.nz / V, &fl, &q0)) return;
-  esdf_x_scan_block<V>(g, fin, dist, dist32, fl * V, q0, sr);
+  esdf_x_scan_block<V>(g, fin, dist, fl * V, q0, sr);
 #ifdef GTOP_ESDF_STAMPS
   if (!getenv_stamp_y) esdf_stamp(t0, -1);
 #endif
@@ -885,13 +848,13 @@ esdf_x_kernel(const GtopGrid g, const int *__restrict__ fin, double *__restrict_
 // occupied voxels only (esdf_interior)
 template <int V>
 __global__ void __launch_bounds__(256)
-esdf_x_signed_kernel(const GtopGrid g, const int *__restrict__ fin, double *__restrict__ dist, float *__restrict__ dist32,
-                     const int *__restrict__ cnt, const uint8_t *__restrict__ occ, double neg_depth) {
+esdf_x_signed_kernel(const GtopGrid g, const int *__restrict__ fin, double *__restrict__ dist, const int *__restrict__ cnt,
+                     const uint8_t *__restrict__ occ, double neg_depth) {
   __shared__ EsdfSlabRuns s_runs;
   const EsdfSlabRuns *sr = esdf_stage_slab_runs(&s_runs, cnt, g.nx) ? &s_runs : nullptr;
   int fl, q0;
   if (!esdf_x_lane(g.ny * g.nz / V, &fl, &q0)) return;
-  esdf_x_scan_block<V, true>(g, fin, dist, dist32, fl * V, q0, sr, nullptr, occ, neg_depth);
+  esdf_x_scan_block<V, true>(g, fin, dist, fl * V, q0, sr, nullptr, occ, neg_depth);
 }
 
 // The x sweep on packed 16-bit values.  Squared distances below 2^16 (255 voxels: 51 m at the reference's 0.2 m)
@@ -907,11 +870,7 @@ esdf_x_signed_kernel(const GtopGrid g, const int *__restrict__ fin, double *__re
 // its special-case selects (22 instructions): the hardware's reciprocal-square-root estimate and the same Goldschmidt
 // refinement (two residual corrections), 12 instructions.  Bit for bit the library's result on every value the packed
 // sweep can produce (tests/test_gpu_parity.py: a 256^3 map with one obstacle in its corner holds them all).
-#ifndef GTOP_ESDF_LEAN_SQRT
-#define GTOP_ESDF_LEAN_SQRT 1
-#endif
 __device__ __forceinline__ double esdf_sqrt_u16(int n) {
-#if GTOP_ESDF_LEAN_SQRT
   const double x = (double)n;
   const double y = __builtin_amdgcn_rsq(x);   // (n = 0: inf, selected away below)
   double g = x * y, h = 0.5 * y;
@@ -921,23 +880,15 @@ __device__ __forceinline__ double esdf_sqrt_u16(int n) {
   g = fma(fma(-g, g, x), h, g);
   g = fma(fma(-g, g, x), h, g);
   return n == 0 ? 0.0 : g;
-#else
-  return sqrt((double)n);
-#endif
 }
-
-#ifndef GTOP_ESDF_X16_BATCH
-#define GTOP_ESDF_X16_BATCH 4
-#endif
 
 template <bool SIGNED>
 __device__ __forceinline__ void esdf_x16_body(const GtopGrid &g, const uint16_t *__restrict__ f16, const int *__restrict__ fin,
-                                              double *__restrict__ dist, float *__restrict__ dist32,
-                                              const int *__restrict__ cnt, const uint8_t *__restrict__ occ,
-                                              const double neg_depth) {
+                                              double *__restrict__ dist, const int *__restrict__ cnt,
+                                              const uint8_t *__restrict__ occ, const double neg_depth) {
   __shared__ EsdfSlabRuns s_runs;
   const EsdfSlabRuns *sr = esdf_stage_slab_runs(&s_runs, cnt, g.nx) ? &s_runs : nullptr;
-  constexpr int kScanBatch = GTOP_ESDF_X16_BATCH;
+  constexpr int kScanBatch = 4;   // steps per round trip
   const int nyz = g.ny * g.nz;
   const int n = g.nx;
   int fl, q0;
@@ -1032,8 +983,8 @@ __device__ __forceinline__ void esdf_x16_body(const GtopGrid &g, const uint16_t 
     worst = worst_of();
   }
   if (__any(worst == 0xFFFF)) {   // (wave-uniform) a minimum at or past 2^16 - 1: the exact 32-bit scan instead
-    esdf_x_scan_block<4, SIGNED>(g, fin, dist, dist32, first, q0, sr, f16, occ, neg_depth);
-    esdf_x_scan_block<4, SIGNED>(g, fin, dist, dist32, first + 4, q0, sr, f16, occ, neg_depth);
+    esdf_x_scan_block<4, SIGNED>(g, fin, dist, first, q0, sr, f16, occ, neg_depth);
+    esdf_x_scan_block<4, SIGNED>(g, fin, dist, first + 4, q0, sr, f16, occ, neg_depth);
     return;
   }
 #ifdef GTOP_ESDF_STAMPS
@@ -1064,14 +1015,8 @@ __device__ __forceinline__ void esdf_x16_body(const GtopGrid &g, const uint16_t 
       const int nn[2] = {(int)(pk & 0xFFFFu), (int)(pk >> 16)};
       if constexpr (SIGNED) {   // the occupied voxels of the pair only (esdf_interior); every value here is finite
         const uchar2 o = *reinterpret_cast<const uchar2 *>(occ + rowbase + v);
-        if (o.x == 1) {
-          dist[rowbase + v] = esdf_interior(g.res, neg_depth, esdf_sqrt_u16(nn[0]));
-          if (dist32) dist32[rowbase + v] = (float)dist[rowbase + v];
-        }
-        if (o.y == 1) {
-          dist[rowbase + v + 1] = esdf_interior(g.res, neg_depth, esdf_sqrt_u16(nn[1]));
-          if (dist32) dist32[rowbase + v + 1] = (float)dist[rowbase + v + 1];
-        }
+        if (o.x == 1) dist[rowbase + v] = esdf_interior(g.res, neg_depth, esdf_sqrt_u16(nn[0]));
+        if (o.y == 1) dist[rowbase + v + 1] = esdf_interior(g.res, neg_depth, esdf_sqrt_u16(nn[1]));
         continue;
       }
       double2 dv;
@@ -1081,7 +1026,6 @@ __device__ __forceinline__ void esdf_x16_body(const GtopGrid &g, const uint16_t 
         dv.y = r1 < 10000.0 ? r1 : 10000.0;
       }
       *reinterpret_cast<double2 *>(dist + rowbase + v) = dv;
-      if (dist32) *reinterpret_cast<float2 *>(dist32 + rowbase + v) = make_float2((float)dv.x, (float)dv.y);
     }
   }
 #ifdef GTOP_ESDF_STAMPS
@@ -1090,20 +1034,17 @@ __device__ __forceinline__ void esdf_x16_body(const GtopGrid &g, const uint16_t 
 }
 
 __global__ void __launch_bounds__(kEsdfX16Block)
-#ifdef GTOP_ESDF_X16_WPE
-__attribute__((amdgpu_waves_per_eu(GTOP_ESDF_X16_WPE)))
-#endif
 esdf_x16_kernel(const GtopGrid g, const uint16_t *__restrict__ f16, const int *__restrict__ fin,
-                double *__restrict__ dist, float *__restrict__ dist32, const int *__restrict__ cnt) {
-  esdf_x16_body<false>(g, f16, fin, dist, dist32, cnt, nullptr, 0.0);
+                double *__restrict__ dist, const int *__restrict__ cnt) {
+  esdf_x16_body<false>(g, f16, fin, dist, cnt, nullptr, 0.0);
 }
 
 // the signed field's interior pass (see esdf_x_signed_kernel)
 __global__ void __launch_bounds__(kEsdfX16Block)
 esdf_x16_signed_kernel(const GtopGrid g, const uint16_t *__restrict__ f16, const int *__restrict__ fin,
-                       double *__restrict__ dist, float *__restrict__ dist32, const int *__restrict__ cnt,
-                       const uint8_t *__restrict__ occ, double neg_depth) {
-  esdf_x16_body<true>(g, f16, fin, dist, dist32, cnt, occ, neg_depth);
+                       double *__restrict__ dist, const int *__restrict__ cnt, const uint8_t *__restrict__ occ,
+                       double neg_depth) {
+  esdf_x16_body<true>(g, f16, fin, dist, cnt, occ, neg_depth);
 }
 
 }  // namespace
@@ -1144,7 +1085,7 @@ size_t gtop_esdf_rows_ints(const GtopGrid &g) {
 // on what grid, is the plan's (gtop_esdf_plan): nothing below looks at the grid's sizes.
 template <bool FREE>
 static hipError_t esdf_build_pass(const GtopGrid &g, const uint8_t *occ, int *tmp1, int *tmp2, int *rows, double *dist,
-                                  float *dist32, double neg_depth, hipStream_t stream) {
+                                  double neg_depth, hipStream_t stream) {
   GtopEsdfPlan p;
   if (!gtop_esdf_plan(g.nx, g.ny, g.nz, &p)) return hipErrorInvalidValue;   // (the callers ask gtop_esdf_supported first)
   int *cols = rows, *rank = rows + p.off_rank, *cnt = rows + p.off_cnt;     // cnt[nx] = number of empty slabs
@@ -1153,23 +1094,13 @@ static hipError_t esdf_build_pass(const GtopGrid &g, const uint8_t *occ, int *tm
   // the z sweep's 16-bit output, read by the packed y sweep alone
   uint16_t *z16 = p.y_vox == 8 ? reinterpret_cast<uint16_t *>(rows + p.off_z16) : (uint16_t *)nullptr;
   const dim3 zgrid(p.z_blocks), zblock(kEsdfZBlock);
-#define ZS(NCH) (esdf_z_small_kernel<NCH, FREE>)
-  if (p.z_lds) {
-    hipLaunchKernelGGL((FREE ? esdf_z_free_kernel : esdf_z_kernel), zgrid, zblock, 0, stream, g, occ, tmp1, z16, colany, cnt + g.nx);
-  } else {
-    switch (p.z_chunks) {
-      case 1: hipLaunchKernelGGL(ZS(1), zgrid, zblock, 0, stream, g, occ, tmp1, z16, colany, cnt + g.nx); break;
-      case 2: hipLaunchKernelGGL(ZS(2), zgrid, zblock, 0, stream, g, occ, tmp1, z16, colany, cnt + g.nx); break;
-      case 3: hipLaunchKernelGGL(ZS(3), zgrid, zblock, 0, stream, g, occ, tmp1, z16, colany, cnt + g.nx); break;
-      case 4: hipLaunchKernelGGL(ZS(4), zgrid, zblock, 0, stream, g, occ, tmp1, z16, colany, cnt + g.nx); break;
-      case 5: hipLaunchKernelGGL(ZS(5), zgrid, zblock, 0, stream, g, occ, tmp1, z16, colany, cnt + g.nx); break;
-      case 6: hipLaunchKernelGGL(ZS(6), zgrid, zblock, 0, stream, g, occ, tmp1, z16, colany, cnt + g.nx); break;
-      case 7: hipLaunchKernelGGL(ZS(7), zgrid, zblock, 0, stream, g, occ, tmp1, z16, colany, cnt + g.nx); break;
-      case 8: hipLaunchKernelGGL(ZS(8), zgrid, zblock, 0, stream, g, occ, tmp1, z16, colany, cnt + g.nx); break;
-      default: return hipErrorInvalidValue;   // (a grid without columns)
-    }
-  }
-#undef ZS
+  using ZKernel = void (*)(GtopGrid, const uint8_t *, int *, uint16_t *, uint8_t *, int *);
+  static constexpr ZKernel kZSmall[kEsdfZSmallChunks] = {   // by z_chunks - 1
+      esdf_z_small_kernel<1, FREE>, esdf_z_small_kernel<2, FREE>, esdf_z_small_kernel<3, FREE>, esdf_z_small_kernel<4, FREE>,
+      esdf_z_small_kernel<5, FREE>, esdf_z_small_kernel<6, FREE>, esdf_z_small_kernel<7, FREE>, esdf_z_small_kernel<8, FREE>};
+  if (p.z_chunks < 1) return hipErrorInvalidValue;   // (a grid without columns)
+  const ZKernel zsweep = p.z_lds ? (FREE ? esdf_z_free_kernel : esdf_z_kernel) : kZSmall[p.z_chunks - 1];
+  hipLaunchKernelGGL(zsweep, zgrid, zblock, 0, stream, g, occ, tmp1, z16, colany, cnt + g.nx);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   const bool ylocal = !p.rows_kernel;   // the y sweep lists its slab's candidates itself
@@ -1180,60 +1111,52 @@ static hipError_t esdf_build_pass(const GtopGrid &g, const uint8_t *occ, int *tm
   }
   uint16_t *y16 = p.y_writes_16 ? f16 : (uint16_t *)nullptr;   // the packed x sweep's input
   const dim3 ygrid(p.y_blocks), yblock(kEsdfYBlock);
-#define GTOP_Y_LAUNCH(VV, LL)                                                                              \
-  hipLaunchKernelGGL((esdf_y_kernel<VV, LL>), ygrid, yblock, 0, stream, g, (const int *)tmp1, tmp2, y16, \
-                     (const int *)cols, (const int *)rank, (const int *)cnt, (const uint8_t *)colany, cnt)
   if (p.y_vox == 8) {
-    if (ylocal)
-      hipLaunchKernelGGL(esdf_y16_kernel<true>, ygrid, yblock, 0, stream, g, (const uint16_t *)z16, (const int *)tmp1,
-                         tmp2, y16, (const int *)cols, (const int *)rank, (const int *)cnt, (const uint8_t *)colany, cnt);
-    else
-      hipLaunchKernelGGL(esdf_y16_kernel<false>, ygrid, yblock, 0, stream, g, (const uint16_t *)z16, (const int *)tmp1,
-                         tmp2, y16, (const int *)cols, (const int *)rank, (const int *)cnt, (const uint8_t *)colany, cnt);
-  } else if (p.y_vox == 4) {
-    if (ylocal) GTOP_Y_LAUNCH(4, true);
-    else GTOP_Y_LAUNCH(4, false);
+    const auto ysweep = ylocal ? esdf_y16_kernel<true> : esdf_y16_kernel<false>;
+    hipLaunchKernelGGL(ysweep, ygrid, yblock, 0, stream, g, (const uint16_t *)z16, (const int *)tmp1, tmp2, y16,
+                       (const int *)cols, (const int *)rank, (const int *)cnt, (const uint8_t *)colany, cnt);
   } else {
-    if (ylocal) GTOP_Y_LAUNCH(1, true);
-    else GTOP_Y_LAUNCH(1, false);
+    const auto ysweep = p.y_vox == 4 ? (ylocal ? esdf_y_kernel<4, true> : esdf_y_kernel<4, false>)
+                                     : (ylocal ? esdf_y_kernel<1, true> : esdf_y_kernel<1, false>);
+    hipLaunchKernelGGL(ysweep, ygrid, yblock, 0, stream, g, (const int *)tmp1, tmp2, y16, (const int *)cols,
+                       (const int *)rank, (const int *)cnt, (const uint8_t *)colany, cnt);
   }
-#undef GTOP_Y_LAUNCH
   e = hipGetLastError();
   if (e != hipSuccess) return e;
   const dim3 xgrid(p.x_blocks), xblock(p.x_block);
   if constexpr (FREE) {
     if (p.x_vox == 8) {
       hipLaunchKernelGGL(esdf_x16_signed_kernel, xgrid, xblock, 0, stream, g, (const uint16_t *)f16, (const int *)tmp2, dist,
-                         dist32, (const int *)cnt, occ, neg_depth);
+                         (const int *)cnt, occ, neg_depth);
     } else if (p.x_vox == 4)
-      hipLaunchKernelGGL(esdf_x_signed_kernel<4>, xgrid, xblock, 0, stream, g, (const int *)tmp2, dist, dist32,
-                         (const int *)cnt, occ, neg_depth);
+      hipLaunchKernelGGL(esdf_x_signed_kernel<4>, xgrid, xblock, 0, stream, g, (const int *)tmp2, dist, (const int *)cnt,
+                         occ, neg_depth);
     else
-      hipLaunchKernelGGL(esdf_x_signed_kernel<1>, xgrid, xblock, 0, stream, g, (const int *)tmp2, dist, dist32,
-                         (const int *)cnt, occ, neg_depth);
+      hipLaunchKernelGGL(esdf_x_signed_kernel<1>, xgrid, xblock, 0, stream, g, (const int *)tmp2, dist, (const int *)cnt,
+                         occ, neg_depth);
     return hipGetLastError();
   }
   (void)neg_depth;
   if (p.x_vox == 8) {
-    hipLaunchKernelGGL(esdf_x16_kernel, xgrid, xblock, 0, stream, g, (const uint16_t *)f16, (const int *)tmp2, dist, dist32,
+    hipLaunchKernelGGL(esdf_x16_kernel, xgrid, xblock, 0, stream, g, (const uint16_t *)f16, (const int *)tmp2, dist,
                        (const int *)cnt);
   } else if (p.x_vox == 4)
-    hipLaunchKernelGGL(esdf_x_kernel<4>, xgrid, xblock, 0, stream, g, (const int *)tmp2, dist, dist32, (const int *)cnt);
+    hipLaunchKernelGGL(esdf_x_kernel<4>, xgrid, xblock, 0, stream, g, (const int *)tmp2, dist, (const int *)cnt);
   else
-    hipLaunchKernelGGL(esdf_x_kernel<1>, xgrid, xblock, 0, stream, g, (const int *)tmp2, dist, dist32, (const int *)cnt);
+    hipLaunchKernelGGL(esdf_x_kernel<1>, xgrid, xblock, 0, stream, g, (const int *)tmp2, dist, (const int *)cnt);
   return hipGetLastError();
 }
 
 hipError_t gtop_launch_esdf_build(const GtopGrid &g, const uint8_t *occ, int *tmp1, int *tmp2, int *rows,
-                                  double *dist, float *dist32, hipStream_t stream) {
-  return esdf_build_pass<false>(g, occ, tmp1, tmp2, rows, dist, dist32, 0.0, stream);
+                                  double *dist, hipStream_t stream) {
+  return esdf_build_pass<false>(g, occ, tmp1, tmp2, rows, dist, 0.0, stream);
 }
 
 // The signed field: the distance field as above, then the transform whose seeds are the free voxels over the same
 // workspaces (the stream orders the passes), which overwrites the occupied voxels.
 hipError_t gtop_launch_esdf_build_signed(const GtopGrid &g, const uint8_t *occ, int *tmp1, int *tmp2, int *rows,
-                                         double *dist, float *dist32, double max_depth, hipStream_t stream) {
-  const hipError_t e = esdf_build_pass<false>(g, occ, tmp1, tmp2, rows, dist, dist32, 0.0, stream);
+                                         double *dist, double max_depth, hipStream_t stream) {
+  const hipError_t e = esdf_build_pass<false>(g, occ, tmp1, tmp2, rows, dist, 0.0, stream);
   if (e != hipSuccess) return e;
-  return esdf_build_pass<true>(g, occ, tmp1, tmp2, rows, dist, dist32, -max_depth, stream);
+  return esdf_build_pass<true>(g, occ, tmp1, tmp2, rows, dist, -max_depth, stream);
 }

@@ -17,14 +17,14 @@ bool gtop_esdf_plan(int nx, int ny, int nz, GtopEsdfPlan *plan) {
   p.z_strided = zwant > (size_t)kEsdfZMaxBlocks;
   p.z_blocks = (unsigned)(p.z_strided ? (size_t)kEsdfZMaxBlocks : zwant);
   // the y sweep's candidate lists: in LDS up to kEsdfYLocalMax columns per row
-  p.rows_kernel = !(GTOP_ESDF_YLOCAL && ny <= kEsdfYLocalMax);
+  p.rows_kernel = ny > kEsdfYLocalMax;
   p.rows_blocks = (unsigned)(nx < kEsdfRowsMaxBlocks ? nx : kEsdfRowsMaxBlocks);
   // Voxels per lane.  The 32-bit scans: 4 adjacent in z where nz % 4 == 0 (16-byte loads), else 1.  The packed 16-bit
   // x sweep (8 per lane) wherever the plane splits into eights of such fours; the packed y sweep (8 per lane) where a
   // lane's eight voxels share a y as well.
-  const int V = (GTOP_ESDF_VEC == 4 && nz % 4 == 0) ? 4 : 1;
-  const bool x16 = GTOP_ESDF_X16 && V == 4 && nyz % 8 == 0;
-  const bool y16 = GTOP_ESDF_Y16 && GTOP_ESDF_X16 && GTOP_ESDF_VEC == 4 && nz % 8 == 0;
+  const int V = nz % 4 == 0 ? 4 : 1;
+  const bool x16 = V == 4 && nyz % 8 == 0;
+  const bool y16 = nz % 8 == 0;
   p.y_vox = y16 ? 8 : V;
   p.y_blocks = gtop_esdf_y_blocks(nx, nyz, p.y_vox);
   p.y_writes_16 = x16;

@@ -17,26 +17,6 @@
 #define GTOP_HD_INLINE inline
 #endif
 
-// ---- tuning switches (make lib OUT=... EXTRA=-D...): the product build defines none of them
-#ifndef GTOP_ESDF_Y16
-#define GTOP_ESDF_Y16 1       // the packed 16-bit y sweep
-#endif
-#ifndef GTOP_ESDF_X16
-#define GTOP_ESDF_X16 1       // the packed 16-bit x sweep
-#endif
-#ifndef GTOP_ESDF_VEC
-#define GTOP_ESDF_VEC 4       // voxels per lane of the 32-bit scans where nz allows
-#endif
-#ifndef GTOP_ESDF_YLOCAL
-#define GTOP_ESDF_YLOCAL 1    // the y sweep lists its slab's candidates itself, in LDS
-#endif
-#ifndef GTOP_ESDF_XB
-#define GTOP_ESDF_XB 4
-#endif
-#ifndef GTOP_ESDF_X16_BLOCK
-#define GTOP_ESDF_X16_BLOCK 128
-#endif
-
 // ---- the thresholds
 constexpr int kEsdfMaxChunks = 64;       // z sweep: 64-voxel chunks per column, i.e. columns up to 4096 voxels ...
 constexpr int kEsdfZSmallChunks = 8;     // ... up to 8 of them with the ballots in scalar registers, past that in LDS
@@ -47,9 +27,9 @@ constexpr int kEsdfRowsMaxBlocks = 65536;
 constexpr int kEsdfYLocalMax = 2048;     // y sweep: candidate lists in LDS up to this many columns per row
 constexpr int kEsdfYBlock = 256;
 constexpr int kEsdfSlabMax = 2048;       // x sweep: empty-slab tables (in LDS) for lines of up to this many slabs
-constexpr int kEsdfXB = GTOP_ESDF_XB;    // x sweep: consecutive slabs per lane
+constexpr int kEsdfXB = 4;               // x sweep: consecutive slabs per lane
 constexpr int kEsdfXBlock = 256;         // the 32-bit x sweep's workgroup
-constexpr int kEsdfX16Block = GTOP_ESDF_X16_BLOCK;   // the packed x sweep's
+constexpr int kEsdfX16Block = 128;       // the packed x sweep's
 
 struct GtopEsdfPlan {
   bool supported;      // false: the builder refuses the grid (everything below is still filled in)
@@ -119,11 +99,7 @@ struct GtopEsdfXLane {
   bool work;   // false: the thread has nothing to do and leaves
 };
 // lanes of one XCD's share of the plane, whole 64-lane chunks
-#ifdef GTOP_ESDF_X_PARTS   // tuning (the x sweep's first form, gtop_esdf.hip): one contiguous eighth of the plane per XCD
-GTOP_HD constexpr int gtop_esdf_x_lanes_per_xcd(int nl) { return (nl + 7) >> 3; }
-#else
 GTOP_HD constexpr int gtop_esdf_x_lanes_per_xcd(int nl) { return ((((nl + 63) >> 6) + 7) >> 3) * 64; }
-#endif
 GTOP_HD constexpr unsigned gtop_esdf_x_blocks(int nx, int nl, int block) {
   return 8u * (unsigned)((nx + kEsdfXB - 1) / kEsdfXB) * (unsigned)((gtop_esdf_x_lanes_per_xcd(nl) + block - 1) / block);
 }

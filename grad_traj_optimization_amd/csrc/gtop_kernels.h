@@ -115,17 +115,17 @@ hipError_t gtop_launch_esdf_reset(uint8_t *occ, double *dist, size_t nvox, hipSt
 hipError_t gtop_launch_esdf_mark(const GtopGrid &g, const double *pts, int npts, uint8_t *occ,
                                  hipStream_t stream);
 // updateESDF3d (sdf_map.cpp:310-368): the three sweeps z, y, x as exact integer minimisations,
-// then res*sqrt(.) into dist (fp64; dist32, an fp32 copy, may be NULL and is since round 4: the fp32 path reads fp32
-// corner records).  tmp1/tmp2: nvox int32 each.
+// then res*sqrt(.) into dist, in fp64 only (the fp32 path reads fp32 corner records, which gtop_records.hip makes from
+// dist).  tmp1/tmp2: nvox int32 each.
 bool gtop_esdf_supported(const GtopGrid &g);
 size_t gtop_esdf_rows_ints(const GtopGrid &g);   // ints of row workspace the builder needs
 hipError_t gtop_launch_esdf_build(const GtopGrid &g, const uint8_t *occ, int *tmp1, int *tmp2, int *rows,
-                                  double *dist, float *dist32, hipStream_t stream);
+                                  double *dist, hipStream_t stream);
 // The signed field (gtop_set_field_sign): the distance field above at free voxels; at occupied ones
 // max(-max_depth, res - res*sqrt(n)), n the squared voxel distance to the nearest free voxel (-max_depth if none).
 // Two transforms over the same workspaces.
 hipError_t gtop_launch_esdf_build_signed(const GtopGrid &g, const uint8_t *occ, int *tmp1, int *tmp2, int *rows,
-                                         double *dist, float *dist32, double max_depth, hipStream_t stream);
+                                         double *dist, double max_depth, hipStream_t stream);
 
 // the local update of compare2.cpp:147-152 (gtop_esdf_window.hip): resetBuffer(min, max) over the inclusive voxel box
 // lo .. hi, and updateESDF3d over the same box (sdf_map.cpp:28-53, :310-368)
