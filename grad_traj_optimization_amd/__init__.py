@@ -10,8 +10,8 @@ There is no CPU fallback: importing works anywhere (so the build and the
 symbol check can run on a CPU box), but creating a context without a gfx950
 device raises.
 """
-from ._lib import (GTOP_F32, GTOP_F64, GtopError, GtopLimits, GtopParams, OPTI_NODE_PARAMS,
+from ._lib import (GTOP_F32, GTOP_F64, GtopError, GtopLimits, GtopParams, GtopRetime, OPTI_NODE_PARAMS,
                    GtopContext, GtopGroup, Rendezvous, box_polynomial_centres, library_path, load_library)
 
-__all__ = ["GTOP_F32", "GTOP_F64", "GtopError", "GtopLimits", "GtopParams", "OPTI_NODE_PARAMS",
+__all__ = ["GTOP_F32", "GTOP_F64", "GtopError", "GtopLimits", "GtopParams", "GtopRetime", "OPTI_NODE_PARAMS",
            "GtopContext", "GtopGroup", "Rendezvous", "box_polynomial_centres", "library_path", "load_library"]

@@ -55,6 +55,21 @@ class GtopLimits(C.Structure):
                          int(bool(use_boxes)))
 
 
+class GtopRetime(C.Structure):
+    """gtop_retime of include/gtop.h: how reallocate_times[_device] forms the new segment times.  mode 0 (LENGTH):
+    length / mean_v of the waypoints as they stand in x, init_time on the first and last segment; mode 1 (LIMITS): the
+    segments whose figure in the segment report breaks max_vel / max_acc are stretched."""
+    LENGTH, LIMITS = 0, 1
+    _fields_ = [("mode", C.c_int32), ("mean_v", C.c_double), ("init_time", C.c_double), ("max_vel", C.c_double),
+                ("max_acc", C.c_double), ("per_axis", C.c_int32), ("uniform", C.c_int32), ("scale_x", C.c_int32),
+                ("max_ratio", C.c_double)]
+
+    def __init__(self, mode=0, mean_v=1.8, init_time=0.3, max_vel=0.0, max_acc=0.0, per_axis=False, uniform=False,
+                 scale_x=False, max_ratio=4.0):
+        super().__init__(int(mode), float(mean_v), float(init_time), float(max_vel), float(max_acc), int(bool(per_axis)),
+                         int(bool(uniform)), int(bool(scale_x)), float(max_ratio))
+
+
 def library_path():
     return _SO
 
@@ -137,6 +152,13 @@ def load_library():
         "gtop_select_best_device": (C.c_int, [vp, C.c_int, vp, vp, C.POINTER(GtopLimits), vp, vp, vp]),
         "gtop_validate_batch": (C.c_int, [vp, C.c_int, dp, C.c_double, C.POINTER(GtopLimits), dp, dp,
                                           C.POINTER(C.c_ubyte), C.POINTER(C.c_int32)]),
+        "gtop_validate_segments_device": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_double,
+                                                    C.POINTER(GtopLimits), vp, vp]),
+        "gtop_validate_segments": (C.c_int, [vp, C.c_int, dp, C.c_double, C.POINTER(GtopLimits), dp]),
+        "gtop_reallocate_times_device": (C.c_int, [vp, C.POINTER(GtopRetime), C.c_int, C.c_int, vp, vp, vp, C.c_int, vp,
+                                                   vp, vp]),
+        "gtop_reallocate_times": (C.c_int, [vp, C.POINTER(GtopRetime), C.c_int, dp, C.c_double, C.POINTER(GtopLimits),
+                                            dp]),
         "gtop_default_bounds": (C.c_int, [C.c_int, C.c_int, dp, C.c_double, C.c_double, C.c_double, dp, dp]),
         "gtop_optimize_batch": (C.c_int, [vp, C.c_int, dp, dp, dp, C.c_int, dp]),
         "gtop_optimize_device": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp, C.c_int, vp, vp]),
@@ -201,7 +223,9 @@ def load_library():
              "gtop_set_start_times_device": 4, "gtop_validate_trajectories_device": 5, "gtop_select_best_device": 5,
              "gtop_validate_batch": 5, "gtop_set_gradient_mode": 6, "gtop_get_gradient_mode": 6,
              "gtop_group_set_gradient_mode": 6, "gtop_set_moving_box_polynomials": 7, "gtop_get_moving_box_kind": 7,
-             "gtop_box_polynomial_centres": 7, "gtop_min_jerk_start_device": 8, "gtop_min_jerk_start": 8}
+             "gtop_box_polynomial_centres": 7, "gtop_min_jerk_start_device": 8, "gtop_min_jerk_start": 8,
+             "gtop_validate_segments_device": 9, "gtop_validate_segments": 9, "gtop_reallocate_times_device": 9,
+             "gtop_reallocate_times": 9}
     L.gtop_abi_version.restype = C.c_int
     abi = L.gtop_abi_version() if os.environ.get("GTOP_HIP_LIB") else max(since.values())
     for name, (res, args) in sig.items():
@@ -796,6 +820,77 @@ class GtopContext:
                                                   C.byref(limits), C.c_void_p(ok.data_ptr()) if want_pass else None,
                                                   C.c_void_p(best.data_ptr()), C.c_void_p(stream)))
         return ok, best
+
+    # -- per-segment report and segment-time reallocation (include/gtop.h) --
+    SEG_REPORT = ("n_samples", "first_sample", "clearance", "clearance_t", "n_below_margin", "n_out_of_map",
+                  "max_vel_norm", "max_acc_norm", "max_vel_axis", "max_acc_axis")
+
+    def validate_segments(self, x, limits, dt_sample=0.01):
+        """The per-segment report (B, m, 10) of the context's problem at free variables x (B, n): the samples and
+        distances of validate_batch, reduced per segment (the columns of SEG_REPORT)."""
+        x = _f64(x)
+        B = x.shape[0]
+        seg = np.empty((B, self.m, len(self.SEG_REPORT)))
+        self._chk(self._L.gtop_validate_segments(self._h, B, _p(x), float(dt_sample), C.byref(limits), _p(seg)))
+        return seg
+
+    def validate_segments_device(self, coeff, T, limits, dt_sample=0.01, seg_report=None, stream=None):
+        """torch fp64 CUDA tensors coeff (B, m, 18), T (B, m) or (m,) -> seg_report (B, m, 10); asynchronous,
+        capturable (pass `seg_report` to write into a buffer of the caller's)."""
+        import torch
+        assert coeff.is_cuda and coeff.dtype == T.dtype == torch.float64 and coeff.is_contiguous() and T.is_contiguous()
+        B, m = coeff.shape[0], coeff.shape[1]
+        assert T.shape == (m,) or T.shape == (B, m)
+        if seg_report is None:
+            seg_report = torch.empty(B, m, len(self.SEG_REPORT), dtype=torch.float64, device=coeff.device)
+        assert seg_report.is_cuda and seg_report.is_contiguous() and seg_report.dtype == torch.float64
+        assert seg_report.numel() == B * m * len(self.SEG_REPORT)
+        if stream is None:
+            stream = torch.cuda.current_stream(coeff.device).cuda_stream
+        self._chk(self._L.gtop_validate_segments_device(self._h, B, m, C.c_void_p(coeff.data_ptr()),
+                                                        C.c_void_p(T.data_ptr()), m if T.dim() == 2 else 0,
+                                                        float(dt_sample), C.byref(limits),
+                                                        C.c_void_p(seg_report.data_ptr()), C.c_void_p(stream)))
+        return seg_report
+
+    def reallocate_times(self, x, options, limits=None, dt_sample=0.01):
+        """New segment times (B, m) for the first B rows of the context's problem at free variables x (B, n), by
+        `options` (a GtopRetime).  LIMITS forms the segment report itself from `limits` and dt_sample; LENGTH ignores
+        both.  Returns (T_out, x): x is a copy, rescaled under scale_x.  The context's problem is not changed: pass
+        T_out to set_problem."""
+        x = _f64(x).copy()
+        B = x.shape[0]
+        T_out = np.empty((B, self.m))
+        if limits is None:
+            limits = GtopLimits()
+        self._chk(self._L.gtop_reallocate_times(self._h, C.byref(options), B, _p(x), float(dt_sample), C.byref(limits),
+                                                _p(T_out)))
+        return T_out, x
+
+    def reallocate_times_device(self, options, x=None, Df=None, T=None, seg_report=None, T_out=None, stream=None):
+        """torch fp64 CUDA tensors -> T_out (B, m); asynchronous, capturable.  LENGTH reads x (B, n) and Df (B, 18);
+        LIMITS reads T (B, m) or (m,) and seg_report (B, m, 10) and, under scale_x, rescales x in place.  T_out may be
+        T itself when T is (B, m)."""
+        import torch
+        given = [t for t in (x, Df, T, seg_report, T_out) if t is not None]
+        for t in given:
+            assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float64
+        if x is not None:
+            B, m = x.shape[0], x.shape[1] // 9 + 1
+        else:
+            B, m = seg_report.shape[0], seg_report.shape[1]
+        stride = m if (T is None or T.dim() == 2) else 0
+        if T_out is None:
+            T_out = torch.empty(B, m, dtype=torch.float64, device=given[0].device)
+        assert T_out.numel() == B * m
+        if stream is None:
+            stream = torch.cuda.current_stream(T_out.device).cuda_stream
+        elif hasattr(stream, "cuda_stream"):
+            stream = stream.cuda_stream
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        self._chk(self._L.gtop_reallocate_times_device(self._h, C.byref(options), B, m, ptr(x), ptr(Df), ptr(T), stride,
+                                                       ptr(seg_report), ptr(T_out), C.c_void_p(stream)))
+        return T_out
 
     # -- batched optimizer --
     @staticmethod

@@ -147,6 +147,66 @@ bool GradTrajOptimizer::validateTrajectory(const Limits &limits, Report *report)
   return pass != 0;
 }
 
+bool GradTrajOptimizer::segmentReport(const Limits &limits, std::vector<SegmentReport> *rows) {
+  if (!ctx_ || m_ < 2 || dp_.empty()) {
+    last_status_ = GTOP_ERR_STATE;
+    return false;
+  }
+  gtop_limits lim{};
+  lim.margin = limits.margin;
+  lim.use_boxes = limits.use_boxes;
+  std::vector<double> r((size_t)m_ * GTOP_SEG_REPORT);
+  last_status_ = gtop_validate_segments(ctx_, 1, dp_.data(), limits.dt_sample, &lim, r.data());
+  if (last_status_ != GTOP_OK) return false;
+  if (rows) {
+    rows->resize(m_);
+    for (int s = 0; s < m_; ++s) {
+      const double *q = &r[(size_t)s * GTOP_SEG_REPORT];
+      SegmentReport &o = (*rows)[s];
+      o.n_samples = (int)q[0];
+      o.first_sample = (int)q[1];
+      o.clearance = q[2];
+      o.clearance_time = q[3];
+      o.n_below_margin = (int)q[4];
+      o.n_out_of_map = (int)q[5];
+      o.max_vel_norm = q[6];
+      o.max_acc_norm = q[7];
+      o.max_vel_axis = q[8];
+      o.max_acc_axis = q[9];
+    }
+  }
+  return true;
+}
+
+bool GradTrajOptimizer::reallocateSegmentTime(const RetimeOptions &options) {
+  if (!ctx_ || m_ < 2 || dp_.empty()) {
+    last_status_ = GTOP_ERR_STATE;
+    return false;
+  }
+  gtop_retime opt{};
+  opt.mode = options.mode;
+  opt.mean_v = options.mean_v < 0.0 ? cfg_.mean_v : options.mean_v;
+  opt.init_time = options.init_time < 0.0 ? cfg_.init_time : options.init_time;
+  opt.max_vel = options.max_vel;
+  opt.max_acc = options.max_acc;
+  opt.per_axis = options.per_axis;
+  opt.uniform = options.uniform;
+  opt.scale_x = options.scale_x;
+  opt.max_ratio = options.max_ratio;
+  gtop_limits lim{};
+  lim.margin = options.report.margin;
+  lim.use_boxes = options.report.use_boxes;
+  std::vector<double> T(m_), x = dp_;
+  last_status_ = gtop_reallocate_times(ctx_, &opt, 1, x.data(), options.report.dt_sample, &lim, T.data());
+  if (last_status_ != GTOP_OK) return false;
+  last_status_ = gtop_set_problem(ctx_, 1, m_, T.data(), m_, df_.data());   // (refuses a time that is not > 0)
+  if (last_status_ != GTOP_OK) return false;
+  segment_time_ = T;
+  dp_ = x;
+  coefficientsFromDerivatives(dp_);
+  return true;
+}
+
 // Common tail of setPath / setKinoPath: Df, Dp (getInitialD,
 // src/qp_generator.cpp:407-451), initial coefficients (Px = A^-1 Dx,
 // :334-336 / :134-136), then the problem goes to the device.
@@ -307,7 +367,12 @@ bool GradTrajOptimizer::optimizeTrajectory(int step) {
     last_evals_ = r.nevals;
   }
   dp_ = x;                        // :202-207
-  coefficientsFromDerivatives(x);  // :230
+  if (cfg_.reallocate_time == 1) {   // :209-227, the block the reference carries commented out
+    RetimeOptions length;
+    length.mode = GTOP_RETIME_LENGTH;
+    if (!reallocateSegmentTime(length)) return true;   // (:242 — always true; ok() tells)
+  }
+  coefficientsFromDerivatives(x);  // :230 — with the new times where they were reallocated
   if (step == 1 || step == 2) {   // :233-240
     int64_t it = 0;
     double tt = 0;

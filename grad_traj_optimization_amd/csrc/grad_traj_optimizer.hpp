@@ -79,6 +79,12 @@ class GradTrajOptimizer {
     // accelerations replaced by the minimiser of the smoothness term (include/gtop.h, gtop_min_jerk_start: the
     // reference's type == 1, src/qp_generator.cpp:242-315), the coefficients refreshed from it
     int initial_guess = 0;
+    // 1: optimizeTrajectory reallocates the segment times behind the solve, where the reference carries the block
+    // commented out (:209-227): segment_time(i) = the distance between waypoints i and i + 1 as the optimizer left
+    // them / mean_v, plus init_time on the first and the last segment (include/gtop.h, GTOP_RETIME_LENGTH).  The
+    // coefficients getCoefficient returns afterwards are those of the NEW times (the block sits in front of :230), and
+    // the next optimizeTrajectory runs on them.  0 (default): the times of setPath / setKinoPath stand, as shipped.
+    int reallocate_time = 0;
   };
 
   GradTrajOptimizer();
@@ -133,6 +139,31 @@ class GradTrajOptimizer {
     double max_vel_norm = 0.0, max_acc_norm = 0.0, max_vel_axis = 0.0, max_acc_axis = 0.0, time_sum = 0.0;
   };
   bool validateTrajectory(const Limits &limits, Report *report = nullptr);
+
+  // The same figures per SEGMENT (include/gtop.h, gtop_validate_segments): rows->at(s) covers the getTraj samples that
+  // fall into segment s; of `limits` margin, use_boxes and dt_sample are read.  false when the call fails.
+  struct SegmentReport {
+    int n_samples = 0, first_sample = -1;         // a segment without samples: 0, -1, clearance +inf, time -1, zeros
+    double clearance = 0.0, clearance_time = -1.0;
+    int n_below_margin = 0, n_out_of_map = 0;
+    double max_vel_norm = 0.0, max_acc_norm = 0.0, max_vel_axis = 0.0, max_acc_axis = 0.0;
+  };
+  bool segmentReport(const Limits &limits, std::vector<SegmentReport> *rows);
+  // New segment times from the trajectory at the current Dp (include/gtop.h, gtop_reallocate_times): by waypoint
+  // distance (GTOP_RETIME_LENGTH, the reference's commented block :209-227; mean_v / init_time < 0: the Config's) or by
+  // stretching the segments whose velocity / acceleration breaks max_vel / max_acc (GTOP_RETIME_LIMITS; the report
+  // is formed with `report`'s margin, use_boxes and dt_sample).  The new times become the object's segment_time — what
+  // getSegmentTime returns and the next optimizeTrajectory runs on —, Dp is rescaled under scale_x, the coefficients
+  // are refreshed.  false, and nothing changed, when the call fails.
+  struct RetimeOptions {
+    int mode = GTOP_RETIME_LIMITS;
+    double mean_v = -1.0, init_time = -1.0;
+    double max_vel = 0.0, max_acc = 0.0;
+    bool per_axis = false, uniform = false, scale_x = false;
+    double max_ratio = 4.0;
+    Limits report;
+  };
+  bool reallocateSegmentTime(const RetimeOptions &options);
 
   // extras (not in the reference)
   bool ok() const { return ctx_ != nullptr && last_status_ == GTOP_OK; }

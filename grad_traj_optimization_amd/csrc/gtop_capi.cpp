@@ -7,7 +7,8 @@
 
 #include "gtop_ctx.h"
 
-#define GTOP_ABI_VERSION 8   // 8: gtop_min_jerk_start_device, gtop_min_jerk_start
+#define GTOP_ABI_VERSION 9   // 9: gtop_validate_segments[_device], gtop_reallocate_times[_device]
+                             // 8: gtop_min_jerk_start_device, gtop_min_jerk_start
                              // 7: gtop_set_moving_box_polynomials, gtop_get_moving_box_kind, gtop_box_polynomial_centres
                              // 6: gtop_set_gradient_mode, gtop_get_gradient_mode, gtop_group_set_gradient_mode
                              // 5: gtop_validate_trajectories_device, gtop_select_best_device, gtop_validate_batch

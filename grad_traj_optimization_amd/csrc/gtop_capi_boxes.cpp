@@ -365,4 +365,129 @@ int gtop_validate_batch(gtop_ctx *c, int B, const double *x, double dt_sample, c
   return GTOP_OK;
 } GTOP_CATCH_STATUS(c)
 
+// ---- per-segment report (gtop_segments.hip) and segment-time reallocation (gtop_retime.hip) ----
+static int segments_on_stream(gtop_ctx *c, int B, int m, const void *d_coeff, const void *d_T, int time_stride,
+                              double dt_sample, const gtop_limits *lim, void *d_seg, hipStream_t s, int problem_B) {
+  if (int rc = validate_ready(c, B, m, time_stride, dt_sample, lim, problem_B)) return rc;
+  const bool boxes = lim->use_boxes != 0;
+  if (B == 0) return GTOP_OK;
+  if (!d_coeff || !d_T || !d_seg) return fail(c, GTOP_ERR_INVALID, "validate_segments: NULL buffer");
+  HIPCHK(c, hipSetDevice(c->device));
+  const double *t0 = (boxes && c->t0_count > 0) ? c->t0_dev : nullptr;
+  HIPCHK(c, gtop_launch_traj_segments(c->field.grid, c->field.rec64.data(), box_list(c, boxes ? c->nbox : 0), B, m,
+                                      static_cast<const double *>(d_coeff), static_cast<const double *>(d_T), time_stride,
+                                      dt_sample, t0, c->t0_count > 1 ? 1 : 0, lim->margin, static_cast<double *>(d_seg), s));
+  return GTOP_OK;
+}
+
+int gtop_validate_segments_device(gtop_ctx *c, int B, int m, const void *d_coeff, const void *d_T, int time_stride,
+                                  double dt_sample, const gtop_limits *limits, void *d_seg_report, void *hip_stream) try {
+  if (!c) return GTOP_ERR_INVALID;
+  return segments_on_stream(c, B, m, d_coeff, d_T, time_stride, dt_sample, limits, d_seg_report,
+                            static_cast<hipStream_t>(hip_stream), 0);
+} GTOP_CATCH_STATUS(c)
+
+// x of the problem's first B rows -> d_x -> coefficients (scratch) -> the segment report in seg_rep; no synchronisation
+static int segments_staged(gtop_ctx *c, int B, const double *x, double dt_sample, const gtop_limits *limits) {
+  const int m = c->m;
+  const size_t n = 9 * (size_t)(m - 1), ncoef = (size_t)B * m * 18;
+  HIPCHK(c, c->mma_g.reserve(ncoef > (size_t)B * n ? ncoef : (size_t)B * n));   // coefficient scratch
+  HIPCHK(c, c->seg_rep.reserve((size_t)B * m * (GTOP_SEG_REPORT + 1)));         // report | T_out
+  HIPCHK(c, hipMemcpyAsync(c->d_x.data(), x, (size_t)B * n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  if (int rc = gtop_coefficients_device(c, B, m, c->d_x.data(), c->d_Df.data(), c->d_T.data(), c->t_stride, c->mma_g.data(),
+                                        c->stream))
+    return rc;
+  return segments_on_stream(c, B, m, c->mma_g.data(), c->d_T.data(), c->t_stride, dt_sample, limits, c->seg_rep.data(),
+                            c->stream, c->B);
+}
+
+int gtop_validate_segments(gtop_ctx *c, int B, const double *x, double dt_sample, const gtop_limits *limits,
+                           double *seg_report) try {
+  if (!c) return GTOP_ERR_INVALID;
+  if (c->B == 0) return fail(c, GTOP_ERR_STATE, "gtop_set_problem / gtop_set_paths has not been called");
+  if (B < 1 || B > c->B || !x || !seg_report)
+    return fail(c, GTOP_ERR_INVALID, "validate_segments: 1 <= B <= problem batch, x and seg_report required");
+  int rc = validate_ready(c, B, c->m, c->t_stride, dt_sample, limits, c->B);   // (before anything is staged)
+  if (rc) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  if ((rc = segments_staged(c, B, x, dt_sample, limits))) return rc;
+  HIPCHK(c, hipMemcpyAsync(seg_report, c->seg_rep.data(), (size_t)B * c->m * GTOP_SEG_REPORT * sizeof(double),
+                           hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return GTOP_OK;
+} GTOP_CATCH_STATUS(c)
+
+// the rules of a gtop_retime, before anything is staged or launched
+static int check_retime(gtop_ctx *c, const gtop_retime *o) {
+  if (!o) return fail(c, GTOP_ERR_INVALID, "reallocate_times: options is NULL");
+  if (o->mode == GTOP_RETIME_LENGTH) {
+    if (!(o->mean_v > 0.0) || !std::isfinite(o->mean_v) || !(o->init_time >= 0.0) || !std::isfinite(o->init_time))
+      return fail(c, GTOP_ERR_INVALID, "reallocate_times: LENGTH needs a finite mean_v > 0 and a finite init_time >= 0");
+  } else if (o->mode == GTOP_RETIME_LIMITS) {
+    if (!(o->max_ratio >= 1.0) || !std::isfinite(o->max_ratio))
+      return fail(c, GTOP_ERR_INVALID, "reallocate_times: LIMITS needs a finite max_ratio >= 1");
+  } else {
+    return fail(c, GTOP_ERR_INVALID, "reallocate_times: unknown mode");
+  }
+  return GTOP_OK;
+}
+
+int gtop_reallocate_times_device(gtop_ctx *c, const gtop_retime *opt, int B, int m, void *d_x, const void *d_Df,
+                                 const void *d_T, int time_stride, const void *d_seg_report, void *d_T_out,
+                                 void *hip_stream) try {
+  if (!c) return GTOP_ERR_INVALID;
+  if (int rc = check_retime(c, opt)) return rc;
+  if (B < 0 || m < 2 || m > 227 || (time_stride != 0 && time_stride != m))
+    return fail(c, GTOP_ERR_INVALID, "reallocate_times: need B >= 0, 2 <= m <= 227, time_stride in {0, m}");
+  if (B == 0) return GTOP_OK;
+  hipStream_t s = static_cast<hipStream_t>(hip_stream);
+  double *T_out = static_cast<double *>(d_T_out);
+  if (opt->mode == GTOP_RETIME_LENGTH) {
+    if (!d_x || !d_Df || !d_T_out) return fail(c, GTOP_ERR_INVALID, "reallocate_times: NULL buffer (LENGTH: x, Df, T_out)");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, gtop_launch_retime_length(B, m, static_cast<const double *>(d_x), static_cast<const double *>(d_Df),
+                                        opt->mean_v, opt->init_time, T_out, s));
+    return GTOP_OK;
+  }
+  if (!d_T || !d_seg_report || !d_T_out || (opt->scale_x && !d_x))
+    return fail(c, GTOP_ERR_INVALID, "reallocate_times: NULL buffer (LIMITS: T, seg_report, T_out; x with scale_x)");
+  if (d_T_out == d_T && time_stride == 0 && B > 1)
+    return fail(c, GTOP_ERR_INVALID, "reallocate_times: a shared time vector cannot be its own per-trajectory output");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, gtop_launch_retime_limits(B, m, static_cast<double *>(d_x), static_cast<const double *>(d_T), time_stride,
+                                      static_cast<const double *>(d_seg_report), opt->max_vel, opt->max_acc,
+                                      opt->max_ratio, opt->per_axis != 0, opt->uniform != 0, opt->scale_x != 0, T_out, s));
+  return GTOP_OK;
+} GTOP_CATCH_STATUS(c)
+
+int gtop_reallocate_times(gtop_ctx *c, const gtop_retime *opt, int B, double *x, double dt_sample,
+                          const gtop_limits *limits, double *T_out) try {
+  if (!c) return GTOP_ERR_INVALID;
+  if (c->B == 0) return fail(c, GTOP_ERR_STATE, "gtop_set_problem / gtop_set_paths has not been called");
+  int rc = check_retime(c, opt);
+  if (rc) return rc;
+  if (B < 1 || B > c->B || !x || !T_out)
+    return fail(c, GTOP_ERR_INVALID, "reallocate_times: 1 <= B <= problem batch, x and T_out required");
+  const int m = c->m;
+  const size_t n = 9 * (size_t)(m - 1), nT = (size_t)B * m;
+  const bool limits_mode = opt->mode == GTOP_RETIME_LIMITS;
+  if (limits_mode && (rc = validate_ready(c, B, m, c->t_stride, dt_sample, limits, c->B))) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (limits_mode) {
+    if ((rc = segments_staged(c, B, x, dt_sample, limits))) return rc;
+  } else {
+    HIPCHK(c, c->seg_rep.reserve(nT * (GTOP_SEG_REPORT + 1)));
+    HIPCHK(c, hipMemcpyAsync(c->d_x.data(), x, (size_t)B * n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  }
+  double *d_seg = c->seg_rep.data(), *d_Tout = d_seg + nT * GTOP_SEG_REPORT;
+  if ((rc = gtop_reallocate_times_device(c, opt, B, m, c->d_x.data(), c->d_Df.data(), c->d_T.data(), c->t_stride, d_seg,
+                                         d_Tout, c->stream)))
+    return rc;
+  HIPCHK(c, hipMemcpyAsync(T_out, d_Tout, nT * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (limits_mode && opt->scale_x)
+    HIPCHK(c, hipMemcpyAsync(x, c->d_x.data(), (size_t)B * n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return GTOP_OK;
+} GTOP_CATCH_STATUS(c)
+
 }  // extern "C"

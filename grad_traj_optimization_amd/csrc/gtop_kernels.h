@@ -223,4 +223,21 @@ hipError_t gtop_launch_select_best(int B, const double *report, const double *co
                                    int per_axis, int allow_out_of_map, unsigned char *pass, int *best, void *workspace,
                                    hipStream_t stream);
 
+// ---- per-segment report (gtop_segments.hip) and segment-time reallocation (gtop_retime.hip), fp64 ------------
+#define GTOP_SEG_REPORT 10   // = include/gtop.h
+// seg_report[b][s] of the trajectories (coeff, T) as include/gtop.h lays it out: traj_report_kernel's samples, segments
+// and distances, reduced per segment; one wavefront per trajectory, both list kinds, any number of boxes
+hipError_t gtop_launch_traj_segments(const GtopGrid &g, const double *rec, const GtopBoxList &boxes, int B, int m,
+                                     const double *coeff, const double *T, int t_stride, double dt_sample,
+                                     const double *t0, int t0_stride, double margin, double *seg_report,
+                                     hipStream_t stream);
+// T_out [B][m] = length / mean_v of the waypoints as they stand in x and Df, init_time on the first and last segment
+hipError_t gtop_launch_retime_length(int B, int m, const double *x, const double *Df, double mean_v, double init_time,
+                                     double *T_out, hipStream_t stream);
+// T_out [B][m] = ratio_s T[s] from the segment report's velocity / acceleration figures; scale_x: the interior
+// velocities and accelerations of x divided by rho_k, rho_k^2 in place (x may be NULL otherwise)
+hipError_t gtop_launch_retime_limits(int B, int m, double *x, const double *T, int t_stride, const double *seg_report,
+                                     double max_vel, double max_acc, double max_ratio, int per_axis, int uniform,
+                                     int scale_x, double *T_out, hipStream_t stream);
+
 #endif  // GTOP_KERNELS_H_

@@ -85,7 +85,9 @@ const char *gtop_last_error(const gtop_ctx *ctx);
  * gtop_set_gradient_mode / gtop_get_gradient_mode / gtop_group_set_gradient_mode;
  * 7: the polynomial box list, gtop_set_moving_box_polynomials /
  * gtop_get_moving_box_kind / gtop_box_polynomial_centres; 8: the minimum-jerk
- * start point, gtop_min_jerk_start_device / gtop_min_jerk_start;
+ * start point, gtop_min_jerk_start_device / gtop_min_jerk_start; 9: the
+ * per-segment report and segment-time reallocation,
+ * gtop_validate_segments[_device] / gtop_reallocate_times[_device];
  * nothing of an earlier version changed meaning). */
 int gtop_abi_version(void);
 
@@ -776,6 +778,125 @@ int gtop_select_best_device(gtop_ctx *ctx, int B, const void *d_report, const vo
 int gtop_validate_batch(gtop_ctx *ctx, int B, const double *x, double dt_sample,
                         const gtop_limits *limits, const double *cost, double *report,
                         unsigned char *pass, int32_t best[2]);
+
+/* ---- per-segment trajectory report ------------------------------------- */
+/* (Not a PolynomialTraj method.)  The report above says THAT a row fails and names
+ * its sample of least clearance; a row that is too fast or too close in several
+ * places needs the figures per SEGMENT, the unit a caller can act on: insert a
+ * waypoint, or stretch a time (below).  The samples, the segment each one belongs
+ * to, positions, velocities, accelerations and distances are exactly those of
+ * gtop_validate_trajectories_device: the accumulated eval_t, the walk
+ * `while (idx < m-1 && ts[idx] <= t)` of PolynomialTraj::evaluate
+ * (polynomial_traj.hpp:48-51) with the last segment extended, and the
+ * interpolating lookup at tau = t0[b] + eval_t with use_boxes, -1 otherwise — both
+ * kinds of box list, any number of boxes, a signed field as it is, the start-time
+ * rules of gtop_set_start_times[_device].  Of `limits` only margin and use_boxes
+ * are read (the others must still be finite).
+ * seg_report is B x m x GTOP_SEG_REPORT doubles; row [b][s] covers the samples
+ * whose walk ends at idx == s:
+ *   [0] number of samples                        (a segment without samples:  0)
+ *   [1] index of its first sample                                            -1
+ *   [2] clearance: the least distance (an out-of-map sample gives -1)      +inf
+ *   [3] eval_t of the first sample that attains it                           -1
+ *   [4] samples with distance <= margin                                       0
+ *   [5] samples out of the map                                                0
+ *   [6] max ||v||_2   [7] max ||a||_2   over its samples                      0
+ *   [8] max |v_k|     [9] max |a_k|     over its samples and the three axes   0
+ * (a segment time below dt_sample can leave a segment without a sample).  Against
+ * the whole report R of the same inputs, bit for bit: sum_s [0] = R[0]; the [1] of
+ * consecutive non-empty segments advance by [0]; min_s [2] = R[1], and the first
+ * segment attaining it has [3] = R[2] and holds sample R[3]; sum_s [4] = R[4];
+ * sum_s [5] = R[6]; max_s [6..9] = R[7..10].
+ * One wavefront per trajectory (csrc/gtop_segments.hip); every row is written
+ * exactly once; nothing per sample goes to HBM.
+ * The device form only enqueues one launch: no allocation, no synchronisation,
+ * capturable; boxes, start times and the field are read at replay, the list's kind
+ * and length are launch arguments, as for the report.  Errors are those of
+ * gtop_validate_trajectories_device; B = 0 launches nothing.  gtop_validate_segments
+ * serves the first B rows of the context's problem at free variables x
+ * (1 <= B <= the problem's batch), staged as gtop_validate_batch stages.
+ * fp64 only.  The gtop_group_* entry points do not forward it. */
+#define GTOP_SEG_REPORT 10
+int gtop_validate_segments_device(gtop_ctx *ctx, int B, int m, const void *d_coeff,
+                                  const void *d_T, int time_stride, double dt_sample,
+                                  const gtop_limits *limits, void *d_seg_report,
+                                  void *hip_stream);
+int gtop_validate_segments(gtop_ctx *ctx, int B, const double *x, double dt_sample,
+                           const gtop_limits *limits, double *seg_report);
+
+/* ---- segment-time reallocation ----------------------------------------- */
+/* Segment times are length / mean_v of the straight-line path
+ * (src/grad_traj_optimizer.cpp:73-81) and never change afterwards: a candidate the
+ * optimizer has bent around an obstacle keeps the times of the path it no longer
+ * follows, and one that breaks max_vel / max_acc can only be discarded.  The
+ * reference has the remedy written down and switched off: the commented block
+ * "reallocate segment time" behind the solve (src/grad_traj_optimizer.cpp:209-227).
+ *
+ * GTOP_RETIME_LENGTH is that block.  For i = 0 .. m-1, len = the distance between
+ * waypoint positions i and i+1 AS THEY STAND IN x (position 0 is Df[k][0],
+ * position m is Df[k][3], interior position j is x[3(j-1) + k(3m-3)]), formed as
+ * sqrt(dx*dx + dy*dy + dz*dz) unfused, and T_out[i] = len / mean_v, plus init_time
+ * for i == 0 AND i == m-1 — the block's rule (:226); setPath's own condition (:76)
+ * only ever fires on the first segment, so on a straight-line start T_out equals
+ * gtop_setup_paths_device's T but for init_time on the last segment.  Reads x and
+ * Df, writes T_out; d_T and d_seg_report are not read (may be NULL).  mean_v must be
+ * finite and > 0, init_time finite and >= 0.
+ *
+ * GTOP_RETIME_LIMITS stretches the segments that break a limit.  With V, A the
+ * segment report's entries (6, 7), or (8, 9) under per_axis, each step one rounded
+ * IEEE operation, nothing fused:
+ *   rv = max_vel > 0 ? V / max_vel : 0      ra = max_acc > 0 ? sqrt(A / max_acc) : 0
+ *   ratio_s = fmin(fmax(fmax(rv, ra), 1.0), max_ratio)
+ *   uniform:  ratio_s := the largest ratio of the trajectory's segments
+ *   T_out[s] = ratio_s * T[s]
+ *   scale_x:  rho_k = fmax(ratio_{k-1}, ratio_k), k = 1 .. m-1;
+ *             v_k := v_k / rho_k;  a_k := a_k / (rho_k * rho_k)     (in x, in place)
+ * Times only grow; a segment within its limits keeps its bits, and so does a
+ * junction with rho_k == 1.  Positions and Df are never written: the boundary
+ * state is the caller's.  With uniform and scale_x on a rest-to-rest row (zero
+ * boundary velocity and acceleration) the result is exactly the old curve flown
+ * lambda times slower, p'(t) = p(t / lambda): velocities fall by lambda,
+ * accelerations by lambda^2.  Otherwise the result is a new problem (x, T_out) to
+ * re-optimise or to hand to gtop_min_jerk_start_device: a remedy, not a guarantee.
+ * The loop is report -> reallocate -> optimise -> report:
+ *   gtop_coefficients_device, gtop_validate_segments_device,
+ *   gtop_reallocate_times_device, [gtop_min_jerk_start_device,]
+ *   gtop_optimize_device_ex on (x, T_out), gtop_coefficients_device,
+ *   gtop_validate_trajectories_device, gtop_select_best_device
+ * — all on one stream, capturable as one graph.  max_ratio must be finite and >= 1;
+ * a max_vel / max_acc <= 0 (or NaN) switches that limit off.
+ *
+ * One lane per trajectory, O(m) (csrc/gtop_retime.hip).  d_T_out is B x m.
+ * d_T_out == d_T is allowed when time_stride == m (each lane reads a time before it
+ * writes it); any other overlap of the buffers is not allowed.  time_stride == 0
+ * gives per-trajectory output from a shared input.  The device form only enqueues
+ * one launch and can be captured.  GTOP_ERR_INVALID, nothing launched: opt NULL, an
+ * unknown mode, the parameter rules above, B < 0, m outside 2 .. 227, a time_stride
+ * that is neither 0 nor m, and for B > 0 a NULL buffer that the mode reads or
+ * writes (LENGTH: x, Df, T_out; LIMITS: T, seg_report, T_out, and x under scale_x).
+ * B = 0 launches nothing.
+ * gtop_reallocate_times serves the first B rows of the context's problem
+ * (GTOP_ERR_STATE when none is set): LIMITS forms the coefficients and the segment
+ * report itself from x, dt_sample and limits (errors as gtop_validate_segments);
+ * LENGTH ignores both.  x is updated in place under scale_x.  The context's problem
+ * is NOT changed: pass T_out to gtop_set_problem.  fp64 only; not forwarded by
+ * groups. */
+#define GTOP_RETIME_LENGTH 0 /* the reference's commented block, src/grad_traj_optimizer.cpp:209-227 */
+#define GTOP_RETIME_LIMITS 1 /* stretch the segments that break max_vel / max_acc */
+typedef struct {
+  int32_t mode;
+  double mean_v, init_time; /* LENGTH */
+  double max_vel, max_acc;  /* LIMITS; <= 0: that limit is off */
+  int32_t per_axis;         /* LIMITS: entries 8, 9 of the segment report instead of 6, 7 */
+  int32_t uniform;          /* LIMITS: every segment takes the largest ratio of its trajectory */
+  int32_t scale_x;          /* LIMITS: also rescale the interior velocities and accelerations of x, in place */
+  double max_ratio;         /* LIMITS: cap of a segment's stretch, finite and >= 1 */
+} gtop_retime;
+int gtop_reallocate_times_device(gtop_ctx *ctx, const gtop_retime *opt, int B, int m, void *d_x,
+                                 const void *d_Df, const void *d_T, int time_stride,
+                                 const void *d_seg_report, void *d_T_out, void *hip_stream);
+int gtop_reallocate_times(gtop_ctx *ctx, const gtop_retime *opt, int B, double *x,
+                          double dt_sample, const gtop_limits *limits, double *T_out);
 
 /* ---- bookkeeping the reference keeps inside the callback ------------ */
 
