@@ -917,7 +917,12 @@ class GtopContext:
         return x, cost
 
     def optimize_batch_ex(self, x0, lb, ub, max_evals, ftol_rel=0.0, xtol_rel=0.0, maxtime=0.0):
-        """As optimize_batch, with NLopt's other stop rules; returns (x, cost, nevals, code)."""
+        """As optimize_batch, with NLopt's other stop rules; returns (x, cost, nevals, code).
+
+        What lb / ub may hold, per variable (lb <= ub; include/gtop.h): -inf / +inf on either side — the side is
+        open, the variable starts with asymptote width sigma = 1 and its sigma is never clamped to
+        [0.01, 10] (ub - lb); lb == ub — the variable never moves and is returned as given; a start outside the box is
+        clamped into it before the first evaluation.  The returned point lies inside [lb, ub] exactly."""
         x = _f64(x0).copy()
         B = x.shape[0]
         lb, ub = _f64(lb), _f64(ub)

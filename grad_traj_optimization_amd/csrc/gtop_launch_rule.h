@@ -25,7 +25,7 @@ struct GtopEvalPlan {
 };
 // The launch rule.  pinned_spl: 0 = auto, 3 or 6; for_optimizer: the optimizer loop and the evaluations of its
 // multi-launch forms (the same rule with the loop's own switch point to two trajectories per wavefront).  false: the request cannot be served (m < 2, spl 3 with more than 6
-// segments, more segments than one wavefront's LDS holds — 227, in the optimizer loop 118).
+// segments, more segments than one wavefront's LDS holds — past 227, in the optimizer loop past 118).
 bool gtop_eval_plan(int B, int m, size_t elem, int pinned_spl, bool for_optimizer, GtopEvalPlan *plan);
 // the launch rule restricted to the geometries that have a moving-term body; false: none serves the request
 bool gtop_eval_plan_moving(int B, int m, int pinned_spl, bool for_optimizer, GtopEvalPlan *plan);
@@ -41,9 +41,11 @@ GTOP_HD constexpr int gtop_tile_stride(int spl, int nw) { return (nw * (kSamples
 GTOP_HD constexpr int gtop_tile_stride_long(int m) { return ((kSamples / 6) * m) | 1; }
 // rows of the tile (the chunked body sums the cost in registers)
 GTOP_HD constexpr int gtop_tile_rows(bool is_long) { return is_long ? 18 : kRedVals; }
-// rows of the optimizer loop's LDS vectors: n <= 45 resp. 99 variables; the chunked body: n made a multiple of 64
+// rows of the optimizer loop's LDS vectors: n <= 45 resp. 99 variables; the chunked body: n made a multiple of 32 (every
+// access is bounded by n: the padding only keeps the rows whole 256-byte lines apart.  A multiple of 64 put 118 segments — the
+// limit include/gtop.h states — 752 bytes past 160 KiB: refused; with 32 they fit, and 119 and more still do not)
 GTOP_HD constexpr int gtop_mma_rows(int spl, int nt) { return (spl == 6 && nt == 1) ? 128 : 64; }
-GTOP_HD constexpr int gtop_mma_rows_long(int n) { return (n + 63) & ~63; }   // n = 9 (m - 1) free variables
+GTOP_HD constexpr int gtop_mma_rows_long(int n) { return (n + 31) & ~31; }   // n = 9 (m - 1) free variables
 // the gradient rows between the tile and the state: [rounds * 64] <= 128 (the chunked body: one vector)
 GTOP_HD constexpr int gtop_grad_rows(bool is_long, int rows) { return is_long ? rows : 128; }
 // a trajectory's state: Df at kStateVecs * rows, T at kStateVecs * rows + kDfVals; its doubles (up to 12 segments: 18 + m <= 32)

@@ -444,7 +444,19 @@ int gtop_default_bounds(int B, int m, const double *path, double bos,
  * maxtime, :144-148, which is not reproducible).  x: in = start point
  * (:182-187), out = best point found; min_cost: its cost.  fp64.
  * gtop_optimize_batch uses the problem of gtop_set_problem and host buffers;
- * gtop_optimize_device takes device pointers and only enqueues work. */
+ * gtop_optimize_device takes device pointers and only enqueues work.
+ * What lb / ub may hold, per variable (lb <= ub; every entry point below, all three
+ * launch forms and csrc/mma.hpp alike):
+ *  - -inf as lb and/or +inf as ub: the side is open.  A variable with an infinite
+ *    bound on either side starts with asymptote width sigma = 1 (a bounded one with
+ *    (ub - lb) / 2) and its sigma is never clamped to [0.01, 10] (ub - lb).
+ *  - lb == ub: the variable never moves and is returned as given (bit for bit); when
+ *    every variable is fixed the run costs two evaluations under a tolerance (FTOL
+ *    under ftol_rel, XTOL under xtol_rel or both) and max_evals without one.
+ *  - a start point outside the box is clamped into it before the first evaluation
+ *    (NLopt refuses it): the run is the run from the clamped point, bit for bit.
+ * The returned point lies inside [lb, ub] exactly.  Up to 118 segments (one
+ * wavefront's LDS with the optimizer's state); more: GTOP_ERR_INVALID, x untouched. */
 int gtop_optimize_batch(gtop_ctx *ctx, int B, double *x, const double *lb,
                         const double *ub, int max_evals, double *min_cost);
 int gtop_optimize_device(gtop_ctx *ctx, int B, int m, void *d_x,

@@ -84,7 +84,9 @@ def mma_serial(f, x0, lb, ub, max_evals, ftol_rel=0.0, xtol_rel=0.0, full=False)
         if k > 1:
             dx2 = (xcur - xprev) * (xprev - xprevprev)
             gam = np.where(dx2 < 0, 0.7, np.where(dx2 > 0, 1.2, 1.0))
-            sigma = np.clip(sigma * gam, 0.01 * (ub - lb), 10 * (ub - lb))
+            sigma = sigma * gam
+            both = np.isfinite(lb) & np.isfinite(ub)       # an open bound: no clamp, as mma.hpp (inf * 0.01 would make sigma infinite)
+            sigma[both] = np.clip(sigma[both], 0.01 * (ub - lb)[both], 10 * (ub - lb)[both])
     if full:
         return x, minf, trace, nev, code
     return x, minf, trace
