@@ -2,7 +2,7 @@
 
 The product is the C-ABI library ``libgtop_hip.so`` (include/gtop.h) built from
 csrc/ with hipcc for gfx950.  This package is the thin Python host side:
-``_lib`` binds the C-ABI with ctypes, ``GtopContext`` wraps a context, and
+``_abi`` binds the C-ABI with ctypes, ``_lib`` wraps it (``GtopContext``), and
 ``problem`` generates the synthetic inputs of SURVEY.md §8d.  torch is used
 only for device memory, streams and torch.distributed.
 

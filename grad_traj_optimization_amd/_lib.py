@@ -1,241 +1,15 @@
-"""ctypes binding of include/gtop.h (the C-ABI of libgtop_hip.so)."""
+"""ctypes binding of include/gtop.h (the C-ABI of libgtop_hip.so): the classes over the entry points of _abi.py.
+
+A device tensor reaches the library as a raw address, and the library cannot know how long the buffer behind it is.
+So every *_device method states, per tensor, what the entry point reads or writes, and GtopContext._dev refuses
+(ValueError) whatever is not that before anything is called."""
 import ctypes as C
-import os
+import math
 
 import numpy as np
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-# GTOP_HIP_LIB selects another build of the same C-ABI (kernel tuning variants)
-_SO = os.environ.get("GTOP_HIP_LIB") or os.path.join(_HERE, "libgtop_hip.so")
-
-GTOP_F64, GTOP_F32 = 0, 1
-_STATUS = {0: "GTOP_OK", 1: "GTOP_ERR_INVALID", 2: "GTOP_ERR_HIP", 3: "GTOP_ERR_NO_DEVICE",
-           4: "GTOP_ERR_STATE"}
-
-
-class GtopError(RuntimeError):
-    def __init__(self, code, msg=""):
-        self.code = code
-        super().__init__(f"{_STATUS.get(code, code)}: {msg}")
-
-
-class GtopParams(C.Structure):
-    """gtop_params — the ROS parameters the callback reads
-    (src/grad_traj_optimizer.cpp:5-32 of the reference) + step + enable_dyn."""
-    _fields_ = [
-        ("ws", C.c_double), ("wc", C.c_double),
-        ("alpha", C.c_double), ("r", C.c_double), ("d0", C.c_double),
-        ("alpha_v", C.c_double), ("r_v", C.c_double), ("v0", C.c_double),
-        ("alpha_a", C.c_double), ("r_a", C.c_double), ("a0", C.c_double),
-        ("step", C.c_int32), ("enable_dyn", C.c_int32),
-    ]
-
-
-class GtopStop(C.Structure):
-    """gtop_stop — evaluation cap + NLopt's ftol_rel / xtol_rel / maxtime."""
-    _fields_ = [("max_evals", C.c_int32), ("ftol_rel", C.c_double), ("xtol_rel", C.c_double), ("maxtime", C.c_double)]
-
-
-# launch/opti_node.launch:3-28 of the reference — the only parameter set whose
-# names match what the ctor reads.
-OPTI_NODE_PARAMS = dict(ws=1.0, wc=5.0, alpha=10.0, r=0.5, d0=0.8,
-                        alpha_v=0.0, r_v=1.5, v0=2.5, alpha_a=0.0, r_a=1.5, a0=3.5,
-                        step=2, enable_dyn=0)
-
-_lib = None
-
-
-class GtopLimits(C.Structure):
-    """gtop_limits of include/gtop.h: what a trajectory must keep to pass (validate_batch / select_best_device)."""
-    _fields_ = [("margin", C.c_double), ("max_vel", C.c_double), ("max_acc", C.c_double), ("per_axis", C.c_int32),
-                ("allow_out_of_map", C.c_int32), ("use_boxes", C.c_int32)]
-
-    def __init__(self, margin=0.0, max_vel=0.0, max_acc=0.0, per_axis=False, allow_out_of_map=False, use_boxes=False):
-        super().__init__(float(margin), float(max_vel), float(max_acc), int(bool(per_axis)), int(bool(allow_out_of_map)),
-                         int(bool(use_boxes)))
-
-
-class GtopRetime(C.Structure):
-    """gtop_retime of include/gtop.h: how reallocate_times[_device] forms the new segment times.  mode 0 (LENGTH):
-    length / mean_v of the waypoints as they stand in x, init_time on the first and last segment; mode 1 (LIMITS): the
-    segments whose figure in the segment report breaks max_vel / max_acc are stretched."""
-    LENGTH, LIMITS = 0, 1
-    _fields_ = [("mode", C.c_int32), ("mean_v", C.c_double), ("init_time", C.c_double), ("max_vel", C.c_double),
-                ("max_acc", C.c_double), ("per_axis", C.c_int32), ("uniform", C.c_int32), ("scale_x", C.c_int32),
-                ("max_ratio", C.c_double)]
-
-    def __init__(self, mode=0, mean_v=1.8, init_time=0.3, max_vel=0.0, max_acc=0.0, per_axis=False, uniform=False,
-                 scale_x=False, max_ratio=4.0):
-        super().__init__(int(mode), float(mean_v), float(init_time), float(max_vel), float(max_acc), int(bool(per_axis)),
-                         int(bool(uniform)), int(bool(scale_x)), float(max_ratio))
-
-
-def library_path():
-    return _SO
-
-
-def _preload_torch_hip_runtime():
-    """One process must hold ONE HIP runtime.  The PyTorch-ROCm wheel bundles
-    its own libamdhip64.so (SONAME libamdhip64.so.7, the name libgtop_hip.so
-    needs): if libgtop_hip.so were loaded first it would pull /opt/rocm's copy,
-    a later `import torch` would add the bundled one, and whichever initialises
-    second sees "no ROCm-capable device".  So when torch is installed, map its
-    copy first (by path, without importing torch); the loader then resolves our
-    NEEDED entry to it by SONAME, and torch finds it already loaded."""
-    import importlib.util
-    try:
-        spec = importlib.util.find_spec("torch")
-    except (ImportError, ValueError):
-        spec = None
-    if spec is None or not spec.submodule_search_locations:
-        return
-    cand = os.path.join(list(spec.submodule_search_locations)[0], "lib", "libamdhip64.so")
-    if os.path.exists(cand):
-        C.CDLL(cand, mode=C.RTLD_GLOBAL)
-
-
-def load_library():
-    """Load libgtop_hip.so.  Raises (never falls back) if it is missing."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(_SO):
-        raise ImportError(
-            f"{_SO} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-            "or `make -C grad_traj_optimization_amd/csrc` — there is no CPU fallback")
-    _preload_torch_hip_runtime()
-    L = C.CDLL(_SO)
-    vp, dp, ip = C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int)
-    sig = {
-        "gtop_abi_version": (C.c_int, []),
-        "gtop_create": (C.c_int, [C.POINTER(vp), C.c_int]),
-        "gtop_destroy": (C.c_int, [vp]),
-        "gtop_last_error": (C.c_char_p, [vp]),
-        "gtop_set_params": (C.c_int, [vp, C.POINTER(GtopParams)]),
-        "gtop_set_sdf": (C.c_int, [vp, dp, C.c_int, C.c_int, C.c_int, dp, dp, C.c_double]),
-        "gtop_set_sdf_device": (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, dp, dp, C.c_double]),
-        "gtop_init_sdf_map": (C.c_int, [vp, dp, dp, C.c_double]),
-        "gtop_update_sdf_map": (C.c_int, [vp, dp, C.c_int]),
-        "gtop_update_sdf_map_device": (C.c_int, [vp, vp, C.c_int, vp]),
-        "gtop_get_sdf": (C.c_int, [vp, dp, ip]),
-        "gtop_set_problem": (C.c_int, [vp, C.c_int, C.c_int, dp, C.c_int, dp]),
-        "gtop_eval_batch": (C.c_int, [vp, C.c_int, dp, dp, dp]),
-        "gtop_cost_nlopt": (C.c_double, [C.c_uint, dp, dp, vp]),
-        "gtop_eval_device": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp]),
-        "gtop_set_paths": (C.c_int, [vp, C.c_int, C.c_int, dp, C.c_double, C.c_double, dp]),
-        "gtop_setup_paths_device": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_double, C.c_double, vp, vp, vp, vp]),
-        "gtop_get_problem": (C.c_int, [vp, dp, dp]),
-        "gtop_min_jerk_start_device": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp]),
-        "gtop_min_jerk_start": (C.c_int, [vp, C.c_int, dp]),
-        "gtop_coefficients_device": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp]),
-        "gtop_eval_trajectories_device": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_double, vp, vp]),
-        "gtop_trajectory_stats": (C.c_int, [vp, C.c_int, dp, C.c_double, dp, dp]),
-        "gtop_set_moving_boxes": (C.c_int, [vp, C.c_int, dp, dp, dp]),
-        "gtop_set_moving_box_polynomials": (C.c_int, [vp, C.c_int, dp, dp, dp]),
-        "gtop_get_moving_box_kind": (C.c_int, [vp, ip, ip]),
-        "gtop_box_polynomial_centres": (C.c_int, [C.c_int, dp, dp, C.c_int, dp, dp]),
-        "gtop_set_moving_cost": (C.c_int, [vp, C.c_int]),
-        "gtop_get_moving_cost": (C.c_int, [vp, ip]),
-        "gtop_set_gradient_mode": (C.c_int, [vp, C.c_int]),
-        "gtop_get_gradient_mode": (C.c_int, [vp, ip]),
-        "gtop_group_set_gradient_mode": (C.c_int, [vp, C.c_int]),
-        "gtop_set_start_times": (C.c_int, [vp, C.c_int, dp]),
-        "gtop_set_start_times_device": (C.c_int, [vp, C.c_int, vp]),
-        "gtop_edt_query_device": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp]),
-        "gtop_edt_query": (C.c_int, [vp, C.c_int, dp, dp, dp, dp]),
-        "gtop_edt_coarse_query_device": (C.c_int, [vp, C.c_int, vp, vp, vp, vp]),
-        "gtop_edt_coarse_query": (C.c_int, [vp, C.c_int, dp, dp, dp]),
-        "gtop_sample_trajectories_device": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_double, vp, vp, C.c_int, vp]),
-        "gtop_trajectory_samples": (C.c_int, [vp, C.c_int, dp, C.c_double, dp, dp, dp, C.c_int]),
-        "gtop_validate_trajectories_device": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_double,
-                                                        C.POINTER(GtopLimits), vp, vp]),
-        "gtop_select_best_device": (C.c_int, [vp, C.c_int, vp, vp, C.POINTER(GtopLimits), vp, vp, vp]),
-        "gtop_validate_batch": (C.c_int, [vp, C.c_int, dp, C.c_double, C.POINTER(GtopLimits), dp, dp,
-                                          C.POINTER(C.c_ubyte), C.POINTER(C.c_int32)]),
-        "gtop_validate_segments_device": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_double,
-                                                    C.POINTER(GtopLimits), vp, vp]),
-        "gtop_validate_segments": (C.c_int, [vp, C.c_int, dp, C.c_double, C.POINTER(GtopLimits), dp]),
-        "gtop_reallocate_times_device": (C.c_int, [vp, C.POINTER(GtopRetime), C.c_int, C.c_int, vp, vp, vp, C.c_int, vp,
-                                                   vp, vp]),
-        "gtop_reallocate_times": (C.c_int, [vp, C.POINTER(GtopRetime), C.c_int, dp, C.c_double, C.POINTER(GtopLimits),
-                                            dp]),
-        "gtop_default_bounds": (C.c_int, [C.c_int, C.c_int, dp, C.c_double, C.c_double, C.c_double, dp, dp]),
-        "gtop_optimize_batch": (C.c_int, [vp, C.c_int, dp, dp, dp, C.c_int, dp]),
-        "gtop_optimize_device": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp, C.c_int, vp, vp]),
-        "gtop_optimize_batch_ex": (C.c_int, [vp, C.c_int, dp, dp, dp, C.POINTER(GtopStop), dp, C.POINTER(C.c_int32),
-                                             C.POINTER(C.c_int32)]),
-        "gtop_optimize_device_ex": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp, C.POINTER(GtopStop), vp,
-                                              vp, vp, vp]),
-        "gtop_get_stats": (C.c_int, [vp, C.POINTER(C.c_int64), dp]),
-        "gtop_reset_stats": (C.c_int, [vp]),
-        "gtop_get_cost_curve": (C.c_int, [vp, dp, dp, C.c_int, ip]),
-        "gtop_clear_cost_curve": (C.c_int, [vp]),
-        "gtop_set_launch_geometry": (C.c_int, [vp, C.c_int, C.c_int]),
-        "gtop_update_sdf_map_window": (C.c_int, [vp, dp, dp, dp, C.c_int]),
-        "gtop_update_sdf_map_window_device": (C.c_int, [vp, dp, dp, vp, C.c_int, vp]),
-        "gtop_set_field_precisions": (C.c_int, [vp, C.c_int]),
-        "gtop_set_field_sign": (C.c_int, [vp, C.c_int, C.c_double]),
-        "gtop_get_field_sign": (C.c_int, [vp, ip, dp]),
-        "gtop_group_set_field_sign": (C.c_int, [vp, C.c_int, C.c_double]),
-        "gtop_device_clock_stamp": (C.c_int, [vp, vp, vp]),
-        "gtop_push_rows": (C.c_int, [vp, vp, C.c_size_t, C.POINTER(C.c_void_p), C.c_int, vp, vp]),
-        "gtop_shared_alloc": (C.c_int, [vp, C.c_size_t, C.POINTER(C.c_void_p), C.c_char_p]),
-        "gtop_shared_open": (C.c_int, [vp, C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]),
-        "gtop_shared_close": (C.c_int, [vp, vp]),
-        "gtop_shared_free": (C.c_int, [vp, vp]),
-        "gtop_device_clock_hz": (C.c_int, [vp, dp]),
-        "gtop_rendezvous_create": (C.c_int, [C.POINTER(vp), vp, C.c_int, C.c_int]),
-        "gtop_rendezvous_destroy": (C.c_int, [vp]),
-        "gtop_rendezvous_get_slot": (vp, [vp, C.c_int]),
-        "gtop_cost_nlopt_shared": (C.c_double, [C.c_uint, dp, dp, vp]),
-        "gtop_rendezvous_leave": (C.c_int, [vp]),
-        "gtop_rendezvous_set_timeout": (C.c_int, [vp, C.c_double]),
-        "gtop_rendezvous_abort": (C.c_int, [vp]),
-        "gtop_rendezvous_stats": (C.c_int, [vp, C.POINTER(C.c_int64), dp, C.POINTER(C.c_int64)]),
-        "gtop_set_optimizer_fusion": (C.c_int, [vp, C.c_int]),
-        "gtop_set_optimizer_precision": (C.c_int, [vp, C.c_int]),
-        "gtop_group_create": (C.c_int, [C.POINTER(vp), ip, C.c_int]),
-        "gtop_group_destroy": (C.c_int, [vp]),
-        "gtop_group_size": (C.c_int, [vp]),
-        "gtop_group_context": (vp, [vp, C.c_int]),
-        "gtop_group_last_error": (C.c_char_p, [vp]),
-        "gtop_group_gather_backend": (C.c_char_p, [vp]),
-        "gtop_group_gather_note": (C.c_char_p, [vp]),
-        "gtop_group_update_sdf_map_window": (C.c_int, [vp, dp, dp, dp, C.c_int]),
-        "gtop_group_set_params": (C.c_int, [vp, C.POINTER(GtopParams)]),
-        "gtop_group_init_sdf_map": (C.c_int, [vp, dp, dp, C.c_double]),
-        "gtop_group_update_sdf_map": (C.c_int, [vp, dp, C.c_int]),
-        "gtop_group_set_sdf": (C.c_int, [vp, dp, C.c_int, C.c_int, C.c_int, dp, dp, C.c_double]),
-        "gtop_group_set_problem": (C.c_int, [vp, C.c_int, C.c_int, dp, C.c_int, dp]),
-        "gtop_group_shard": (C.c_int, [vp, C.c_int, ip, ip]),
-        "gtop_group_eval_batch": (C.c_int, [vp, C.c_int, dp, dp, dp]),
-        "gtop_group_upload_x": (C.c_int, [vp, C.c_int, dp]),
-        "gtop_group_eval_resident": (C.c_int, [vp, C.c_int, C.c_int]),
-        "gtop_group_synchronize": (C.c_int, [vp]),
-        "gtop_group_read_gathered": (C.c_int, [vp, C.c_int, dp, dp]),
-        "gtop_group_device_buffers": (C.c_int, [vp, C.c_int] + [C.POINTER(vp)] * 6),
-        "gtop_group_optimize_batch_ex": (C.c_int, [vp, C.c_int, dp, dp, dp, C.POINTER(GtopStop), dp, C.POINTER(C.c_int32),
-                                                   C.POINTER(C.c_int32)]),
-    }
-    # An OLDER build chosen through GTOP_HIP_LIB (A/B timing against a parent commit) lacks the entry points of a later
-    # ABI version: those stay unbound there (calling one raises AttributeError); the in-tree library must have them all.
-    since = {"gtop_set_moving_cost": 4, "gtop_get_moving_cost": 4, "gtop_set_start_times": 4,
-             "gtop_set_start_times_device": 4, "gtop_validate_trajectories_device": 5, "gtop_select_best_device": 5,
-             "gtop_validate_batch": 5, "gtop_set_gradient_mode": 6, "gtop_get_gradient_mode": 6,
-             "gtop_group_set_gradient_mode": 6, "gtop_set_moving_box_polynomials": 7, "gtop_get_moving_box_kind": 7,
-             "gtop_box_polynomial_centres": 7, "gtop_min_jerk_start_device": 8, "gtop_min_jerk_start": 8,
-             "gtop_validate_segments_device": 9, "gtop_validate_segments": 9, "gtop_reallocate_times_device": 9,
-             "gtop_reallocate_times": 9}
-    L.gtop_abi_version.restype = C.c_int
-    abi = L.gtop_abi_version() if os.environ.get("GTOP_HIP_LIB") else max(since.values())
-    for name, (res, args) in sig.items():
-        if since.get(name, 0) > abi:
-            continue
-        f = getattr(L, name)
-        f.restype = res
-        f.argtypes = args
-    _lib = L
-    return L
+from ._abi import (GTOP_F32, GTOP_F64, OPTI_NODE_PARAMS, _HERE, _SO, _STATUS, GtopError, GtopLimits,  # noqa: F401
+                   GtopParams, GtopRetime, GtopStop, _preload_torch_hip_runtime, library_path, load_library)
 
 
 def _f64(a):
@@ -244,6 +18,39 @@ def _f64(a):
 
 def _p(a):
     return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+_torch = None
+
+
+def _th():
+    """torch, imported at first use: this module imports without it, for the build and for callers of the host arrays."""
+    global _torch
+    if _torch is None:
+        import torch
+        _torch = torch
+    return _torch
+
+
+def _stream(stream, tensor):
+    """The stream argument of every method that has one, as the library takes it: None is torch's current stream on
+    `tensor`'s device, an object with .cuda_stream (a torch Stream) is that handle, anything else is the handle."""
+    if stream is None:
+        stream = _th().cuda.current_stream(tensor.get_device())     # by index: a device object costs torch microseconds
+    return getattr(stream, "cuda_stream", stream)
+
+
+_PRECISIONS = {}
+
+
+def _precision(name, t):
+    """GTOP_F64 or GTOP_F32: the two precisions a field or an evaluation may have."""
+    if not _PRECISIONS:
+        _PRECISIONS.update({_th().float64: GTOP_F64, _th().float32: GTOP_F32})
+    code = _PRECISIONS.get(t.dtype)
+    if code is None:
+        raise ValueError(f"{name}: expected a float64 or float32 tensor, got {t.dtype}")
+    return code
 
 
 def box_polynomial_centres(coef, times, t_range=None):
@@ -255,7 +62,8 @@ def box_polynomial_centres(coef, times, t_range=None):
     tr = None
     if t_range is not None:
         tr = _f64(t_range).reshape(-1, 2)
-        assert tr.shape[0] == coef.shape[0]
+        if tr.shape[0] != coef.shape[0]:
+            raise ValueError("t_range: expected one (t1, t2) per box")
     out = np.empty((times.shape[0], coef.shape[0], 3))
     rc = L.gtop_box_polynomial_centres(coef.shape[0], _p(coef), None if tr is None else _p(tr), times.shape[0], _p(times),
                                        _p(out))
@@ -264,7 +72,75 @@ def box_polynomial_centres(coef, times, t_range=None):
     return out
 
 
-class GtopContext:
+class _Handle:
+    """Owner of one handle `_h` of the library `_L`.  `_prefix` names the handle's family of entry points: its
+    <prefix>destroy runs once, at close() or collection, and _chk turns a status into a GtopError that carries
+    <prefix>last_error."""
+    _prefix = "gtop_"
+
+    def _fn(self, name):
+        return getattr(self._L, self._prefix + name)
+
+    def _chk(self, rc):
+        if rc != 0:
+            raise GtopError(rc, self._fn("last_error")(self._h).decode())
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._fn("destroy")(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _HostProblem(_Handle):
+    """What a context and a group of contexts do alike with host arrays."""
+
+    def set_params(self, **kw):
+        d = dict(OPTI_NODE_PARAMS)
+        d.update(kw)
+        self.params = d
+        p = GtopParams(**d)
+        self._chk(self._fn("set_params")(self._h, C.byref(p)))
+
+    def set_problem(self, T, Df):
+        Df = _f64(Df)
+        B = Df.size // 18
+        T = _f64(T)
+        if T.ndim == 2:
+            m, stride = T.shape[1], T.shape[1]
+            if T.shape[0] != B:
+                raise ValueError(f"T: expected {B} rows, one per 18 entries of Df, got {T.shape[0]}")
+        else:
+            m, stride = T.shape[0], 0
+        self._chk(self._fn("set_problem")(self._h, B, m, _p(T), stride, _p(Df)))
+        self.B, self.m = B, m
+
+    def optimize_batch_ex(self, x0, lb, ub, max_evals, ftol_rel=0.0, xtol_rel=0.0, maxtime=0.0):
+        """As optimize_batch, with NLopt's other stop rules; returns (x, cost, nevals, code).
+
+        What lb / ub may hold, per variable (lb <= ub; include/gtop.h): -inf / +inf on either side — the side is
+        open, the variable starts with asymptote width sigma = 1 and its sigma is never clamped to
+        [0.01, 10] (ub - lb); lb == ub — the variable never moves and is returned as given; a start outside the box is
+        clamped into it before the first evaluation.  The returned point lies inside [lb, ub] exactly."""
+        x = _f64(x0).copy()
+        B = x.shape[0]
+        lb, ub = _f64(lb), _f64(ub)
+        cost = np.empty(B)
+        nev = np.empty(B, dtype=np.int32)
+        code = np.empty(B, dtype=np.int32)
+        stop = GtopStop(int(max_evals), float(ftol_rel), float(xtol_rel), float(maxtime))
+        ip = C.POINTER(C.c_int32)
+        self._chk(self._fn("optimize_batch_ex")(self._h, B, _p(x), _p(lb), _p(ub), C.byref(stop), _p(cost),
+                                                nev.ctypes.data_as(ip), code.ctypes.data_as(ip)))
+        return x, cost, nev, code
+
+
+class GtopContext(_HostProblem):
     """One gtop_ctx (one per host thread / HIP stream)."""
 
     def __init__(self, device=0, params=None):
@@ -278,46 +154,77 @@ class GtopContext:
         self.device = int(device)
         self.set_params(**(params or {}))
 
-    # -- helpers --
-    def _chk(self, rc):
-        if rc != 0:
-            raise GtopError(rc, self._L.gtop_last_error(self._h).decode())
+    # -- device arguments --
+    def _dev(self, name, t, count, dtype=None):
+        """The address of tensor `t` (an int: the entry point's argtypes make it a void *), once `t` is what the entry
+        point reads or writes: on this context's device (get_device() is -1 for a host tensor), contiguous, of `dtype`
+        (None: float64) and of exactly `count` elements."""
+        if dtype is None:
+            dtype = _th().float64
+        if not (t.get_device() == self.device and t.dtype == dtype and t.numel() == count and t.is_contiguous()):
+            raise ValueError(f"{name}: expected a contiguous {dtype} tensor of {count} elements on cuda:{self.device}, "
+                             f"got {'a' if t.is_contiguous() else 'a non-contiguous'} {t.dtype} tensor of shape "
+                             f"{tuple(t.shape)} on {t.device}")
+        return t.data_ptr()
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.gtop_destroy(self._h)
-            self._h = None
+    def _new(self, shape, like, dtype=None, make="empty"):
+        """The output a caller left out: a new tensor on `like`'s device (make="zeros": zeroed)."""
+        return getattr(_th(), make)(shape, dtype=dtype or _th().float64, device=like.device)
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _out(self, name, t, shape, like, dtype=None, make="empty"):
+        """(tensor, address) of an output of `shape`: the caller's `t`, held to what _dev asks, or a new one."""
+        if t is None:
+            t = self._new(shape, like, dtype, make)
+        return t, self._dev(name, t, math.prod(shape), dtype)
+
+    def _times(self, T, B, m, dtype=None):
+        """Segment times -> (address, time stride): a 2-D T holds B m of them, one row per trajectory (stride m);
+        any other holds m, shared by the batch (stride 0)."""
+        stride = m if T.dim() == 2 else 0
+        return self._dev("T", T, B * m if stride else m, dtype), stride
+
+    def _problem(self, x, Df, T, dtype=None):
+        """The problem triple x (B, n), Df (18 B elements), T, with n == 9 (m - 1) -> (B, m, x, Df, T, time stride),
+        the run of arguments every entry point that takes the triple has."""
+        shape = x.shape
+        if len(shape) != 2 or shape[1] % 9:
+            raise ValueError(f"x: expected shape (B, 9 (m - 1)), got {tuple(shape)}")
+        B, n = shape
+        m = n // 9 + 1
+        return (B, m, self._dev("x", x, B * n, dtype), self._dev("Df", Df, B * 18, dtype), *self._times(T, B, m, dtype))
+
+    def _trajectory(self, coeff, T):
+        """The trajectory pair coeff (B, m, 18), T -> (B, m, coeff, T, time stride), likewise."""
+        shape = coeff.shape
+        if len(shape) != 3 or shape[2] != 18:
+            raise ValueError(f"coeff: expected shape (B, m, 18), got {tuple(shape)}")
+        B, m = shape[:2]
+        return (B, m, self._dev("coeff", coeff, B * m * 18), *self._times(T, B, m))
+
+    def _points(self, pts):
+        """(N, 3) fp64 occupied points -> (the tensor to keep until the call is made, its address, N): a tensor made
+        from np.argwhere's transposed view is column-major, so the copy into row-major is made here."""
+        if pts.dim() != 2 or pts.shape[1] != 3:
+            raise ValueError(f"pts: expected shape (N, 3), got {tuple(pts.shape)}")
+        pts = pts.contiguous()
+        return pts, self._dev("pts", pts, pts.shape[0] * 3), pts.shape[0]
 
     # -- configuration --
-    def set_params(self, **kw):
-        d = dict(OPTI_NODE_PARAMS)
-        d.update(kw)
-        self.params = d
-        p = GtopParams(**d)
-        self._chk(self._L.gtop_set_params(self._h, C.byref(p)))
-
     def set_sdf(self, dist, grid, origin, resolution, map_size=None):
         dist = _f64(dist).reshape(-1)
         nx, ny, nz = (int(g) for g in grid)
-        assert dist.size == nx * ny * nz
+        if dist.size != nx * ny * nz:
+            raise ValueError(f"dist: expected {nx * ny * nz} entries, got {dist.size}")
         ms = _p(_f64(map_size)) if map_size is not None else None
         self._chk(self._L.gtop_set_sdf(self._h, _p(dist), nx, ny, nz, _p(_f64(origin)), ms, float(resolution)))
         self.grid = (nx, ny, nz)
 
     def set_sdf_device(self, tensor, grid, origin, resolution, map_size=None):
-        import torch
-        dtype = {torch.float64: GTOP_F64, torch.float32: GTOP_F32}[tensor.dtype]
+        dtype = _precision("tensor", tensor)
         nx, ny, nz = (int(g) for g in grid)
-        assert tensor.is_cuda and tensor.is_contiguous() and tensor.numel() == nx * ny * nz
         ms = _p(_f64(map_size)) if map_size is not None else None
-        self._chk(self._L.gtop_set_sdf_device(self._h, dtype, C.c_void_p(tensor.data_ptr()), nx, ny, nz,
-                                              _p(_f64(origin)), ms, float(resolution)))
+        self._chk(self._L.gtop_set_sdf_device(self._h, dtype, self._dev("tensor", tensor, nx * ny * nz, tensor.dtype),
+                                              nx, ny, nz, _p(_f64(origin)), ms, float(resolution)))
         self._sdf_keepalive = tensor
         self.grid = (nx, ny, nz)
 
@@ -333,12 +240,8 @@ class GtopContext:
 
     def update_sdf_map_device(self, pts, stream=None):
         """pts: (N, 3) float64 CUDA tensor; asynchronous on `stream` (default: torch's current stream)."""
-        import torch
-        assert pts.is_cuda and pts.dtype == torch.float64 and pts.dim() == 2 and pts.shape[1] == 3
-        pts = pts.contiguous()   # (a tensor made from np.argwhere's transposed view is column-major)
-        st = stream if stream is not None else torch.cuda.current_stream()
-        self._chk(self._L.gtop_update_sdf_map_device(self._h, C.c_void_p(pts.data_ptr()), pts.shape[0],
-                                                     C.c_void_p(st.cuda_stream)))
+        pts, *points = self._points(pts)
+        self._chk(self._L.gtop_update_sdf_map_device(self._h, *points, _stream(stream, pts)))
 
     def update_sdf_map_window(self, min_pos, max_pos, pts):
         """The reference's local update (compare2.cpp:147-152): resetBuffer(min, max), setOccupancy per point,
@@ -348,13 +251,9 @@ class GtopContext:
         self._chk(self._L.gtop_update_sdf_map_window(self._h, _p(mn), _p(mx), _p(pts) if pts.size else None, pts.shape[0]))
 
     def update_sdf_map_window_device(self, min_pos, max_pos, pts, stream=None):
-        import torch
-        assert pts.is_cuda and pts.dtype == torch.float64 and pts.dim() == 2 and pts.shape[1] == 3
-        pts = pts.contiguous()
         mn, mx = _f64(min_pos).reshape(3), _f64(max_pos).reshape(3)
-        st = stream if stream is not None else torch.cuda.current_stream()
-        self._chk(self._L.gtop_update_sdf_map_window_device(self._h, _p(mn), _p(mx), C.c_void_p(pts.data_ptr()),
-                                                            pts.shape[0], C.c_void_p(st.cuda_stream)))
+        pts, *points = self._points(pts)
+        self._chk(self._L.gtop_update_sdf_map_window_device(self._h, _p(mn), _p(mx), *points, _stream(stream, pts)))
 
     def get_sdf(self):
         g = (C.c_int * 3)()
@@ -362,18 +261,6 @@ class GtopContext:
         out = np.empty(g[0] * g[1] * g[2])
         self._chk(self._L.gtop_get_sdf(self._h, _p(out), g))
         return out.reshape(tuple(g))
-
-    def set_problem(self, T, Df):
-        Df = _f64(Df)
-        B = Df.size // 18
-        T = _f64(T)
-        if T.ndim == 2:
-            m, stride = T.shape[1], T.shape[1]
-            assert T.shape[0] == B
-        else:
-            m, stride = T.shape[0], 0
-        self._chk(self._L.gtop_set_problem(self._h, B, m, _p(T), stride, _p(Df)))
-        self.B, self.m = B, m
 
     def set_optimizer_fusion(self, mode=2):
         """2 (or True): whole optimizer loop in one launch; 1: MMA update fused into the
@@ -413,26 +300,15 @@ class GtopContext:
     def eval_device(self, x, Df, T, cost=None, grad=None, stream=None):
         """torch CUDA tensors in HBM; launches on `stream` (default: torch's
         current stream) and returns without synchronising."""
-        import torch
-        dtype = {torch.float64: GTOP_F64, torch.float32: GTOP_F32}[x.dtype]
-        B, n = x.shape
-        m = n // 9 + 1
-        assert n == 9 * (m - 1) and Df.numel() == B * 18
-        stride = m if T.dim() == 2 else 0
-        assert T.numel() == (B * m if stride else m)
-        for t in (x, Df, T):
-            assert t.is_cuda and t.is_contiguous() and t.dtype == x.dtype
-        if cost is None:
-            cost = torch.empty(B, dtype=x.dtype, device=x.device)
+        dtype = x.dtype
+        prob = self._problem(x, Df, T, dtype)
+        B, n = prob[0], 9 * (prob[1] - 1)
+        if cost is None:    # not through _out: this is the one method whose host time per launch is measured
+            cost = self._new((B,), x, dtype)
         if grad is None:
-            grad = torch.empty(B, n, dtype=x.dtype, device=x.device)
-        assert cost.is_contiguous() and grad.is_contiguous() and cost.numel() == B and grad.numel() == B * n
-        if stream is None:
-            stream = torch.cuda.current_stream(x.device).cuda_stream
-        self._chk(self._L.gtop_eval_device(self._h, dtype, B, m, C.c_void_p(x.data_ptr()),
-                                           C.c_void_p(Df.data_ptr()), C.c_void_p(T.data_ptr()), stride,
-                                           C.c_void_p(cost.data_ptr()), C.c_void_p(grad.data_ptr()),
-                                           C.c_void_p(stream)))
+            grad = self._new((B, n), x, dtype)
+        self._chk(self._L.gtop_eval_device(self._h, _precision("x", x), *prob, self._dev("cost", cost, B, dtype),
+                                           self._dev("grad", grad, B * n, dtype), _stream(stream, x)))
         return cost, grad
 
     def set_field_precisions(self, keep_fp32=True):
@@ -454,16 +330,15 @@ class GtopContext:
     def push_rows(self, src, dst_ptrs, nbytes=None, stream=None, clock_minmax=None):
         """ONE kernel copies `src` (a contiguous CUDA tensor, or its first nbytes) to every device address in dst_ptrs
         (ints: slots in this process's and in peers' mapped buffers) — gtop_push_rows, the all-gather as stores."""
-        import torch
-        assert src.is_cuda and src.is_contiguous()
+        held = src.numel() * src.element_size()
         if nbytes is None:
-            nbytes = src.numel() * src.element_size()
-        if stream is None:
-            stream = torch.cuda.current_stream(src.device).cuda_stream
+            nbytes = held
+        if int(nbytes) > held:
+            raise ValueError(f"nbytes: expected at most the {held} bytes of src, got {nbytes}")
         arr = (C.c_void_p * len(dst_ptrs))(*[int(p) for p in dst_ptrs])
-        self._chk(self._L.gtop_push_rows(self._h, C.c_void_p(src.data_ptr()), int(nbytes), arr, len(dst_ptrs),
-                                         C.c_void_p(clock_minmax.data_ptr()) if clock_minmax is not None else None,
-                                         C.c_void_p(stream)))
+        pclock = None if clock_minmax is None else self._dev("clock_minmax", clock_minmax, 2, _th().int64)
+        self._chk(self._L.gtop_push_rows(self._h, self._dev("src", src, src.numel(), src.dtype), int(nbytes), arr,
+                                         len(dst_ptrs), pclock, _stream(stream, src)))
 
     def shared_alloc(self, nbytes):
         """(device address, 64-byte handle) of a zeroed allocation another process can map (gtop_shared_alloc)."""
@@ -489,11 +364,8 @@ class GtopContext:
     def clock_stamp(self, minmax, stream=None):
         """Enqueue a device-clock stamp: minmax (torch int64 tensor of 2 on the device, preset to [2**63 - 1, 0])
         becomes [min(., t), max(., t)] of the device's wall clock (gtop_device_clock_stamp)."""
-        import torch
-        assert minmax.is_cuda and minmax.dtype == torch.int64 and minmax.numel() == 2 and minmax.is_contiguous()
-        if stream is None:
-            stream = torch.cuda.current_stream(minmax.device).cuda_stream
-        self._chk(self._L.gtop_device_clock_stamp(self._h, C.c_void_p(minmax.data_ptr()), C.c_void_p(stream)))
+        self._chk(self._L.gtop_device_clock_stamp(self._h, self._dev("minmax", minmax, 2, _th().int64),
+                                                  _stream(stream, minmax)))
 
     def clock_hz(self):
         hz = C.c_double()
@@ -524,27 +396,15 @@ class GtopContext:
         gtop_min_jerk_start): a NEW array (B, n) with the positions of x and, in the velocity and acceleration entries,
         the minimiser of the smoothness term at those positions."""
         out = _f64(x).copy()
-        assert out.ndim == 2 and out.shape[1] == 9 * (self.m - 1)
+        if out.ndim != 2 or out.shape[1] != 9 * (self.m - 1):
+            raise ValueError(f"x: expected shape (B, {9 * (self.m - 1)})")
         self._chk(self._L.gtop_min_jerk_start(self._h, out.shape[0], _p(out)))
         return out
 
     def min_jerk_start_device(self, x, Df, T, stream=None):
         """The same IN PLACE on a torch fp64 CUDA tensor x (B, n), with Df (B, 18) and T (B, m) or (m,): overwrites
         the velocity and acceleration entries of x; asynchronous, capturable.  Returns x."""
-        import torch
-        B, n = x.shape
-        m = n // 9 + 1
-        assert n == 9 * (m - 1) and Df.numel() == B * 18
-        stride = m if T.dim() == 2 else 0
-        assert T.numel() == (B * m if stride else m)
-        for t in (x, Df, T):
-            assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float64
-        if stream is None:
-            stream = torch.cuda.current_stream(x.device).cuda_stream
-        elif hasattr(stream, "cuda_stream"):
-            stream = stream.cuda_stream
-        self._chk(self._L.gtop_min_jerk_start_device(self._h, B, m, C.c_void_p(x.data_ptr()), C.c_void_p(Df.data_ptr()),
-                                                     C.c_void_p(T.data_ptr()), stride, C.c_void_p(stream)))
+        self._chk(self._L.gtop_min_jerk_start_device(self._h, *self._problem(x, Df, T), _stream(stream, x)))
         return x
 
     def trajectory_stats(self, x, dt_sample=0.01):
@@ -571,7 +431,8 @@ class GtopContext:
     def set_moving_boxes(self, p0, vel, scale):
         """Boxes {p0, vel, scale}, each (nbox, 3): centre p0 + vel*t, extent +-scale/2."""
         p0, vel, scale = (_f64(a).reshape(-1, 3) for a in (p0, vel, scale))
-        assert p0.shape == vel.shape == scale.shape
+        if not (p0.shape == vel.shape == scale.shape):
+            raise ValueError("p0, vel, scale: expected one row of 3 per box in each")
         self._chk(self._L.gtop_set_moving_boxes(self._h, p0.shape[0], _p(p0), _p(vel), _p(scale)))
 
     BOXES_CONST_VEL, BOXES_POLYNOMIAL = 0, 1
@@ -582,11 +443,13 @@ class GtopContext:
         [t1, t2] a box stands where its prediction ends.  Replaces whatever list was set, of either kind."""
         coef = _f64(coef).reshape(-1, 3, 6)
         scale = _f64(scale).reshape(-1, 3)
-        assert coef.shape[0] == scale.shape[0]
+        if coef.shape[0] != scale.shape[0]:
+            raise ValueError("scale: expected one row of 3 per box of coef")
         tr = None
         if t_range is not None:
             tr = _f64(t_range).reshape(-1, 2)
-            assert tr.shape[0] == coef.shape[0]
+            if tr.shape[0] != coef.shape[0]:
+                raise ValueError("t_range: expected one (t1, t2) per box of coef")
         self._chk(self._L.gtop_set_moving_box_polynomials(self._h, coef.shape[0], _p(coef), None if tr is None else _p(tr),
                                                           _p(scale)))
 
@@ -642,10 +505,9 @@ class GtopContext:
             self._chk(self._L.gtop_set_start_times_device(self._h, 0, None))
             self._t0_keep = None
             return
-        import torch
-        assert t0.is_cuda and t0.dtype == torch.float64 and t0.is_contiguous()
+        pt0 = self._dev("t0", t0, t0.numel())
         self._t0_keep = t0
-        self._chk(self._L.gtop_set_start_times_device(self._h, t0.numel(), C.c_void_p(t0.data_ptr())))
+        self._chk(self._L.gtop_set_start_times_device(self._h, t0.numel(), pt0))
 
     def edt_query(self, pos, time):
         """(dist (N,), grad (N, 3)) at pos (N, 3), time (N,); time < 0 = static field only."""
@@ -666,16 +528,13 @@ class GtopContext:
 
     def edt_query_device(self, pos, time, stream=None):
         """torch fp64 CUDA tensors pos (N, 3), time (N,) -> dist (N,), grad (N, 3); asynchronous."""
-        import torch
-        assert pos.is_cuda and pos.dtype == torch.float64 and pos.is_contiguous() and time.is_contiguous()
+        if pos.dim() != 2 or pos.shape[1] != 3:
+            raise ValueError(f"pos: expected shape (N, 3), got {tuple(pos.shape)}")
         N = pos.shape[0]
-        dist = torch.empty(N, dtype=torch.float64, device=pos.device)
-        grad = torch.empty(N, 3, dtype=torch.float64, device=pos.device)
-        if stream is None:
-            stream = torch.cuda.current_stream(pos.device).cuda_stream
-        self._chk(self._L.gtop_edt_query_device(self._h, N, C.c_void_p(pos.data_ptr()), C.c_void_p(time.data_ptr()),
-                                                C.c_void_p(dist.data_ptr()), C.c_void_p(grad.data_ptr()),
-                                                C.c_void_p(stream)))
+        ppos, ptime = self._dev("pos", pos, N * 3), self._dev("time", time, N)
+        dist, pdist = self._out("dist", None, (N,), pos)
+        grad, pgrad = self._out("grad", None, (N, 3), pos)
+        self._chk(self._L.gtop_edt_query_device(self._h, N, ppos, ptime, pdist, pgrad, _stream(stream, pos)))
         return dist, grad
 
     # -- trajectory safety report and best-candidate selection (include/gtop.h) --
@@ -694,7 +553,8 @@ class GtopContext:
                                                   None, None))
             return report, None, None
         cost = _f64(cost).reshape(-1)
-        assert cost.shape[0] == B
+        if cost.shape[0] != B:
+            raise ValueError(f"cost: expected {B} entries, one per row of x, got {cost.shape[0]}")
         ok = np.zeros(B, dtype=np.uint8)
         best = np.zeros(2, dtype=np.int32)
         self._chk(self._L.gtop_validate_batch(self._h, B, _p(x), float(dt_sample), C.byref(limits), _p(cost), _p(report),
@@ -704,61 +564,32 @@ class GtopContext:
 
     def coefficients_device(self, x, Df, T, coeff=None, stream=None):
         """torch fp64 CUDA tensors x (B, n), Df (B, 18), T (B, m) or (m,) -> coeff (B, m, 18); asynchronous."""
-        import torch
-        assert x.is_cuda and Df.is_cuda and T.is_cuda and x.dtype == Df.dtype == T.dtype == torch.float64
-        assert x.is_contiguous() and Df.is_contiguous() and T.is_contiguous()
-        B, m = x.shape[0], T.shape[-1]
-        assert x.numel() == B * 9 * (m - 1) and Df.numel() == B * 18 and (T.dim() == 1 or T.shape == (B, m))
-        if coeff is None:
-            coeff = torch.empty(B, m, 18, dtype=torch.float64, device=x.device)
-        if stream is None:
-            stream = torch.cuda.current_stream(x.device).cuda_stream
-        self._chk(self._L.gtop_coefficients_device(self._h, B, m, C.c_void_p(x.data_ptr()), C.c_void_p(Df.data_ptr()),
-                                                   C.c_void_p(T.data_ptr()), m if T.dim() == 2 else 0,
-                                                   C.c_void_p(coeff.data_ptr()), C.c_void_p(stream)))
+        prob = self._problem(x, Df, T)
+        coeff, pcoeff = self._out("coeff", coeff, (*prob[:2], 18), x)
+        self._chk(self._L.gtop_coefficients_device(self._h, *prob, pcoeff, _stream(stream, x)))
         return coeff
 
     def setup_paths_device(self, waypoints, mean_v=1.8, init_time=0.3, T=None, Df=None, x0=None, stream=None):
         """torch fp64 CUDA tensor waypoints (B, m+1, 3) -> T (B, m), Df (B, 18), x0 (B, 9(m-1)): setPath's segment
         times, fixed derivatives and straight-line free variables; asynchronous."""
-        import torch
-        assert waypoints.is_cuda and waypoints.dtype == torch.float64 and waypoints.is_contiguous()
-        assert waypoints.dim() == 3 and waypoints.shape[2] == 3
+        if waypoints.dim() != 3 or waypoints.shape[2] != 3:
+            raise ValueError(f"waypoints: expected shape (B, m + 1, 3), got {tuple(waypoints.shape)}")
         B, m = waypoints.shape[0], waypoints.shape[1] - 1
-        n = 9 * (m - 1)
-        if T is None:
-            T = torch.empty(B, m, dtype=torch.float64, device=waypoints.device)
-        if Df is None:
-            Df = torch.empty(B, 18, dtype=torch.float64, device=waypoints.device)
-        if x0 is None:
-            x0 = torch.empty(B, max(n, 0), dtype=torch.float64, device=waypoints.device)
-        for t, cnt in ((T, B * m), (Df, B * 18), (x0, B * n)):
-            assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and t.numel() == max(cnt, 0)
-        if stream is None:
-            stream = torch.cuda.current_stream(waypoints.device).cuda_stream
-        self._chk(self._L.gtop_setup_paths_device(self._h, B, m, C.c_void_p(waypoints.data_ptr()), float(mean_v),
-                                                  float(init_time), C.c_void_p(T.data_ptr()), C.c_void_p(Df.data_ptr()),
-                                                  C.c_void_p(x0.data_ptr()), C.c_void_p(stream)))
+        pwp = self._dev("waypoints", waypoints, B * (m + 1) * 3)
+        T, pT = self._out("T", T, (B, m), waypoints)
+        Df, pDf = self._out("Df", Df, (B, 18), waypoints)
+        x0, px0 = self._out("x0", x0, (B, max(9 * (m - 1), 0)), waypoints)
+        self._chk(self._L.gtop_setup_paths_device(self._h, B, m, pwp, float(mean_v), float(init_time), pT, pDf, px0,
+                                                  _stream(stream, waypoints)))
         return T, Df, x0
 
     def eval_trajectories_device(self, coeff, T, dt_sample=0.01, stats=None, stream=None):
         """torch fp64 CUDA tensors coeff (B, m, 18), T (B, m) or (m,) -> stats (B, 9), the columns of TRAJ_STATS;
         asynchronous."""
-        import torch
-        assert coeff.is_cuda and T.is_cuda and coeff.dtype == T.dtype == torch.float64
-        assert coeff.is_contiguous() and T.is_contiguous() and coeff.dim() == 3 and coeff.shape[2] == 18
-        B, m = coeff.shape[0], coeff.shape[1]
-        assert T.shape == (m,) or T.shape == (B, m)
-        if stats is None:
-            stats = torch.empty(B, len(self.TRAJ_STATS), dtype=torch.float64, device=coeff.device)
-        assert stats.is_cuda and stats.is_contiguous() and stats.dtype == torch.float64
-        assert stats.numel() == B * len(self.TRAJ_STATS)
-        if stream is None:
-            stream = torch.cuda.current_stream(coeff.device).cuda_stream
-        self._chk(self._L.gtop_eval_trajectories_device(self._h, B, m, C.c_void_p(coeff.data_ptr()),
-                                                        C.c_void_p(T.data_ptr()), m if T.dim() == 2 else 0,
-                                                        float(dt_sample), C.c_void_p(stats.data_ptr()),
-                                                        C.c_void_p(stream)))
+        traj = self._trajectory(coeff, T)
+        stats, pstats = self._out("stats", stats, (traj[0], len(self.TRAJ_STATS)), coeff)
+        self._chk(self._L.gtop_eval_trajectories_device(self._h, *traj, float(dt_sample), pstats,
+                                                        _stream(stream, coeff)))
         return stats
 
     def sample_trajectories_device(self, coeff, T, dt_sample=0.01, max_samples=4096, stats=None, samples=None,
@@ -766,59 +597,32 @@ class GtopContext:
         """torch fp64 CUDA tensors coeff (B, m, 18), T (B, m) or (m,) -> (stats (B, 9), samples (B, max_samples, 3)):
         the getTraj points; trajectory b has stats[b, 8] of them, the first max_samples are stored and the rows behind
         them are left as they were (zero in a buffer allocated here); asynchronous."""
-        import torch
-        assert coeff.is_cuda and T.is_cuda and coeff.dtype == T.dtype == torch.float64
-        assert coeff.is_contiguous() and T.is_contiguous() and coeff.dim() == 3 and coeff.shape[2] == 18
-        B, m = coeff.shape[0], coeff.shape[1]
-        assert T.shape == (m,) or T.shape == (B, m)
+        traj = self._trajectory(coeff, T)
         max_samples = int(max_samples)
-        if stats is None:
-            stats = torch.empty(B, len(self.TRAJ_STATS), dtype=torch.float64, device=coeff.device)
-        if samples is None:
-            samples = torch.zeros(B, max(max_samples, 0), 3, dtype=torch.float64, device=coeff.device)
-        for t, cnt in ((stats, B * len(self.TRAJ_STATS)), (samples, B * max_samples * 3)):
-            assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and t.numel() == max(cnt, 0)
-        if stream is None:
-            stream = torch.cuda.current_stream(coeff.device).cuda_stream
-        self._chk(self._L.gtop_sample_trajectories_device(self._h, B, m, C.c_void_p(coeff.data_ptr()),
-                                                          C.c_void_p(T.data_ptr()), m if T.dim() == 2 else 0,
-                                                          float(dt_sample), C.c_void_p(stats.data_ptr()),
-                                                          C.c_void_p(samples.data_ptr()), max_samples,
-                                                          C.c_void_p(stream)))
+        stats, pstats = self._out("stats", stats, (traj[0], len(self.TRAJ_STATS)), coeff)
+        samples, psamples = self._out("samples", samples, (traj[0], max(max_samples, 0), 3), coeff, make="zeros")
+        self._chk(self._L.gtop_sample_trajectories_device(self._h, *traj, float(dt_sample), pstats, psamples,
+                                                          max_samples, _stream(stream, coeff)))
         return stats, samples
 
     def validate_device(self, coeff, T, limits, dt_sample=0.01, report=None, stream=None):
         """torch fp64 CUDA tensors coeff (B, m, 18), T (B, m) or (m,) -> report (B, 12); asynchronous, capturable
         (pass `report` to write into a buffer of the caller's)."""
-        import torch
-        assert coeff.is_cuda and coeff.dtype == T.dtype == torch.float64 and coeff.is_contiguous() and T.is_contiguous()
-        B, m = coeff.shape[0], coeff.shape[1]
-        if report is None:
-            report = torch.empty(B, len(self.TRAJ_REPORT), dtype=torch.float64, device=coeff.device)
-        assert report.is_contiguous() and report.dtype == torch.float64 and report.numel() == B * len(self.TRAJ_REPORT)
-        if stream is None:
-            stream = torch.cuda.current_stream(coeff.device).cuda_stream
-        self._chk(self._L.gtop_validate_trajectories_device(self._h, B, m, C.c_void_p(coeff.data_ptr()),
-                                                            C.c_void_p(T.data_ptr()), m if T.dim() == 2 else 0,
-                                                            float(dt_sample), C.byref(limits),
-                                                            C.c_void_p(report.data_ptr()), C.c_void_p(stream)))
+        traj = self._trajectory(coeff, T)
+        report, preport = self._out("report", report, (traj[0], len(self.TRAJ_REPORT)), coeff)
+        self._chk(self._L.gtop_validate_trajectories_device(self._h, *traj, float(dt_sample), C.byref(limits), preport,
+                                                            _stream(stream, coeff)))
         return report
 
     def select_best_device(self, report, cost, limits, want_pass=True, best=None, stream=None):
         """report (B, 12), cost (B,) torch fp64 CUDA tensors -> (pass (B,) uint8 or None, best (2,) int32);
         asynchronous, capturable."""
-        import torch
-        assert report.is_cuda and report.dtype == cost.dtype == torch.float64 and report.is_contiguous() and cost.is_contiguous()
         B = cost.numel()
-        assert report.numel() == B * len(self.TRAJ_REPORT)
-        ok = torch.empty(B, dtype=torch.uint8, device=report.device) if want_pass else None
-        if best is None:
-            best = torch.empty(2, dtype=torch.int32, device=report.device)
-        if stream is None:
-            stream = torch.cuda.current_stream(report.device).cuda_stream
-        self._chk(self._L.gtop_select_best_device(self._h, B, C.c_void_p(report.data_ptr()), C.c_void_p(cost.data_ptr()),
-                                                  C.byref(limits), C.c_void_p(ok.data_ptr()) if want_pass else None,
-                                                  C.c_void_p(best.data_ptr()), C.c_void_p(stream)))
+        preport, pcost = self._dev("report", report, B * len(self.TRAJ_REPORT)), self._dev("cost", cost, B)
+        ok, pok = self._out("pass", None, (B,), report, _th().uint8) if want_pass else (None, None)
+        best, pbest = self._out("best", best, (2,), report, _th().int32)
+        self._chk(self._L.gtop_select_best_device(self._h, B, preport, pcost, C.byref(limits), pok, pbest,
+                                                  _stream(stream, report)))
         return ok, best
 
     # -- per-segment report and segment-time reallocation (include/gtop.h) --
@@ -837,20 +641,10 @@ class GtopContext:
     def validate_segments_device(self, coeff, T, limits, dt_sample=0.01, seg_report=None, stream=None):
         """torch fp64 CUDA tensors coeff (B, m, 18), T (B, m) or (m,) -> seg_report (B, m, 10); asynchronous,
         capturable (pass `seg_report` to write into a buffer of the caller's)."""
-        import torch
-        assert coeff.is_cuda and coeff.dtype == T.dtype == torch.float64 and coeff.is_contiguous() and T.is_contiguous()
-        B, m = coeff.shape[0], coeff.shape[1]
-        assert T.shape == (m,) or T.shape == (B, m)
-        if seg_report is None:
-            seg_report = torch.empty(B, m, len(self.SEG_REPORT), dtype=torch.float64, device=coeff.device)
-        assert seg_report.is_cuda and seg_report.is_contiguous() and seg_report.dtype == torch.float64
-        assert seg_report.numel() == B * m * len(self.SEG_REPORT)
-        if stream is None:
-            stream = torch.cuda.current_stream(coeff.device).cuda_stream
-        self._chk(self._L.gtop_validate_segments_device(self._h, B, m, C.c_void_p(coeff.data_ptr()),
-                                                        C.c_void_p(T.data_ptr()), m if T.dim() == 2 else 0,
-                                                        float(dt_sample), C.byref(limits),
-                                                        C.c_void_p(seg_report.data_ptr()), C.c_void_p(stream)))
+        traj = self._trajectory(coeff, T)
+        seg_report, pseg = self._out("seg_report", seg_report, (*traj[:2], len(self.SEG_REPORT)), coeff)
+        self._chk(self._L.gtop_validate_segments_device(self._h, *traj, float(dt_sample), C.byref(limits), pseg,
+                                                        _stream(stream, coeff)))
         return seg_report
 
     def reallocate_times(self, x, options, limits=None, dt_sample=0.01):
@@ -871,25 +665,17 @@ class GtopContext:
         """torch fp64 CUDA tensors -> T_out (B, m); asynchronous, capturable.  LENGTH reads x (B, n) and Df (B, 18);
         LIMITS reads T (B, m) or (m,) and seg_report (B, m, 10) and, under scale_x, rescales x in place.  T_out may be
         T itself when T is (B, m)."""
-        import torch
-        given = [t for t in (x, Df, T, seg_report, T_out) if t is not None]
-        for t in given:
-            assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float64
-        if x is not None:
-            B, m = x.shape[0], x.shape[1] // 9 + 1
-        else:
-            B, m = seg_report.shape[0], seg_report.shape[1]
-        stride = m if (T is None or T.dim() == 2) else 0
-        if T_out is None:
-            T_out = torch.empty(B, m, dtype=torch.float64, device=given[0].device)
-        assert T_out.numel() == B * m
-        if stream is None:
-            stream = torch.cuda.current_stream(T_out.device).cuda_stream
-        elif hasattr(stream, "cuda_stream"):
-            stream = stream.cuda_stream
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        self._chk(self._L.gtop_reallocate_times_device(self._h, C.byref(options), B, m, ptr(x), ptr(Df), ptr(T), stride,
-                                                       ptr(seg_report), ptr(T_out), C.c_void_p(stream)))
+        first = x if x is not None else seg_report
+        if first is None or first.dim() < 2:
+            raise ValueError("x or seg_report: expected x (B, n) or seg_report (B, m, 10)")
+        B, m = (x.shape[0], x.shape[1] // 9 + 1) if x is not None else seg_report.shape[:2]
+        # the library refuses a buffer that the mode reads and that is absent; one that is given is held to its size
+        px, pDf, pseg = (None if t is None else self._dev(name, t, count) for name, t, count in
+                         (("x", x, B * 9 * (m - 1)), ("Df", Df, B * 18), ("seg_report", seg_report, B * m * 10)))
+        pT, stride = (None, m) if T is None else self._times(T, B, m)
+        T_out, pT_out = self._out("T_out", T_out, (B, m), first)
+        self._chk(self._L.gtop_reallocate_times_device(self._h, C.byref(options), B, m, px, pDf, pT, stride, pseg,
+                                                       pT_out, _stream(stream, first)))
         return T_out
 
     # -- batched optimizer --
@@ -911,66 +697,32 @@ class GtopContext:
         x = _f64(x0).copy()
         B = x.shape[0]
         lb, ub = _f64(lb), _f64(ub)
-        assert lb.shape == x.shape == ub.shape
+        if not (lb.shape == x.shape == ub.shape):
+            raise ValueError(f"lb, ub: expected the shape of x0, {x.shape}")
         cost = np.empty(B)
         self._chk(self._L.gtop_optimize_batch(self._h, B, _p(x), _p(lb), _p(ub), int(max_evals), _p(cost)))
         return x, cost
 
-    def optimize_batch_ex(self, x0, lb, ub, max_evals, ftol_rel=0.0, xtol_rel=0.0, maxtime=0.0):
-        """As optimize_batch, with NLopt's other stop rules; returns (x, cost, nevals, code).
-
-        What lb / ub may hold, per variable (lb <= ub; include/gtop.h): -inf / +inf on either side — the side is
-        open, the variable starts with asymptote width sigma = 1 and its sigma is never clamped to
-        [0.01, 10] (ub - lb); lb == ub — the variable never moves and is returned as given; a start outside the box is
-        clamped into it before the first evaluation.  The returned point lies inside [lb, ub] exactly."""
-        x = _f64(x0).copy()
-        B = x.shape[0]
-        lb, ub = _f64(lb), _f64(ub)
-        cost = np.empty(B)
-        nev = np.empty(B, dtype=np.int32)
-        code = np.empty(B, dtype=np.int32)
-        stop = GtopStop(int(max_evals), float(ftol_rel), float(xtol_rel), float(maxtime))
-        ip = C.POINTER(C.c_int32)
-        self._chk(self._L.gtop_optimize_batch_ex(self._h, B, _p(x), _p(lb), _p(ub), C.byref(stop), _p(cost),
-                                                 nev.ctypes.data_as(ip), code.ctypes.data_as(ip)))
-        return x, cost, nev, code
+    def _bounded_problem(self, x, Df, T, lb, ub):
+        """The optimizer's run of arguments: the problem triple, then lb and ub of B n elements each."""
+        prob = self._problem(x, Df, T)
+        return (*prob, self._dev("lb", lb, x.numel()), self._dev("ub", ub, x.numel()))
 
     def optimize_device_ex(self, x, Df, T, lb, ub, max_evals, ftol_rel=0.0, xtol_rel=0.0, maxtime=0.0, stream=None):
         """torch fp64 CUDA tensors; x is overwritten with the best point; returns (x, min_cost, nevals, code)."""
-        import torch
-        B, n = x.shape
-        m = n // 9 + 1
-        stride = m if T.dim() == 2 else 0
-        for t in (x, Df, T, lb, ub):
-            assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float64
-        min_cost = torch.empty(B, dtype=torch.float64, device=x.device)
-        nev = torch.empty(B, dtype=torch.int32, device=x.device)
-        code = torch.empty(B, dtype=torch.int32, device=x.device)
-        if stream is None:
-            stream = torch.cuda.current_stream(x.device).cuda_stream
+        args = self._bounded_problem(x, Df, T, lb, ub)
+        min_cost, pcost = self._out("min_cost", None, (args[0],), x)
+        nev, pnev = self._out("nevals", None, (args[0],), x, _th().int32)
+        code, pcode = self._out("code", None, (args[0],), x, _th().int32)
         stop = GtopStop(int(max_evals), float(ftol_rel), float(xtol_rel), float(maxtime))
-        self._chk(self._L.gtop_optimize_device_ex(
-            self._h, B, m, C.c_void_p(x.data_ptr()), C.c_void_p(Df.data_ptr()), C.c_void_p(T.data_ptr()), stride,
-            C.c_void_p(lb.data_ptr()), C.c_void_p(ub.data_ptr()), C.byref(stop), C.c_void_p(min_cost.data_ptr()),
-            C.c_void_p(nev.data_ptr()), C.c_void_p(code.data_ptr()), C.c_void_p(stream)))
+        self._chk(self._L.gtop_optimize_device_ex(self._h, *args, C.byref(stop), pcost, pnev, pcode, _stream(stream, x)))
         return x, min_cost, nev, code
 
     def optimize_device(self, x, Df, T, lb, ub, max_evals, min_cost=None, stream=None):
         """torch fp64 CUDA tensors; x is overwritten with the best point."""
-        import torch
-        B, n = x.shape
-        m = n // 9 + 1
-        stride = m if T.dim() == 2 else 0
-        for t in (x, Df, T, lb, ub):
-            assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float64
-        if min_cost is None:
-            min_cost = torch.empty(B, dtype=torch.float64, device=x.device)
-        if stream is None:
-            stream = torch.cuda.current_stream(x.device).cuda_stream
-        self._chk(self._L.gtop_optimize_device(self._h, B, m, C.c_void_p(x.data_ptr()), C.c_void_p(Df.data_ptr()),
-                                               C.c_void_p(T.data_ptr()), stride, C.c_void_p(lb.data_ptr()),
-                                               C.c_void_p(ub.data_ptr()), int(max_evals),
-                                               C.c_void_p(min_cost.data_ptr()), C.c_void_p(stream)))
+        args = self._bounded_problem(x, Df, T, lb, ub)
+        min_cost, pcost = self._out("min_cost", min_cost, (args[0],), x)
+        self._chk(self._L.gtop_optimize_device(self._h, *args, int(max_evals), pcost, _stream(stream, x)))
         return x, min_cost
 
     # -- bookkeeping --
@@ -996,10 +748,11 @@ class GtopContext:
         self._chk(self._L.gtop_clear_cost_curve(self._h))
 
 
-class Rendezvous:
+class Rendezvous(_Handle):
     """N serial callers sharing one launch (include/gtop.h, gtop_rendezvous_*).  The context's problem must hold
     the N trajectories (row i = caller i).  Each caller thread uses `cost(i, x)` as its objective and calls
     `leave(i)` when its optimizer has returned."""
+    _prefix = "gtop_rendezvous_"    # no last_error of its own: errors are read from the context
 
     def __init__(self, ctx, n_slots, m):
         self._L = load_library()
@@ -1036,22 +789,12 @@ class Rendezvous:
         self._L.gtop_rendezvous_stats(self._h, C.byref(n), C.byref(s), C.byref(cb))
         return dict(launches=n.value, launch_seconds=s.value, callbacks=cb.value)
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.gtop_rendezvous_destroy(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class GtopGroup:
+class GtopGroup(_HostProblem):
     """One batch over several devices from one process (include/gtop.h, gtop_group_*): the field replicated, the
     batch in contiguous slices, every slice launched on its own device, results gathered on the host or all-gathered
     on the devices (RCCL when the devices differ, peer copies otherwise)."""
+    _prefix = "gtop_group_"
 
     def __init__(self, devices, params=None):
         self._L = load_library()
@@ -1064,21 +807,6 @@ class GtopGroup:
         self.devices = [int(d) for d in devices]
         self.set_params(**(params or {}))
 
-    def _chk(self, rc):
-        if rc != 0:
-            raise GtopError(rc, self._L.gtop_group_last_error(self._h).decode())
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.gtop_group_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     @property
     def gather_backend(self):
         return self._L.gtop_group_gather_backend(self._h).decode()
@@ -1086,12 +814,6 @@ class GtopGroup:
     def gather_note(self):
         """The backend and why: a fallback from RCCL to peer copies names its reason."""
         return self._L.gtop_group_gather_note(self._h).decode()
-
-    def set_params(self, **kw):
-        d = dict(OPTI_NODE_PARAMS)
-        d.update(kw)
-        p = GtopParams(**d)
-        self._chk(self._L.gtop_group_set_params(self._h, C.byref(p)))
 
     def set_gradient_mode(self, consistent=True):
         """GtopContext.set_gradient_mode on every member."""
@@ -1112,14 +834,6 @@ class GtopGroup:
         pts = _f64(pts).reshape(-1, 3)
         mn, mx = _f64(min_pos).reshape(3), _f64(max_pos).reshape(3)
         self._chk(self._L.gtop_group_update_sdf_map_window(self._h, _p(mn), _p(mx), _p(pts) if pts.size else None, pts.shape[0]))
-
-    def set_problem(self, T, Df):
-        Df = _f64(Df)
-        B = Df.size // 18
-        T = _f64(T)
-        m, stride = (T.shape[1], T.shape[1]) if T.ndim == 2 else (T.shape[0], 0)
-        self._chk(self._L.gtop_group_set_problem(self._h, B, m, _p(T), stride, _p(Df)))
-        self.B, self.m = B, m
 
     def shards(self):
         out = []
@@ -1156,7 +870,6 @@ class GtopGroup:
     def set_launch_geometry(self, waves=0, samples_per_lane=0):
         """gtop_set_launch_geometry on every member's context (pins the kernel body: a slice and the whole batch then
         sum in the same order whatever their sizes)."""
-        self._L.gtop_group_context.restype = C.c_void_p
         for i in range(len(self.devices)):
             ctx = C.c_void_p(self._L.gtop_group_context(self._h, i))
             rc = self._L.gtop_set_launch_geometry(ctx, int(waves), int(samples_per_lane))
@@ -1180,16 +893,3 @@ class GtopGroup:
         g = np.empty((self.B, n)) if grads else None
         self._chk(self._L.gtop_group_read_gathered(self._h, int(member), _p(c), _p(g) if grads else None))
         return c, g
-
-    def optimize_batch_ex(self, x0, lb, ub, max_evals, ftol_rel=0.0, xtol_rel=0.0, maxtime=0.0):
-        x = _f64(x0).copy()
-        B = x.shape[0]
-        lb, ub = _f64(lb), _f64(ub)
-        cost = np.empty(B)
-        nev = np.empty(B, dtype=np.int32)
-        code = np.empty(B, dtype=np.int32)
-        stop = GtopStop(int(max_evals), float(ftol_rel), float(xtol_rel), float(maxtime))
-        ip = C.POINTER(C.c_int32)
-        self._chk(self._L.gtop_group_optimize_batch_ex(self._h, B, _p(x), _p(lb), _p(ub), C.byref(stop), _p(cost),
-                                                       nev.ctypes.data_as(ip), code.ctypes.data_as(ip)))
-        return x, cost, nev, code
