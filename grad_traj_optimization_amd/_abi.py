@@ -67,9 +67,19 @@ class GtopRetime(C.Structure):
                          int(bool(uniform)), int(bool(scale_x)), float(max_ratio))
 
 
+class GtopCertifyOpts(C.Structure):
+    """gtop_certify_opts of include/gtop.h: the margin of the continuous-time clearance certificate, the levels of
+    refinement below a segment's 64 intervals (0 .. 3) and the refinements a trajectory may spend."""
+    _fields_ = [("margin", C.c_double), ("max_depth", C.c_int32), ("max_refine", C.c_int32)]
+
+    def __init__(self, margin=0.0, max_depth=2, max_refine=256):
+        super().__init__(float(margin), int(max_depth), int(max_refine))
+
+
 _i, _d, _vp, _dp, _ip = C.c_int, C.c_double, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int)
 _i32p, _i64p = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
 _params, _stop, _limits, _retime = (C.POINTER(s) for s in (GtopParams, GtopStop, GtopLimits, GtopRetime))
+_certify = C.POINTER(GtopCertifyOpts)
 
 # Every entry point of include/gtop.h: name -> (the ABI version that introduced it, 0 when the header does not say;
 # restype; argtypes).
@@ -178,10 +188,25 @@ ENTRY_POINTS = {
 }
 ABI_VERSION = max(since for since, _, _ in ENTRY_POINTS.values())
 
+# The entry points of ABI version 10 (the continuous-time clearance certificate; certify.py wraps them), in a table of
+# their own: ENTRY_POINTS and ABI_VERSION above are the record of the library up to version 9.  Same layout.
+ENTRY_POINTS_10 = {
+    "gtop_certify_trajectories_device": (10, _i, [_vp, _i, _i, _vp, _vp, _i, _certify, _vp, _vp]),
+    "gtop_certify_batch": (10, _i, [_vp, _i, _dp, _certify, _dp]),
+    "gtop_select_best_certified_device": (10, _i, [_vp, _i, _vp, _vp, _vp, _limits, _i, _vp, _vp, _vp]),
+}
+# the ABI version of the library this package is built with (gtop_abi_version() of the in-tree build)
+LIBRARY_ABI_VERSION = max(since for table in (ENTRY_POINTS, ENTRY_POINTS_10) for since, _, _ in table.values())
+
 
 def entry_points(abi):
     """The names a library of ABI version `abi` has."""
     return [name for name, (since, _, _) in ENTRY_POINTS.items() if since <= abi]
+
+
+def entry_points_10(abi):
+    """Likewise, of the second table."""
+    return [name for name, (since, _, _) in ENTRY_POINTS_10.items() if since <= abi]
 
 
 def library_path():
@@ -225,8 +250,12 @@ def load_library():
     # An OLDER build chosen through GTOP_HIP_LIB (A/B timing against a parent commit) lacks the entry points of a later
     # ABI version: those stay unbound there (calling one raises AttributeError); the in-tree library must have them all.
     L.gtop_abi_version.restype = C.c_int
-    for name in entry_points(L.gtop_abi_version() if os.environ.get("GTOP_HIP_LIB") else ABI_VERSION):
+    other = bool(os.environ.get("GTOP_HIP_LIB"))
+    for name in entry_points(L.gtop_abi_version() if other else ABI_VERSION):
         f = getattr(L, name)
         _, f.restype, f.argtypes = ENTRY_POINTS[name]
+    for name in entry_points_10(L.gtop_abi_version() if other else LIBRARY_ABI_VERSION):   # (the same rule)
+        f = getattr(L, name)
+        _, f.restype, f.argtypes = ENTRY_POINTS_10[name]
     _lib = L
     return L

@@ -147,6 +147,29 @@ bool GradTrajOptimizer::validateTrajectory(const Limits &limits, Report *report)
   return pass != 0;
 }
 
+bool GradTrajOptimizer::certifyTrajectory(const CertifyOptions &options, CertifyReport &report) {
+  if (!ctx_ || m_ < 2 || dp_.empty()) {
+    last_status_ = GTOP_ERR_STATE;
+    return false;
+  }
+  gtop_certify_opts opt{};
+  opt.margin = options.margin;
+  opt.max_depth = options.max_depth;
+  opt.max_refine = options.max_refine;
+  double r[GTOP_CERT_REPORT];
+  last_status_ = gtop_certify_batch(ctx_, 1, dp_.data(), &opt, r);
+  if (last_status_ != GTOP_OK) return false;
+  report.verdict = (int)r[0];
+  report.lo = r[1];
+  report.hi = r[2];
+  report.hi_time = r[3];
+  report.first_violation_time = r[4];
+  report.n_undecided = (int)r[5];
+  report.n_refinements = (int)r[6];
+  report.time_sum = r[7];
+  return report.verdict == 1;
+}
+
 bool GradTrajOptimizer::segmentReport(const Limits &limits, std::vector<SegmentReport> *rows) {
   if (!ctx_ || m_ < 2 || dp_.empty()) {
     last_status_ = GTOP_ERR_STATE;

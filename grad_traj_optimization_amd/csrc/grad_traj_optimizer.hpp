@@ -140,6 +140,23 @@ class GradTrajOptimizer {
   };
   bool validateTrajectory(const Limits &limits, Report *report = nullptr);
 
+  // The continuous-time clearance certificate of the trajectory at the current Dp (include/gtop.h,
+  // gtop_certify_batch): where validateTrajectory speaks about the getTraj samples, this speaks about every point of
+  // the curve — true iff the verdict is SAFE: the interpolated distance of the static field is above `margin` over
+  // the whole of [0, time_sum].  Moving obstacles are not covered.  false also when the call fails (ok() tells).
+  struct CertifyOptions {
+    double margin = 0.0;
+    int max_depth = 2, max_refine = 256;
+  };
+  struct CertifyReport {
+    int verdict = 0;                                  // -1 UNSAFE, 0 UNDECIDED, +1 SAFE
+    double lo = 0.0, hi = 0.0, hi_time = 0.0;         // certified lower bound; least midpoint distance and its time
+    double first_violation_time = -1.0;
+    int n_undecided = 0, n_refinements = 0;
+    double time_sum = 0.0;
+  };
+  bool certifyTrajectory(const CertifyOptions &options, CertifyReport &report);
+
   // The same figures per SEGMENT (include/gtop.h, gtop_validate_segments): rows->at(s) covers the getTraj samples that
   // fall into segment s; of `limits` margin, use_boxes and dt_sample are read.  false when the call fails.
   struct SegmentReport {

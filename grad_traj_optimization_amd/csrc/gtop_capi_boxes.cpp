@@ -1,5 +1,6 @@
 // gtop_capi_boxes.cpp — the moving boxes of a context (constant-velocity and polynomial lists), the start times on
-// their clock, and what reads them beside the cost term: the distance queries, the trajectory report and the selection.
+// their clock, and what reads them beside the cost term: the distance queries, the trajectory report and the selection
+// — and, beside the report, the continuous-time certificate of the static field (gtop_certify.hip).
 #include <cmath>
 #include <string>
 #include <vector>
@@ -326,7 +327,7 @@ int gtop_select_best_device(gtop_ctx *c, int B, const void *d_report, const void
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, gtop_launch_select_best(B, static_cast<const double *>(d_report), static_cast<const double *>(d_cost),
                                     limits->max_vel, limits->max_acc, limits->per_axis != 0, limits->allow_out_of_map != 0,
-                                    static_cast<unsigned char *>(d_pass), static_cast<int *>(d_best), c->sel_part.data(),
+                                    nullptr, 0, static_cast<unsigned char *>(d_pass), static_cast<int *>(d_best), c->sel_part.data(),
                                     static_cast<hipStream_t>(hip_stream)));
   return GTOP_OK;
 } GTOP_CATCH_STATUS(c)
@@ -362,6 +363,70 @@ int gtop_validate_batch(gtop_ctx *c, int B, const double *x, double dt_sample, c
     if (best) HIPCHK(c, hipMemcpyAsync(best, d_best, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
   }
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  return GTOP_OK;
+} GTOP_CATCH_STATUS(c)
+
+// ---- continuous-time clearance certificate (gtop_certify.hip) ----
+// the rules of a certificate of B rows, before anything is staged or launched
+static int certify_ready(gtop_ctx *c, int B, int m, int time_stride, const gtop_certify_opts *o) {
+  if (!o) return fail(c, GTOP_ERR_INVALID, "certify: options is NULL");
+  if (!std::isfinite(o->margin) || o->max_depth < 0 || o->max_depth > GTOP_CERT_MAX_DEPTH || o->max_refine < 0)
+    return fail(c, GTOP_ERR_INVALID, "certify: need a finite margin, max_depth in 0 .. 3, max_refine >= 0");
+  if (B < 0 || m < 2 || m > 227 || (time_stride != 0 && time_stride != m))
+    return fail(c, GTOP_ERR_INVALID, "certify: need B >= 0, 2 <= m <= 227, time_stride in {0, m}");
+  return c->field.need_records64(c);
+}
+
+int gtop_certify_trajectories_device(gtop_ctx *c, int B, int m, const void *d_coeff, const void *d_T, int time_stride,
+                                     const gtop_certify_opts *opt, void *d_cert, void *hip_stream) try {
+  if (!c) return GTOP_ERR_INVALID;
+  if (int rc = certify_ready(c, B, m, time_stride, opt)) return rc;
+  if (B == 0) return GTOP_OK;
+  if (!d_coeff || !d_T || !d_cert) return fail(c, GTOP_ERR_INVALID, "certify: NULL buffer");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, gtop_launch_traj_certify(c->field.grid, c->field.rec64.data(), B, m, static_cast<const double *>(d_coeff),
+                                     static_cast<const double *>(d_T), time_stride, opt->margin, opt->max_depth,
+                                     opt->max_refine, static_cast<double *>(d_cert), static_cast<hipStream_t>(hip_stream)));
+  return GTOP_OK;
+} GTOP_CATCH_STATUS(c)
+
+int gtop_certify_batch(gtop_ctx *c, int B, const double *x, const gtop_certify_opts *opt, double *cert) try {
+  if (!c) return GTOP_ERR_INVALID;
+  if (c->B == 0) return fail(c, GTOP_ERR_STATE, "gtop_set_problem / gtop_set_paths has not been called");
+  if (B < 1 || B > c->B || !x || !cert)
+    return fail(c, GTOP_ERR_INVALID, "certify_batch: 1 <= B <= problem batch, x and cert required");
+  int rc = certify_ready(c, B, c->m, c->t_stride, opt);   // (before anything is staged)
+  if (rc) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  const int m = c->m;
+  const size_t n = 9 * (size_t)(m - 1), ncoef = (size_t)B * m * 18, ncert = (size_t)B * GTOP_CERT_REPORT;
+  HIPCHK(c, c->mma_g.reserve(ncoef > (size_t)B * n ? ncoef : (size_t)B * n));   // coefficient scratch
+  HIPCHK(c, c->val_rep.reserve(ncert));
+  HIPCHK(c, hipMemcpyAsync(c->d_x.data(), x, (size_t)B * n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  double *d_coef = c->mma_g.data();
+  if ((rc = gtop_coefficients_device(c, B, m, c->d_x.data(), c->d_Df.data(), c->d_T.data(), c->t_stride, d_coef, c->stream)))
+    return rc;
+  if ((rc = gtop_certify_trajectories_device(c, B, m, d_coef, c->d_T.data(), c->t_stride, opt, c->val_rep.data(), c->stream)))
+    return rc;
+  HIPCHK(c, hipMemcpyAsync(cert, c->val_rep.data(), ncert * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return GTOP_OK;
+} GTOP_CATCH_STATUS(c)
+
+int gtop_select_best_certified_device(gtop_ctx *c, int B, const void *d_report, const void *d_cert, const void *d_cost,
+                                      const gtop_limits *limits, int require, void *d_pass, void *d_best,
+                                      void *hip_stream) try {
+  if (!c) return GTOP_ERR_INVALID;
+  if (int rc = check_limits(c, limits)) return rc;
+  if (require != GTOP_CERT_REQUIRE_SAFE && require != GTOP_CERT_REQUIRE_NOT_UNSAFE)
+    return fail(c, GTOP_ERR_INVALID, "select_best_certified: require is neither SAFE nor NOT_UNSAFE");
+  if (B < 0 || !d_best || (B > 0 && (!d_report || !d_cert || !d_cost)))
+    return fail(c, GTOP_ERR_INVALID, "select_best_certified: need B >= 0, best, and report, cert and cost for B > 0");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, gtop_launch_select_best(B, static_cast<const double *>(d_report), static_cast<const double *>(d_cost),
+                                    limits->max_vel, limits->max_acc, limits->per_axis != 0, limits->allow_out_of_map != 0,
+                                    static_cast<const double *>(d_cert), require, static_cast<unsigned char *>(d_pass),
+                                    static_cast<int *>(d_best), c->sel_part.data(), static_cast<hipStream_t>(hip_stream)));
   return GTOP_OK;
 } GTOP_CATCH_STATUS(c)
 

@@ -1,0 +1,228 @@
+// gtop_certify.hip — the continuous-time clearance certificate of a batch of trajectories, on gfx950.  fp64, the
+// static field only (include/gtop.h, gtop_certify_trajectories_device).
+//
+// The report of gtop_validate.hip looks the field up at the getTraj samples and knows nothing between two of them.
+// This kernel bounds the interpolated distance over whole time intervals.  The lookup is trilinear, so affine in each
+// coordinate inside a cell: over an axis-aligned box inside one cell its minimum is attained at a vertex of the box.
+// A box that contains the curve over an interval, cut along the (at most 8) cells it touches, therefore gives a lower
+// bound of the distance over that interval from 8 trilinear values per cell — whatever the field holds.
+//
+// One WAVEFRONT per trajectory, as the reports have it, no workgroup barrier, nothing per interval to HBM.  A segment is
+// cut into 64 intervals, one per lane; an interval that is neither certified nor in violation is replaced by its 64
+// children, depth-first in ascending time, while the depth and the trajectory's refinement budget allow.  The midpoint
+// distance is the `dist` of edt_query_kernel<false> for (p, -1) through the shared lookup of gtop_edt_lookup.h: the
+// same bits.
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "gtop_device_common.h"   // poly_eval
+#include "gtop_edt_lookup.h"
+#include "gtop_kernels.h"
+#include "gtop_report_common.h"   // poly_vel
+
+// The certifier's own arithmetic is unfused: interval ends, radii, cell ranges, sub-boxes and vertex values round as a
+// numpy restatement of them does (tests/certify_twin.py).  (poly_vel, included above, keeps the fmas it has everywhere.)
+#pragma clang fp contract(off)
+
+namespace {
+
+struct CertParams {
+  GtopGrid g;
+  const double *rec;
+  double margin, kappa, e_map;   // kappa, e_map: the two rounding allowances' grid-dependent parts (the launcher)
+  int max_depth, max_refine;
+};
+struct CertSeg {
+  const double *cf;   // the segment's 18 coefficients (in LDS, see the kernel)
+  double A[3], E[3];  // per axis: the acceleration bound and the absolute slack of the box
+  double t_off;       // trajectory time of the segment's start
+};
+struct CertLane {     // a lane's running results
+  double lo, hi, hi_t, viol_t;
+};
+
+enum { kCertified = 0, kOpen = 1, kViolation = 2 };
+
+__device__ __forceinline__ double cert_clamp01(double u) { return fmin(fmax(u, 0.0), 1.0); }
+
+// One interval [a, a + w] of segment S: the midpoint's distance into R; returns the interval's status, its lower
+// bound in lb.
+__device__ __forceinline__ int cert_eval(const CertParams &P, const CertSeg &S, double a, double w, CertLane &R,
+                                         double &lb) {
+  const GtopGrid &g = P.g;
+  const double h = 0.5 * w, tc = a + h;
+  double p[3], blo[3], bhi[3];
+  for (int k = 0; k < 3; ++k) {
+    const double *c = S.cf + 6 * k;
+    p[k] = poly_eval(c, tc);
+    const double v = poly_vel(c, tc);
+    double r = fabs(v) * h + 0.5 * S.A[k] * h * h;
+    r = r * GTOP_CERT_INFLATE + S.E[k];
+    blo[k] = p[k] - r;
+    bhi[k] = p[k] + r;
+  }
+  // the midpoint: evaluateEDTWithGrad(p, -1)'s value, as edt_query_kernel<false> forms it
+  bool viol;
+  {
+    const bool out = gtop_edt_out_of_map(g, p);
+    int idx[3];
+    double diff[3], values[2][2][2];
+    gtop_edt_corners(g, P.rec, p, idx, diff, values);
+    const double d = out ? -1.0 : gtop_edt_trilinear(diff, values).d;
+    const double t = S.t_off + tc;
+    if (d < R.hi || (d == R.hi && t < R.hi_t)) {
+      R.hi = d; R.hi_t = t;
+    }
+    viol = d <= P.margin;                               // the report's comparison
+    if (viol) R.viol_t = fmin(R.viol_t, t);
+  }
+  // the lower bound over the box
+  bool bad = gtop_edt_out_of_map(g, blo) || gtop_edt_out_of_map(g, bhi);
+  int i0[3] = {0, 0, 0}, span[3] = {0, 0, 0};
+  if (!bad) {
+    for (int k = 0; k < 3; ++k) {                       // the lookup's own cells, gtop_edt_corners
+      const double lm = blo[k] - 0.5 * g.res, hm = bhi[k] - 0.5 * g.res;
+      i0[k] = (int)floor((lm - g.origin[k]) * g.res_inv);
+      span[k] = (int)floor((hm - g.origin[k]) * g.res_inv) - i0[k];
+      bad |= !(span[k] >= 0 && span[k] <= 1);
+    }
+  }
+  lb = -INFINITY;
+  if (!bad) {
+    double vmin = INFINITY, vabs = 0.0;
+#pragma unroll 1
+    for (int q = 0; q < 8; ++q) {                       // (bounded whatever the spans hold)
+      const int dx = q >> 2, dy = (q >> 1) & 1, dz = q & 1;
+      if (dx > span[0] || dy > span[1] || dz > span[2]) continue;
+      const int cell[3] = {i0[0] + dx, i0[1] + dy, i0[2] + dz};
+      double values[2][2][2], u[3][2];
+      gtop_edt_cell_values(g, P.rec, cell, values);
+      for (int k = 0; k < 3; ++k) {                     // the box cut to the cell, in the cell's local coordinates
+        const double c0 = (cell[k] + 0.5) * g.res + g.origin[k];
+        u[k][0] = cert_clamp01((blo[k] - c0) * g.res_inv);
+        u[k][1] = cert_clamp01((bhi[k] - c0) * g.res_inv);
+      }
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const double diff[3] = {u[0][e >> 2], u[1][(e >> 1) & 1], u[2][e & 1]};
+        vmin = fmin(vmin, gtop_edt_trilinear(diff, values).d);
+        vabs = fmax(vabs, fabs(values[e >> 2][(e >> 1) & 1][e & 1]));
+      }
+    }
+    lb = vmin - P.kappa * vabs;
+    if (!(lb == lb)) lb = -INFINITY;                    // (a NaN in the field certifies nothing)
+  }
+  return viol ? kViolation : (lb > P.margin ? kCertified : kOpen);
+}
+
+// Level L of the refinement: the 64 intervals [base + j w, base + (j + 1) w], lane j's its own; then the OPEN ones in
+// ascending time, each replaced by its children while the depth and the budget allow.  nref and nund are wave-uniform.
+template <int L>
+__device__ __forceinline__ void cert_level(const CertParams &P, const CertSeg &S, double base, double w, int lane,
+                                           CertLane &R, int &nref, int &nund) {
+  const double a = base + (double)lane * w;
+  double lb;
+  const int st = cert_eval(P, S, a, w, R, lb);
+  unsigned long long open = __ballot(st == kOpen);
+  bool leaf = st != kOpen;
+  if constexpr (L < GTOP_CERT_MAX_DEPTH) {
+    const double wc = 0.015625 * w;                     // w / 64
+    while (open) {                                      // wave-uniform
+      const int j = __ffsll((long long)open) - 1;
+      open &= open - 1;
+      if (L < P.max_depth && nref < P.max_refine) {
+        ++nref;
+        const double aj = __shfl(a, j);                 // the interval being refined, from its lane
+        cert_level<L + 1>(P, S, aj, wc, lane, R, nref, nund);
+      } else {
+        ++nund;
+        leaf |= lane == j;
+      }
+    }
+  } else {
+    nund += __popcll(open);
+    leaf = true;
+  }
+  if (leaf) R.lo = fmin(R.lo, lb);
+}
+
+__global__ void __launch_bounds__(64)
+traj_certify_kernel(const CertParams P, int B, int m, const double *__restrict__ coeff, const double *__restrict__ T,
+                    int t_stride, double *__restrict__ cert /*[B][GTOP_CERT_REPORT]*/) {
+  // The segment's coefficients are wave-uniform, and as scalar loads they, the grid and the masks of four levels
+  // overflow the scalar register file (17 SGPRs spilled).  Read back from LDS they are vector registers.
+  __shared__ double seg_c[18];
+  const int b = blockIdx.x, lane = threadIdx.x;
+  if (b >= B) return;
+  const double *cf = coeff + (size_t)b * m * 18;   // row s = [cx0..5 | cy0..5 | cz0..5], ascending powers
+  const double *ts = T + (size_t)b * t_stride;
+  CertLane R = {INFINITY, INFINITY, 0.0, INFINITY};
+  int nref = 0, nund = 0;
+  double t_off = 0.0;                               // accumulated as the reports accumulate time_sum
+  for (int s = 0; s < m; ++s) {
+    const double Ts = ts[s], T2 = Ts * Ts, T3 = T2 * Ts;
+    CertSeg S;
+    __builtin_amdgcn_wave_barrier();                // (LDS operations of one wavefront complete in order)
+    if (lane < 18) seg_c[lane] = cf[s * 18 + lane];
+    __builtin_amdgcn_wave_barrier();
+    S.cf = seg_c;
+    S.t_off = t_off;
+    for (int k = 0; k < 3; ++k) {
+      const double *c = S.cf + 6 * k;
+      S.A[k] = 2.0 * fabs(c[2]) + 6.0 * fabs(c[3]) * Ts + 12.0 * fabs(c[4]) * T2 + 20.0 * fabs(c[5]) * T3;
+      // P_k = sum_j |c_j| Ts^j: what the position's and the velocity's rounding errors scale by
+      const double Pk = ((((fabs(c[5]) * Ts + fabs(c[4])) * Ts + fabs(c[3])) * Ts + fabs(c[2])) * Ts + fabs(c[1])) * Ts +
+                        fabs(c[0]);
+      S.E[k] = GTOP_CERT_SLACK * Pk + P.e_map;
+    }
+    cert_level<0>(P, S, 0.0, 0.015625 * Ts, lane, R, nref, nund);
+    t_off += Ts;
+  }
+
+  // ---- the wavefront's reductions ----
+  double lo = R.lo, vt = R.viol_t, hd = R.hi, ht = R.hi_t;
+  for (int off = 32; off > 0; off >>= 1) {
+    lo = fmin(lo, __shfl_xor(lo, off));
+    vt = fmin(vt, __shfl_xor(vt, off));
+    const double od = __shfl_xor(hd, off), ot = __shfl_xor(ht, off);   // lexicographic min of (distance, time)
+    if (od < hd || (od == hd && ot < ht)) {
+      hd = od; ht = ot;
+    }
+  }
+  if (lane == 0) {
+    double *o = cert + (size_t)b * GTOP_CERT_REPORT;
+    o[0] = vt != INFINITY ? -1.0 : (nund == 0 ? 1.0 : 0.0);
+    o[1] = lo; o[2] = hd; o[3] = ht;
+    o[4] = vt != INFINITY ? vt : -1.0;
+    o[5] = (double)nund; o[6] = (double)nref; o[7] = t_off;
+  }
+}
+
+}  // namespace
+
+hipError_t gtop_launch_traj_certify(const GtopGrid &g, const double *rec, int B, int m, const double *coeff,
+                                    const double *T, int t_stride, double margin, int max_depth, int max_refine,
+                                    double *cert, hipStream_t stream) {
+  if (B <= 0) return hipSuccess;
+  // The grid-dependent parts of the two allowances, in plain fp64 so that a restatement follows:
+  // coord = the largest absolute coordinate a face of a cell of the map can have, cells = that in units of res.
+  double coord = 0.0;
+  int nmax = g.nx > g.ny ? g.nx : g.ny;
+  nmax = nmax > g.nz ? nmax : g.nz;
+  for (int k = 0; k < 3; ++k) {
+    coord = fmax(coord, fmax(fabs(g.origin[k]), fmax(fabs(g.min_range[k]), fabs(g.max_range[k]))));
+  }
+  coord = coord + (nmax + 2) * g.res;
+  const double cells = coord * g.res_inv;
+  CertParams P;
+  P.g = g;
+  P.rec = rec;
+  P.margin = margin;
+  P.kappa = GTOP_CERT_KAPPA * (8.0 + cells);
+  P.e_map = GTOP_CERT_SLACK * coord;
+  P.max_depth = max_depth;
+  P.max_refine = max_refine;
+  hipLaunchKernelGGL(traj_certify_kernel, dim3(B), dim3(64), 0, stream, P, B, m, coeff, T, t_stride, cert);
+  return hipGetLastError();
+}

@@ -48,6 +48,19 @@ __device__ __forceinline__ void gtop_edt_corners(const GtopGrid &g, const double
   values[0][0][1] = q2.x; values[0][1][1] = q2.y; values[1][0][1] = q3.x; values[1][1][1] = q3.y;
 }
 
+// The 8 corner values of the cell of base index idx[], for a caller that has the index and no point (the certificate of
+// gtop_certify.hip, which visits the cells a box touches): the loads of gtop_edt_corners, clamps and all.
+__device__ __forceinline__ void gtop_edt_cell_values(const GtopGrid &g, const double *__restrict__ rec, const int idx[3],
+                                                     double values[2][2][2]) {
+  typedef double d2 __attribute__((ext_vector_type(2)));
+  const int cx = min(max(idx[0], -1), g.nx - 1) + 1, cy = min(max(idx[1], -1), g.ny - 1) + 1;
+  const int cz = min(max(idx[2], -1), g.nz - 1) + 1;
+  const d2 *r = reinterpret_cast<const d2 *>(rec + 4 * (((size_t)cx * (g.ny + 1) + cy) * (g.nz + 2) + cz));
+  const d2 q0 = r[0], q1 = r[1], q2 = r[2], q3 = r[3];
+  values[0][0][0] = q0.x; values[0][1][0] = q0.y; values[1][0][0] = q1.x; values[1][1][0] = q1.y;
+  values[0][0][1] = q2.x; values[0][1][1] = q2.y; values[1][0][1] = q3.x; values[1][1][1] = q3.y;
+}
+
 // the largest of the 8 corner values (0 at least): what a box has to undercut to matter
 __device__ __forceinline__ double gtop_edt_vmax(const double values[2][2][2]) {
   double vmax = 0.0;

@@ -219,9 +219,27 @@ GtopTrajReportLauncher gtop_launch_traj_report, gtop_launch_traj_report_poly;
 // two launches; workspace: GTOP_SELECT_PARTIALS x GTOP_SELECT_PARTIAL_BYTES bytes of device memory
 #define GTOP_SELECT_PARTIALS 256
 #define GTOP_SELECT_PARTIAL_BYTES 16
+// cert (may be NULL: gtop_select_best_device): the certificates of the rows, [B][GTOP_CERT_REPORT]; a row then also
+// needs verdict == +1 (require GTOP_CERT_REQUIRE_SAFE) or verdict != -1 (GTOP_CERT_REQUIRE_NOT_UNSAFE) to pass
 hipError_t gtop_launch_select_best(int B, const double *report, const double *cost, double max_vel, double max_acc,
-                                   int per_axis, int allow_out_of_map, unsigned char *pass, int *best, void *workspace,
-                                   hipStream_t stream);
+                                   int per_axis, int allow_out_of_map, const double *cert, int require,
+                                   unsigned char *pass, int *best, void *workspace, hipStream_t stream);
+
+// ---- continuous-time clearance certificate (gtop_certify.hip), fp64, static field -----------------
+#define GTOP_CERT_REPORT 8      // = include/gtop.h
+#define GTOP_CERT_MAX_DEPTH 3   // = include/gtop.h: levels 0 .. 3
+#define GTOP_CERT_REQUIRE_SAFE 1         // = include/gtop.h
+#define GTOP_CERT_REQUIRE_NOT_UNSAFE 2   // = include/gtop.h
+// The rounding allowances, DESIGN.md §5.13.  A box's radius r becomes r * INFLATE + SLACK * (P_k + coord), P_k =
+// sum_j |c_j| T^j of the segment and axis, coord = the map's largest absolute face coordinate; a cell's vertex minimum
+// is lowered by KAPPA * (8 + coord / res) * the largest |corner value| involved.
+#define GTOP_CERT_INFLATE (1.0 + 0x1p-40)
+#define GTOP_CERT_SLACK 0x1p-40
+#define GTOP_CERT_KAPPA 0x1p-46
+// cert[b] of the trajectories (coeff, T) as include/gtop.h lays it out; one wavefront per trajectory, one launch
+hipError_t gtop_launch_traj_certify(const GtopGrid &g, const double *rec, int B, int m, const double *coeff,
+                                    const double *T, int t_stride, double margin, int max_depth, int max_refine,
+                                    double *cert, hipStream_t stream);
 
 // ---- per-segment report (gtop_segments.hip) and segment-time reallocation (gtop_retime.hip), fp64 ------------
 #define GTOP_SEG_REPORT 10   // = include/gtop.h

@@ -257,6 +257,7 @@ constexpr int kSelBlocks = GTOP_SELECT_PARTIALS;
 
 __global__ void __launch_bounds__(256)
 select_kernel(int B, const double *__restrict__ report, const double *__restrict__ cost, SelLimits lim,
+              const double *__restrict__ cert /* NULL: no certificate asked for */, int require,
               unsigned char *__restrict__ pass, SelPartial *__restrict__ part) {
   double c = INFINITY;
   int i = 0x7fffffff, n = 0;
@@ -269,6 +270,10 @@ select_kernel(int B, const double *__restrict__ report, const double *__restrict
     ok &= lim.max_vel <= 0.0 || vel <= lim.max_vel;
     ok &= lim.max_acc <= 0.0 || acc <= lim.max_acc;
     ok &= isfinite(cb);
+    if (cert) {                                          // gtop_select_best_certified_device: the verdict, entry 0
+      const double verdict = cert[(size_t)b * GTOP_CERT_REPORT];
+      ok &= require == GTOP_CERT_REQUIRE_SAFE ? verdict == 1.0 : verdict != -1.0;
+    }
     if (pass) pass[b] = ok ? 1 : 0;
     if (ok) {
       ++n;
@@ -335,13 +340,14 @@ hipError_t gtop_launch_traj_report(const GtopGrid &g, const double *rec, const G
 
 #ifndef GTOP_REPORT_POLY_TU
 hipError_t gtop_launch_select_best(int B, const double *report, const double *cost, double max_vel, double max_acc,
-                                   int per_axis, int allow_out_of_map, unsigned char *pass, int *best, void *workspace,
-                                   hipStream_t stream) {
+                                   int per_axis, int allow_out_of_map, const double *cert, int require,
+                                   unsigned char *pass, int *best, void *workspace, hipStream_t stream) {
   const int nblocks = B > 0 ? min(kSelBlocks, (B + 255) / 256) : 0;   // (no rows: best = {-1, 0} by the second stage alone)
   const SelLimits lim = {max_vel, max_acc, per_axis, allow_out_of_map};
   SelPartial *part = static_cast<SelPartial *>(workspace);
   if (nblocks > 0) {
-    hipLaunchKernelGGL(select_kernel, dim3(nblocks), dim3(256), 0, stream, B, report, cost, lim, pass, part);
+    hipLaunchKernelGGL(select_kernel, dim3(nblocks), dim3(256), 0, stream, B, report, cost, lim, cert, require, pass,
+                       part);
   }
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;

@@ -87,7 +87,9 @@ const char *gtop_last_error(const gtop_ctx *ctx);
  * gtop_get_moving_box_kind / gtop_box_polynomial_centres; 8: the minimum-jerk
  * start point, gtop_min_jerk_start_device / gtop_min_jerk_start; 9: the
  * per-segment report and segment-time reallocation,
- * gtop_validate_segments[_device] / gtop_reallocate_times[_device];
+ * gtop_validate_segments[_device] / gtop_reallocate_times[_device]; 10: the
+ * continuous-time clearance certificate, gtop_certify_trajectories_device /
+ * gtop_certify_batch / gtop_select_best_certified_device;
  * nothing of an earlier version changed meaning). */
 int gtop_abi_version(void);
 
@@ -909,6 +911,93 @@ int gtop_reallocate_times_device(gtop_ctx *ctx, const gtop_retime *opt, int B, i
                                  const void *d_seg_report, void *d_T_out, void *hip_stream);
 int gtop_reallocate_times(gtop_ctx *ctx, const gtop_retime *opt, int B, double *x,
                           double dt_sample, const gtop_limits *limits, double *T_out);
+
+/* ---- continuous-time clearance certificate ------------------------------ */
+/* (Not a PolynomialTraj method.)  Every figure of the reports above is SAMPLED: a
+ * row passes when none of the getTraj samples is within the margin, and between
+ * two samples nothing is known — at a coarse dt_sample a thin obstacle fits there.
+ * The certificate bounds the interpolated distance over whole time intervals.  The
+ * lookup is trilinear, so affine in each coordinate inside a cell: over an
+ * axis-aligned box inside one cell its minimum is attained at a vertex of the box.
+ * A box that contains the curve over an interval, cut along the cells it touches,
+ * gives a lower bound of the distance over the interval from 8 trilinear values per
+ * cell, for ANY field the library holds (an exact ESDF, a windowed one with its
+ * 10000 sentinels, a signed one, arbitrary values of gtop_set_sdf): no Lipschitz
+ * assumption is made.  The STATIC field only: moving boxes are NOT covered — combine
+ * the certificate with the box figures of the sampled report.
+ *
+ * Per segment (time T) and axis k: A_k = 2|c2| + 6|c3|T + 12|c4|T^2 + 20|c5|T^3
+ * bounds the acceleration.  An interval is [a, a + w] in the segment's local time.
+ * Level 0 cuts a segment into 64 intervals, w = T/64, a = j w, j = 0 .. 63;
+ * refining an interval replaces it by 64 children, w' = w/64, a' = a + j w'.  With
+ * h = w/2, tc = a + h: p = the position and v = the velocity at tc; the box is
+ * p_k +- r_k, r_k = |v_k| h + A_k h^2 / 2, enlarged to r_k (1 + 2^-40) + 2^-40 (P_k
+ * + C), P_k = sum_j |c_j| T^j, C = the largest absolute coordinate of a cell face of
+ * the map: over a hundred times the rounding of the interval ends, the position and
+ * the sub-box ends.
+ *   d_mid = the `dist` gtop_edt_query_device returns for (p, -1), bit for bit (-1
+ *     out of the map).
+ *   lb = -inf if p - r or p + r fails the in-map test of the lookup, or if the box
+ *     spans more than 2 of the lookup's cells (floor((x - res/2 - origin) / res)
+ *     at both ends) on an axis; else the least, over the at most 8 cells the box
+ *     touches, of that cell's trilinear form (its 8 corners with the lookup's
+ *     clamps) at the 8 vertices of the box cut to the cell (local coordinates
+ *     against that cell, clamped to [0, 1]), minus 2^-46 (8 + C / res) times the
+ *     largest |corner value| involved (the rounding of the forms and coordinates).
+ *   VIOLATION if d_mid <= margin (the report's comparison), else CERTIFIED if
+ *   lb > margin, else OPEN.
+ * An OPEN interval is refined while its level is below max_depth and fewer than
+ * max_refine refinements have been done for this trajectory; after that it is an
+ * undecided leaf.  A VIOLATION is never refined.  Segments in order, within a
+ * segment depth-first in ascending time; level 0 of every segment is always
+ * evaluated.  cert is B x GTOP_CERT_REPORT doubles per trajectory:
+ *   [0] verdict: -1 UNSAFE (an evaluated midpoint has d_mid <= margin), +1 SAFE (no
+ *       violation and no undecided leaf), 0 UNDECIDED
+ *   [1] lo: the least lb over all leaves — a certified lower bound of the
+ *       interpolated distance over [0, time_sum]; -inf if the curve leaves the map
+ *   [2] hi: the least d_mid over every evaluated midpoint of every level
+ *   [3] the trajectory time of the earliest midpoint that attains hi
+ *   [4] the trajectory time of the earliest evaluated midpoint with d_mid <=
+ *       margin, -1 if none
+ *   [5] the number of undecided leaves   [6] the number of refinements done
+ *   [7] time_sum
+ * SAFE implies lo > margin.  A row's result depends neither on B nor on the row's
+ * place in the batch; results are deterministic.  One wavefront per trajectory
+ * (csrc/gtop_certify.hip), nothing per interval goes to HBM.
+ *
+ * gtop_certify_trajectories_device only enqueues one launch: no allocation, no
+ * synchronisation, capturable; the field is read at replay.  gtop_certify_batch
+ * serves the first B rows of the context's problem at free variables x (1 <= B <=
+ * the problem's batch; GTOP_ERR_STATE when none is set), staged as
+ * gtop_validate_batch stages.  gtop_select_best_certified_device is
+ * gtop_select_best_device's rule plus one condition on cert[b][0]:
+ * GTOP_CERT_REQUIRE_SAFE verdict == +1, GTOP_CERT_REQUIRE_NOT_UNSAFE verdict != -1
+ * — the same two launches and the same workspace, so its calls are ordered with
+ * gtop_select_best_device's as those are with each other.
+ * GTOP_ERR_INVALID, nothing launched: opt NULL, a non-finite margin, max_depth
+ * outside 0 .. GTOP_CERT_MAX_DEPTH, max_refine < 0, B < 0, m outside 2 .. 227, a
+ * time_stride that is neither 0 nor m, a NULL buffer with B > 0, a `require` that
+ * is neither value, the limits rules of gtop_select_best_device.  No fp64 field
+ * resident: GTOP_ERR_STATE.  B = 0 launches nothing (the selection writes best =
+ * {-1, 0}).  fp64 only.  The gtop_group_* entry points do not forward it. */
+typedef struct {
+  double margin;      /* a midpoint with distance <= margin is a violation; lb > margin certifies */
+  int32_t max_depth;  /* 0 .. GTOP_CERT_MAX_DEPTH: levels of refinement below the 64 intervals of a segment */
+  int32_t max_refine; /* >= 0: refinements per trajectory */
+} gtop_certify_opts;
+#define GTOP_CERT_REPORT 8
+#define GTOP_CERT_MAX_DEPTH 3
+#define GTOP_CERT_REQUIRE_SAFE 1
+#define GTOP_CERT_REQUIRE_NOT_UNSAFE 2
+int gtop_certify_trajectories_device(gtop_ctx *ctx, int B, int m, const void *d_coeff,
+                                     const void *d_T, int time_stride,
+                                     const gtop_certify_opts *opt, void *d_cert, void *hip_stream);
+int gtop_certify_batch(gtop_ctx *ctx, int B, const double *x, const gtop_certify_opts *opt,
+                       double *cert);
+int gtop_select_best_certified_device(gtop_ctx *ctx, int B, const void *d_report,
+                                      const void *d_cert, const void *d_cost,
+                                      const gtop_limits *limits, int require, void *d_pass,
+                                      void *d_best, void *hip_stream);
 
 /* ---- bookkeeping the reference keeps inside the callback ------------ */
 

@@ -1,0 +1,185 @@
+#!/usr/bin/env python3
+"""Device time of the continuous-time clearance certificate (gtop_certify_trajectories_device) beside the sampled
+report (gtop_validate_trajectories_device) on the same OPTIMISED trajectories: B = 1 024 and 16 384 rows of 6 segments
+on the 200^3 map, static field.
+
+  (a) the sampled report at dt_sample = 0.01 from a PARENT build of the library,
+  (b) the same from this build (the report's kernels include the shared lookup header this build added a helper to),
+  (c) the certificate at the default options (max_depth 2, max_refine 256) and the report's margin, this build, with
+      the mean refinements per row and the share of each verdict.
+
+Times are spans of the device's own clock between two one-lane stamp kernels (gtop_device_clock_stamp), never host
+timers.  One child process per library and round, the parent build and this build alternating; each row's minimum is
+taken, and the parent's own spread of (a) over the rounds is the yardstick for (b).  (c) / (a) is recorded, not gated.
+The tool also runs the headline benchmark on both builds, alternating, and writes that line under the table.  It writes
+certify_time.{md,json}.
+
+usage: tools/certify_time.py [--parent-lib build_var/libgtop_parent.so] [--rounds 3] [--bench-rounds 2]
+                             [--out profiles/certify]"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+BATCHES = (1024, 16384)
+DT, MARGIN, EVALS = 0.01, 0.3, 20
+
+
+def child(certify):
+    import time
+
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, ROOT)
+    import grad_traj_optimization_amd as gtop
+    from grad_traj_optimization_amd import problem
+
+    mp = problem.make_map(200, density=0.02, seed=0)
+    ctx = gtop.GtopContext(0)
+    ctx.init_sdf_map(mp.map_size, mp.origin, mp.resolution)
+    ctx.update_sdf_map(mp.obstacle_points())
+    ctx.set_params()
+    dev = torch.device("cuda:0")
+    hz = ctx.clock_hz()
+    init = torch.tensor([2 ** 63 - 1, 0], dtype=torch.int64, device=dev)
+    stamps = init.clone()
+
+    def span(fn, reps):
+        """us per call of fn over `reps` back-to-back calls, by the device clock; sustained clocks first."""
+        t_w = time.perf_counter()
+        while time.perf_counter() - t_w < 0.05:
+            fn()
+            torch.cuda.synchronize()
+        best = None
+        for _ in range(5):
+            stamps.copy_(init)
+            ctx.clock_stamp(stamps)
+            for _ in range(reps):
+                fn()
+            ctx.clock_stamp(stamps)
+            torch.cuda.synchronize()
+            st = stamps.tolist()
+            us = (st[1] - st[0]) / hz * 1e6 / reps
+            best = us if best is None else min(best, us)
+        return best
+
+    out = {}
+    for B in BATCHES:
+        b = problem.make_trajectories(B, 6, mp, seed=1)
+        ctx.set_problem(b.T, b.Df)
+        lb, ub = ctx.default_bounds(b.waypoints)
+        x, _ = ctx.optimize_batch(b.x, lb, ub, EVALS)
+        coeff_h, _ = ctx.trajectory_stats(x, DT)
+        coeff = torch.tensor(coeff_h, device=dev)
+        T = torch.tensor(b.T, device=dev)
+        report = torch.empty(B, 12, dtype=torch.float64, device=dev)
+        lim = gtop.GtopLimits(margin=MARGIN)
+        reps = 20 if B == 1024 else 5
+        out[f"report B={B}"] = span(lambda: ctx.validate_device(coeff, T, lim, dt_sample=DT, report=report), reps)
+        if certify:
+            cert = torch.empty(B, 8, dtype=torch.float64, device=dev)
+            opts = gtop.GtopCertifyOpts(margin=MARGIN)
+            out[f"certificate B={B}"] = span(lambda: gtop.certify_device(ctx, coeff, T, opts, cert=cert), reps)
+            level0 = gtop.GtopCertifyOpts(margin=MARGIN, max_depth=0, max_refine=0)
+            out[f"certificate, level 0 only B={B}"] = span(lambda: gtop.certify_device(ctx, coeff, T, level0, cert=cert), reps)
+            gtop.certify_device(ctx, coeff, T, opts, cert=cert)
+            torch.cuda.synchronize()
+            c, r = cert.cpu().numpy(), report.cpu().numpy()
+            out[f"mean refinements per row B={B}"] = float(c[:, 6].mean())
+            out[f"rows that spend refinements B={B}"] = float((c[:, 6] > 0).mean())
+            for name, v in (("unsafe", -1), ("undecided", 0), ("safe", 1)):
+                out[f"share {name} B={B}"] = float((c[:, 0] == v).mean())
+            out[f"share passing the sampled report B={B}"] = float(((r[:, 4] == 0) & (r[:, 6] == 0)).mean())
+            out[f"rows the report passes and the certificate calls unsafe B={B}"] = int(
+                ((r[:, 4] == 0) & (r[:, 6] == 0) & (c[:, 0] == -1)).sum())
+            assert np.all(c[:, 1] <= c[:, 2])
+    print("CERTIFY_TIME_JSON " + json.dumps(out), flush=True)
+
+
+def run_child(who, parent_lib, args, prefix, timeout):
+    env = dict(os.environ)
+    if who == "parent":
+        env["GTOP_HIP_LIB"] = os.path.realpath(parent_lib)
+    else:
+        env.pop("GTOP_HIP_LIB", None)
+    p = subprocess.run([sys.executable, *args], env=env, capture_output=True, text=True, timeout=timeout, cwd=ROOT)
+    line = [ln for ln in p.stdout.splitlines() if ln.startswith(prefix)]
+    if p.returncode != 0 or not line:
+        sys.exit(f"{who} child failed ({p.returncode}):\n{p.stdout[-2000:]}\n{p.stderr[-2000:]}")
+    return line[-1]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--parent-lib", default=os.path.join(ROOT, "build_var", "libgtop_parent.so"))
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "certify"))
+    ap.add_argument("--bench-rounds", type=int, default=2, help="alternating bench.py runs per build (0 = none)")
+    ap.add_argument("--child", choices=("certify", "report"))
+    a = ap.parse_args()
+    if a.child:
+        return child(a.child == "certify")
+    if not os.path.exists(a.parent_lib):
+        sys.exit(f"no parent build at {a.parent_lib}: make -C grad_traj_optimization_amd/csrc lib OUT=... on the parent commit")
+    runs = {"parent": [], "this": []}
+    for _ in range(a.rounds):                                   # alternating, one fresh process each
+        for who in ("parent", "this"):
+            line = run_child(who, a.parent_lib, [os.path.abspath(__file__), "--child", "report" if who == "parent" else "certify"],
+                             "CERTIFY_TIME_JSON ", 400)
+            runs[who].append(json.loads(line.split(" ", 1)[1]))
+            print(f"{who}: done", flush=True)
+    timed = lambda k: k.startswith(("report", "certificate"))
+    best = {who: {k: min(r[k] for r in rs) for k in rs[0] if timed(k)} for who, rs in runs.items()}
+    spread = {k: max(r[k] for r in runs["parent"]) / min(r[k] for r in runs["parent"]) - 1 for k in best["parent"]}
+    facts = {k: v for k, v in runs["this"][0].items() if not timed(k)}
+    bench = {"parent": [], "this": []}
+    for _ in range(a.bench_rounds):
+        for who in ("parent", "this"):
+            line = run_child(who, a.parent_lib, [os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2000", "--warmup", "100"],
+                             "{", 300)
+            bench[who].append(json.loads(line)["value"])
+    bench_line = None
+    if a.bench_rounds:
+        fm = lambda v: " / ".join(f"{x / 1e6:.2f}" for x in v)
+        pv, tv = bench["parent"], bench["this"]
+        bench_line = (f"`bench.py --gpus 1 --steps 2000 --warmup 100`, {a.bench_rounds} alternating runs per build (parent first), "
+                      f"M evals/s: parent {fm(pv)}; this build {fm(tv)}; means {sum(tv) / len(tv) / (sum(pv) / len(pv)):.4f} of the "
+                      f"parent's; the parent's own runs differ by {(max(pv) / min(pv) - 1) * 100:.2f} %, this build's by "
+                      f"{(max(tv) / min(tv) - 1) * 100:.2f} %")
+    lines = ["| B | (a) report, parent build, us | (b) report, this build, us | (b) / (a) | parent's spread of (a) | inside it "
+             "| (c) certificate, us | (c) / (a) | level 0 only, us | mean refinements per row |",
+             "|---|---|---|---|---|---|---|---|---|---|"]
+    failed = []
+    for B in BATCHES:
+        pa, tb, sp = best["parent"][f"report B={B}"], best["this"][f"report B={B}"], spread[f"report B={B}"]
+        c, c0 = best["this"][f"certificate B={B}"], best["this"][f"certificate, level 0 only B={B}"]
+        ok = tb / pa - 1 <= sp
+        if not ok:
+            failed.append(f"B={B}")
+        lines.append(f"| {B} | {pa:.1f} | {tb:.1f} | {tb / pa:.3f} | {sp * 100:.1f} % | {'yes' if ok else 'NO'} | {c:.1f} | {c / pa:.2f} "
+                     f"| {c0:.1f} | {facts[f'mean refinements per row B={B}']:.2f} |")
+    table = "\n".join(lines)
+    os.makedirs(a.out, exist_ok=True)
+    with open(os.path.join(a.out, "certify_time.json"), "w") as f:
+        json.dump(dict(runs=runs, best_us=best, parent_spread=spread, facts=facts, report_outside_parent_spread=failed,
+                       rounds=a.rounds, bench_evals_per_s=bench, bench_line=bench_line), f, indent=1)
+    with open(os.path.join(a.out, "certify_time.md"), "w") as f:
+        f.write("fp64, m = 6, 200^3 map, static field, rows optimised for %d evaluations, margin %.1f, dt_sample = %.2f, "
+                "certificate at max_depth 2 / max_refine 256; device-clock spans, minimum over %d alternating rounds of one "
+                "fresh process per library\n\n%s\n\nsizes where (b) lies outside the parent's own spread of (a): %s\n\n"
+                % (EVALS, MARGIN, DT, a.rounds, table, ", ".join(failed) if failed else "none"))
+        for k, v in facts.items():
+            f.write(f"- {k}: {v:.4g}\n")
+        if bench_line:
+            f.write("\nbench.py A/B in the same call: %s\n" % bench_line)
+    print(table)
+    print(json.dumps(facts))
+    if bench_line:
+        print(bench_line)
+
+
+if __name__ == "__main__":
+    main()
