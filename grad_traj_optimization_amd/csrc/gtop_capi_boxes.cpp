@@ -294,27 +294,47 @@ static int validate_ready(gtop_ctx *c, int B, int m, int time_stride, double dt_
   return c->field.need_records64(c);
 }
 
-static int validate_on_stream(gtop_ctx *c, int B, int m, const void *d_coeff, const void *d_T, int time_stride,
-                              double dt_sample, const gtop_limits *lim, void *d_report, hipStream_t s, int problem_B) {
+// Either sampled report of B rows into d_out: the whole-trajectory one (gtop_validate.hip, [B][GTOP_TRAJ_REPORT]) or the
+// per-segment one (gtop_segments.hip, [B][m][GTOP_SEG_REPORT]).  who: the entry's name in the NULL-buffer text
+static int report_on_stream(gtop_ctx *c, bool per_segment, const char *who, int B, int m, const void *d_coeff,
+                            const void *d_T, int time_stride, double dt_sample, const gtop_limits *lim, void *d_out,
+                            hipStream_t s, int problem_B) {
   if (int rc = validate_ready(c, B, m, time_stride, dt_sample, lim, problem_B)) return rc;
   const bool boxes = lim->use_boxes != 0;
   if (B == 0) return GTOP_OK;
-  if (!d_coeff || !d_T || !d_report) return fail(c, GTOP_ERR_INVALID, "validate: NULL buffer");
+  if (!d_coeff || !d_T || !d_out) return fail(c, GTOP_ERR_INVALID, std::string(who) + ": NULL buffer");
   HIPCHK(c, hipSetDevice(c->device));
+  const GtopBoxList list = box_list(c, boxes ? c->nbox : 0);
+  const double *coeff = static_cast<const double *>(d_coeff), *T = static_cast<const double *>(d_T);
   const double *t0 = (boxes && c->t0_count > 0) ? c->t0_dev : nullptr;
-  HIPCHK(c, gtop_launch_traj_report(c->field.grid, c->field.rec64.data(), box_list(c, boxes ? c->nbox : 0), B, m,
-                                    static_cast<const double *>(d_coeff), static_cast<const double *>(d_T), time_stride,
-                                    dt_sample, t0, c->t0_count > 1 ? 1 : 0, lim->margin,
-                                    static_cast<double *>(d_report), c->simds, s));
+  const int t0_stride = c->t0_count > 1 ? 1 : 0;
+  double *out = static_cast<double *>(d_out);
+  if (per_segment)
+    HIPCHK(c, gtop_launch_traj_segments(c->field.grid, c->field.rec64.data(), list, B, m, coeff, T, time_stride, dt_sample,
+                                        t0, t0_stride, lim->margin, out, s));
+  else
+    HIPCHK(c, gtop_launch_traj_report(c->field.grid, c->field.rec64.data(), list, B, m, coeff, T, time_stride, dt_sample,
+                                      t0, t0_stride, lim->margin, out, c->simds, s));
   return GTOP_OK;
+}
+
+// x of the problem's first B rows -> d_x -> their coefficients, left in mma_g (the coefficient scratch); no
+// synchronisation
+static int stage_coefficients(gtop_ctx *c, int B, const double *x) {
+  const int m = c->m;
+  const size_t n = 9 * (size_t)(m - 1), ncoef = (size_t)B * m * 18;
+  HIPCHK(c, c->mma_g.reserve(ncoef > (size_t)B * n ? ncoef : (size_t)B * n));
+  HIPCHK(c, hipMemcpyAsync(c->d_x.data(), x, (size_t)B * n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  return gtop_coefficients_device(c, B, m, c->d_x.data(), c->d_Df.data(), c->d_T.data(), c->t_stride, c->mma_g.data(),
+                                  c->stream);
 }
 
 int gtop_validate_trajectories_device(gtop_ctx *c, int B, int m, const void *d_coeff, const void *d_T, int time_stride,
                                       double dt_sample, const gtop_limits *limits, void *d_report,
                                       void *hip_stream) try {
   if (!c) return GTOP_ERR_INVALID;
-  return validate_on_stream(c, B, m, d_coeff, d_T, time_stride, dt_sample, limits, d_report,
-                            static_cast<hipStream_t>(hip_stream), 0);
+  return report_on_stream(c, false, "validate", B, m, d_coeff, d_T, time_stride, dt_sample, limits, d_report,
+                          static_cast<hipStream_t>(hip_stream), 0);
 } GTOP_CATCH_STATUS(c)
 
 int gtop_select_best_device(gtop_ctx *c, int B, const void *d_report, const void *d_cost, const gtop_limits *limits,
@@ -342,19 +362,16 @@ int gtop_validate_batch(gtop_ctx *c, int B, const double *x, double dt_sample, c
   int rc = validate_ready(c, B, c->m, c->t_stride, dt_sample, limits, c->B);   // (before anything is staged)
   if (rc) return rc;
   HIPCHK(c, hipSetDevice(c->device));
-  const int m = c->m;
-  const size_t n = 9 * (size_t)(m - 1), ncoef = (size_t)B * m * 18, nrep = (size_t)B * GTOP_TRAJ_REPORT;
-  HIPCHK(c, c->mma_g.reserve(ncoef > (size_t)B * n ? ncoef : (size_t)B * n));   // coefficient scratch
+  const size_t nrep = (size_t)B * GTOP_TRAJ_REPORT;
   // report | cost | best (2 x int32 in one double's room) | pass (B bytes)
   HIPCHK(c, c->val_rep.reserve(nrep + B + 1 + (B + 7) / 8));
   double *d_rep = c->val_rep.data(), *d_cost = d_rep + nrep;
   int *d_best = reinterpret_cast<int *>(d_cost + B);
   unsigned char *d_pass = reinterpret_cast<unsigned char *>(d_cost + B + 1);
-  HIPCHK(c, hipMemcpyAsync(c->d_x.data(), x, (size_t)B * n * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  double *d_coef = c->mma_g.data();
-  if ((rc = gtop_coefficients_device(c, B, m, c->d_x.data(), c->d_Df.data(), c->d_T.data(), c->t_stride, d_coef, c->stream)))
+  if ((rc = stage_coefficients(c, B, x))) return rc;
+  if ((rc = report_on_stream(c, false, "validate", B, c->m, c->mma_g.data(), c->d_T.data(), c->t_stride, dt_sample, limits,
+                             d_rep, c->stream, c->B)))
     return rc;
-  if ((rc = validate_on_stream(c, B, m, d_coef, c->d_T.data(), c->t_stride, dt_sample, limits, d_rep, c->stream, c->B))) return rc;
   HIPCHK(c, hipMemcpyAsync(report, d_rep, nrep * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   if (cost) {
     HIPCHK(c, hipMemcpyAsync(d_cost, cost, (size_t)B * sizeof(double), hipMemcpyHostToDevice, c->stream));
@@ -398,15 +415,11 @@ int gtop_certify_batch(gtop_ctx *c, int B, const double *x, const gtop_certify_o
   int rc = certify_ready(c, B, c->m, c->t_stride, opt);   // (before anything is staged)
   if (rc) return rc;
   HIPCHK(c, hipSetDevice(c->device));
-  const int m = c->m;
-  const size_t n = 9 * (size_t)(m - 1), ncoef = (size_t)B * m * 18, ncert = (size_t)B * GTOP_CERT_REPORT;
-  HIPCHK(c, c->mma_g.reserve(ncoef > (size_t)B * n ? ncoef : (size_t)B * n));   // coefficient scratch
+  const size_t ncert = (size_t)B * GTOP_CERT_REPORT;
   HIPCHK(c, c->val_rep.reserve(ncert));
-  HIPCHK(c, hipMemcpyAsync(c->d_x.data(), x, (size_t)B * n * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  double *d_coef = c->mma_g.data();
-  if ((rc = gtop_coefficients_device(c, B, m, c->d_x.data(), c->d_Df.data(), c->d_T.data(), c->t_stride, d_coef, c->stream)))
-    return rc;
-  if ((rc = gtop_certify_trajectories_device(c, B, m, d_coef, c->d_T.data(), c->t_stride, opt, c->val_rep.data(), c->stream)))
+  if ((rc = stage_coefficients(c, B, x))) return rc;
+  if ((rc = gtop_certify_trajectories_device(c, B, c->m, c->mma_g.data(), c->d_T.data(), c->t_stride, opt,
+                                             c->val_rep.data(), c->stream)))
     return rc;
   HIPCHK(c, hipMemcpyAsync(cert, c->val_rep.data(), ncert * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -431,39 +444,19 @@ int gtop_select_best_certified_device(gtop_ctx *c, int B, const void *d_report, 
 } GTOP_CATCH_STATUS(c)
 
 // ---- per-segment report (gtop_segments.hip) and segment-time reallocation (gtop_retime.hip) ----
-static int segments_on_stream(gtop_ctx *c, int B, int m, const void *d_coeff, const void *d_T, int time_stride,
-                              double dt_sample, const gtop_limits *lim, void *d_seg, hipStream_t s, int problem_B) {
-  if (int rc = validate_ready(c, B, m, time_stride, dt_sample, lim, problem_B)) return rc;
-  const bool boxes = lim->use_boxes != 0;
-  if (B == 0) return GTOP_OK;
-  if (!d_coeff || !d_T || !d_seg) return fail(c, GTOP_ERR_INVALID, "validate_segments: NULL buffer");
-  HIPCHK(c, hipSetDevice(c->device));
-  const double *t0 = (boxes && c->t0_count > 0) ? c->t0_dev : nullptr;
-  HIPCHK(c, gtop_launch_traj_segments(c->field.grid, c->field.rec64.data(), box_list(c, boxes ? c->nbox : 0), B, m,
-                                      static_cast<const double *>(d_coeff), static_cast<const double *>(d_T), time_stride,
-                                      dt_sample, t0, c->t0_count > 1 ? 1 : 0, lim->margin, static_cast<double *>(d_seg), s));
-  return GTOP_OK;
-}
-
 int gtop_validate_segments_device(gtop_ctx *c, int B, int m, const void *d_coeff, const void *d_T, int time_stride,
                                   double dt_sample, const gtop_limits *limits, void *d_seg_report, void *hip_stream) try {
   if (!c) return GTOP_ERR_INVALID;
-  return segments_on_stream(c, B, m, d_coeff, d_T, time_stride, dt_sample, limits, d_seg_report,
-                            static_cast<hipStream_t>(hip_stream), 0);
+  return report_on_stream(c, true, "validate_segments", B, m, d_coeff, d_T, time_stride, dt_sample, limits, d_seg_report,
+                          static_cast<hipStream_t>(hip_stream), 0);
 } GTOP_CATCH_STATUS(c)
 
-// x of the problem's first B rows -> d_x -> coefficients (scratch) -> the segment report in seg_rep; no synchronisation
+// x of the problem's first B rows -> their coefficients -> the segment report in seg_rep; no synchronisation
 static int segments_staged(gtop_ctx *c, int B, const double *x, double dt_sample, const gtop_limits *limits) {
-  const int m = c->m;
-  const size_t n = 9 * (size_t)(m - 1), ncoef = (size_t)B * m * 18;
-  HIPCHK(c, c->mma_g.reserve(ncoef > (size_t)B * n ? ncoef : (size_t)B * n));   // coefficient scratch
-  HIPCHK(c, c->seg_rep.reserve((size_t)B * m * (GTOP_SEG_REPORT + 1)));         // report | T_out
-  HIPCHK(c, hipMemcpyAsync(c->d_x.data(), x, (size_t)B * n * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  if (int rc = gtop_coefficients_device(c, B, m, c->d_x.data(), c->d_Df.data(), c->d_T.data(), c->t_stride, c->mma_g.data(),
-                                        c->stream))
-    return rc;
-  return segments_on_stream(c, B, m, c->mma_g.data(), c->d_T.data(), c->t_stride, dt_sample, limits, c->seg_rep.data(),
-                            c->stream, c->B);
+  HIPCHK(c, c->seg_rep.reserve((size_t)B * c->m * (GTOP_SEG_REPORT + 1)));   // report | T_out
+  if (int rc = stage_coefficients(c, B, x)) return rc;
+  return report_on_stream(c, true, "validate_segments", B, c->m, c->mma_g.data(), c->d_T.data(), c->t_stride, dt_sample,
+                          limits, c->seg_rep.data(), c->stream, c->B);
 }
 
 int gtop_validate_segments(gtop_ctx *c, int B, const double *x, double dt_sample, const gtop_limits *limits,

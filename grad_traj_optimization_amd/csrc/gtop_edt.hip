@@ -35,36 +35,21 @@
 #include "gtop_edt_lookup.h"
 #include "gtop_kernels.h"
 
-// This file is compiled TWICE (csrc/Makefile), as gtop_kernels.hip and gtop_validate.hip are: as it stands — the query
-// kernels for constant-velocity box lists and the launcher the C-ABI layer calls — and with -DGTOP_EDT_POLY_TU into an
-// object of its own that holds the same two kernels for POLYNOMIAL box lists (gtop_set_moving_box_polynomials; rows of
-// kBoxRowPoly = 24 doubles, gtop_edt_lookup.h) behind a launcher named gtop_launch_edt_query_poly, which the first
-// object's launcher forwards to.  So the kernels of the first object keep their names and their code, and a
-// constant-velocity launch stages the rows it always staged.
-#ifdef GTOP_EDT_POLY_TU
-#define edt_query_kernel edt_query_poly_kernel
-#define gtop_launch_edt_query gtop_launch_edt_query_poly
-constexpr bool kQueryPoly = true;
-#else
-constexpr bool kQueryPoly = false;
-#endif
-
 namespace {
 
-// boxes staged in LDS per pass: 9 KiB of rows in either object (constant velocity: rows of 9; polynomial: rows of 24)
+// boxes staged in LDS per pass: 9 KiB of rows for either kind of list (constant velocity: rows of 9; polynomial: rows of 24)
 constexpr int kBoxChunk = 128, kBoxChunkPoly = 48;
 
-// (the polynomial object: box_p0 is the list's [nbox][kBoxRowPoly] rows, box_vel and box_scale are not read)
-template <bool COARSE>
+// (POLY, a polynomial list: box_p0 is the list's [nbox][kBoxRowPoly] rows, box_vel and box_scale are not read)
+template <bool COARSE, bool POLY>
 __global__ void __launch_bounds__(256)
 edt_query_kernel(const GtopGrid g, const double *__restrict__ field, const double *__restrict__ rec, int nbox,
                  const double *__restrict__ box_p0,
                  const double *__restrict__ box_vel, const double *__restrict__ box_scale, int N,
                  const double *__restrict__ pos, const double *__restrict__ time, double *__restrict__ dist,
                  double *__restrict__ grad) {
-  constexpr bool POLY = kQueryPoly;
-  constexpr int kChunk = POLY ? kBoxChunkPoly : kBoxChunk, kRow = POLY ? kBoxRowPoly : kBoxRowConstVel;
-  __shared__ double bx[kChunk][kRow];   // p0, vel, scale; POLY: the list's rows as they are
+  constexpr int kChunk = POLY ? kBoxChunkPoly : kBoxChunk;
+  __shared__ double bx[kChunk][kBoxRowOf<POLY>];   // p0, vel, scale; POLY: the list's rows as they are
   __shared__ double xyz[3 * 256];       // the workgroup's positions, later its gradients, as they lie in HBM
   const int tid = threadIdx.x;
   const size_t row0 = (size_t)blockIdx.x * 256;   // first query of the workgroup
@@ -100,17 +85,7 @@ edt_query_kernel(const GtopGrid g, const double *__restrict__ field, const doubl
   if constexpr (!COARSE) vmax = gtop_edt_vmax(values);
   for (int b0 = 0; b0 < nbox; b0 += kChunk) {
     const int nb = min(kChunk, nbox - b0);
-    __syncthreads();
-    if constexpr (POLY) {
-      for (int q = tid; q < nb * kRow; q += blockDim.x) (&bx[0][0])[q] = box_p0[(size_t)b0 * kRow + q];
-    } else {
-      for (int q = tid; q < nb * 9; q += blockDim.x) {
-        const int b = q / 9, f = q - 9 * b;
-        const double *src = f < 3 ? box_p0 : (f < 6 ? box_vel : box_scale);
-        bx[b][f] = src[3 * (size_t)(b0 + b) + (f % 3)];
-      }
-    }
-    __syncthreads();
+    stage_boxes<POLY>(bx, box_p0, box_vel, box_scale, b0, nb, tid, 256);
     if (dyn) {
       for (int b = 0; b < nb; ++b) {
         double bmin[3], bmax[3];
@@ -164,18 +139,19 @@ edt_query_kernel(const GtopGrid g, const double *__restrict__ field, const doubl
 hipError_t gtop_launch_edt_query(const GtopGrid &g, const double *field, const double *rec, const GtopBoxList &boxes, int N,
                                  const double *pos, const double *time, double *dist, double *grad, hipStream_t stream) {
   if (N <= 0) return hipSuccess;
-#ifndef GTOP_EDT_POLY_TU
-  if (boxes.kind == GTOP_BOX_LIST_POLYNOMIAL && boxes.count > 0)   // the other object's kernels
-    return gtop_launch_edt_query_poly(g, field, rec, boxes, N, pos, time, dist, grad, stream);
-#endif
-  // (the kernels' own parameters: the polynomial object's read the rows through the first pointer and not the others)
+  const bool poly = boxes.kind == GTOP_BOX_LIST_POLYNOMIAL && boxes.count > 0;
   const int nbox = boxes.count;
-  const double *box_p0 = kQueryPoly ? boxes.rows : boxes.p0, *box_vel = boxes.vel, *box_scale = boxes.scale;
-  if (grad)
-    hipLaunchKernelGGL(edt_query_kernel<false>, dim3((N + 255) / 256), dim3(256), 0, stream, g, field, rec, nbox, box_p0,
-                       box_vel, box_scale, N, pos, time, dist, grad);
-  else   // evaluateCoarseEDT: no interpolation, no gradient
-    hipLaunchKernelGGL(edt_query_kernel<true>, dim3((N + 255) / 256), dim3(256), 0, stream, g, field, rec, nbox, box_p0,
-                       box_vel, box_scale, N, pos, time, dist, grad);
+  const double *box_p0 = poly ? boxes.rows : boxes.p0, *box_vel = boxes.vel, *box_scale = boxes.scale;
+#define GTOP_QUERY_LAUNCH(COARSE_, POLY_)                                                                                 \
+  hipLaunchKernelGGL((edt_query_kernel<COARSE_, POLY_>), dim3((N + 255) / 256), dim3(256), 0, stream, g, field, rec, nbox, \
+                     box_p0, box_vel, box_scale, N, pos, time, dist, grad)
+  if (grad) {
+    if (poly) GTOP_QUERY_LAUNCH(false, true);
+    else GTOP_QUERY_LAUNCH(false, false);
+  } else {   // evaluateCoarseEDT: no interpolation, no gradient
+    if (poly) GTOP_QUERY_LAUNCH(true, true);
+    else GTOP_QUERY_LAUNCH(true, false);
+  }
+#undef GTOP_QUERY_LAUNCH
   return hipGetLastError();
 }

@@ -1,10 +1,11 @@
 // gtop_edt_lookup.h — the interpolating lookup of EDTEnvironment::evaluateEDTWithGrad
 // (src/edt_environment.cpp:76-122 of EpicOne1/grad_traj_optimization) as device
-// functions, shared by the batched query (gtop_edt.hip) and the trajectory report
-// (gtop_validate.hip): the in-map test, base index / diff / the 8 corner values
-// from the corner records, the min over one box with the exact skip, and the
+// functions, shared by the batched query (gtop_edt.hip) and the trajectory reports
+// (gtop_validate.hip and gtop_segments.hip, through gtop_report_common.h): the in-map
+// test, base index / diff / the 8 corner values from the corner records, the staging
+// of a box list in LDS, the min over one box with the exact skip, and the
 // trilinear value.  The library is built with -ffp-contract=on, so the same source
-// expression rounds the same way wherever it is inlined: both kernels get the same
+// expression rounds the same way wherever it is inlined: all of them get the same
 // distance, bit for bit.  The gradient stays with the query kernel.
 // The centre of a POLYNOMIAL box (gtop_set_moving_box_polynomials) is stated here once for those two kernels and for
 // the cost bodies (mov_min_boxes, gtop_wave_kernel.h).
@@ -27,29 +28,12 @@ __device__ __forceinline__ bool gtop_edt_out_of_map(const GtopGrid &g, const dou
   return out;
 }
 
-// base index and diff, sdf_map.cpp:201-209, and the 8 corner loads of sdf_map.cpp:211-219, each index clamped per axis
+// The 8 corner values of the cell of base index idx[]: the loads of sdf_map.cpp:211-219, each index clamped per axis
 // (getDistance(int,int,int), :166-174), from the CORNER RECORDS (gtop_records.hip): the two consecutive records of
 // levels iz and iz + 1 hold all eight, clamps applied — 64 contiguous bytes, four 16-byte loads at one address (round 3
 // read four (z, z+1) pairs from four lines: 4.24 lines of 128 bytes per query, 16 bytes used of each; now 1.25).
-__device__ __forceinline__ void gtop_edt_corners(const GtopGrid &g, const double *__restrict__ rec, const double p[3],
-                                                 int idx[3], double diff[3], double values[2][2][2]) {
-#pragma clang fp contract(off)
-  for (int k = 0; k < 3; ++k) {
-    const double pm = p[k] - 0.5 * g.res;
-    idx[k] = (int)floor((pm - g.origin[k]) * g.res_inv);
-    diff[k] = (p[k] - ((idx[k] + 0.5) * g.res + g.origin[k])) * g.res_inv;
-  }
-  typedef double d2 __attribute__((ext_vector_type(2)));
-  const int cx = min(max(idx[0], -1), g.nx - 1) + 1, cy = min(max(idx[1], -1), g.ny - 1) + 1;
-  const int cz = min(max(idx[2], -1), g.nz - 1) + 1;
-  const d2 *r = reinterpret_cast<const d2 *>(rec + 4 * (((size_t)cx * (g.ny + 1) + cy) * (g.nz + 2) + cz));
-  const d2 q0 = r[0], q1 = r[1], q2 = r[2], q3 = r[3];
-  values[0][0][0] = q0.x; values[0][1][0] = q0.y; values[1][0][0] = q1.x; values[1][1][0] = q1.y;
-  values[0][0][1] = q2.x; values[0][1][1] = q2.y; values[1][0][1] = q3.x; values[1][1][1] = q3.y;
-}
-
-// The 8 corner values of the cell of base index idx[], for a caller that has the index and no point (the certificate of
-// gtop_certify.hip, which visits the cells a box touches): the loads of gtop_edt_corners, clamps and all.
+// Called by gtop_edt_corners, and by a caller that has the index and no point (the certificate of gtop_certify.hip,
+// which visits the cells a box touches).
 __device__ __forceinline__ void gtop_edt_cell_values(const GtopGrid &g, const double *__restrict__ rec, const int idx[3],
                                                      double values[2][2][2]) {
   typedef double d2 __attribute__((ext_vector_type(2)));
@@ -59,6 +43,18 @@ __device__ __forceinline__ void gtop_edt_cell_values(const GtopGrid &g, const do
   const d2 q0 = r[0], q1 = r[1], q2 = r[2], q3 = r[3];
   values[0][0][0] = q0.x; values[0][1][0] = q0.y; values[1][0][0] = q1.x; values[1][1][0] = q1.y;
   values[0][0][1] = q2.x; values[0][1][1] = q2.y; values[1][0][1] = q3.x; values[1][1][1] = q3.y;
+}
+
+// base index and diff of the point p, sdf_map.cpp:201-209, and the 8 corner values of that cell
+__device__ __forceinline__ void gtop_edt_corners(const GtopGrid &g, const double *__restrict__ rec, const double p[3],
+                                                 int idx[3], double diff[3], double values[2][2][2]) {
+#pragma clang fp contract(off)
+  for (int k = 0; k < 3; ++k) {
+    const double pm = p[k] - 0.5 * g.res;
+    idx[k] = (int)floor((pm - g.origin[k]) * g.res_inv);
+    diff[k] = (p[k] - ((idx[k] + 0.5) * g.res + g.origin[k])) * g.res_inv;
+  }
+  gtop_edt_cell_values(g, rec, idx, values);
 }
 
 // the largest of the 8 corner values (0 at least): what a box has to undercut to matter
@@ -109,11 +105,33 @@ __device__ __forceinline__ void gtop_edt_box_faces_poly(const double *row, doubl
     bmin[k] = c - row[18 + k];
   }
 }
-// either list form (POLY: a constant of the object the query / report kernel is compiled into)
+// either list form (POLY: a template parameter of the query and report kernels)
 template <bool POLY>
 __device__ __forceinline__ void gtop_edt_box_faces_of(const double *row, double t, double bmin[3], double bmax[3]) {
   if constexpr (POLY) gtop_edt_box_faces_poly(row, t, bmin, bmax);
   else gtop_edt_box_faces(row, t, bmin, bmax);
+}
+template <bool POLY> constexpr int kBoxRowOf = POLY ? kBoxRowPoly : kBoxRowConstVel;
+
+// boxes b0 .. b0 + nb - 1 into LDS as rows of p0, vel, scale, by the whole workgroup.  (With one wavefront per workgroup
+// the barriers order that wavefront's own LDS reads and writes and nothing else.)
+// POLY: box_p0 is the list's [nbox][kBoxRowPoly] rows, copied as they are.
+template <bool POLY>
+__device__ __forceinline__ void stage_boxes(double (*bx)[kBoxRowOf<POLY>], const double *__restrict__ box_p0,
+                                            const double *__restrict__ box_vel, const double *__restrict__ box_scale,
+                                            int b0, int nb, int tid, int nthreads) {
+  constexpr int ROW = kBoxRowOf<POLY>;
+  __syncthreads();
+  if constexpr (POLY) {
+    for (int q = tid; q < nb * ROW; q += nthreads) (&bx[0][0])[q] = box_p0[(size_t)b0 * ROW + q];
+  } else {
+    for (int q = tid; q < nb * 9; q += nthreads) {
+      const int bb = q / 9, f = q - 9 * bb, k = f % 3;
+      const size_t e = 3 * (size_t)(b0 + bb) + k;
+      bx[bb][f] = f < 3 ? box_p0[e] : (f < 6 ? box_vel[e] : box_scale[e]);
+    }
+  }
+  __syncthreads();
 }
 
 // values := min(values, distance from each corner voxel's centre to the box) (edt_environment.cpp:26-73, :96-98)

@@ -197,24 +197,18 @@ struct GtopBoxList {
   const double *rows;               // polynomial (gtop_set_moving_box_polynomials): [count][kBoxRowPoly], gtop_edt_lookup.h
 };
 // field: the z-fastest fp64 buffer (the coarse query's voxel values); rec: its corner records (the interpolating query);
-// grad NULL: the coarse query.  gtop_edt.hip is compiled into two objects: the second (-DGTOP_EDT_POLY_TU) holds the
-// kernels for polynomial lists behind the _poly launcher, which gtop_launch_edt_query forwards to on `kind` and nobody
-// else calls.
-using GtopEdtQueryLauncher = hipError_t(const GtopGrid &g, const double *field, const double *rec, const GtopBoxList &boxes,
-                                        int N, const double *pos, const double *time, double *dist, double *grad,
-                                        hipStream_t stream);
-GtopEdtQueryLauncher gtop_launch_edt_query, gtop_launch_edt_query_poly;
+// grad NULL: the coarse query.
+hipError_t gtop_launch_edt_query(const GtopGrid &g, const double *field, const double *rec, const GtopBoxList &boxes, int N,
+                                 const double *pos, const double *time, double *dist, double *grad, hipStream_t stream);
 
 // ---- trajectory report + selection (gtop_validate.hip), fp64 -----------------
 #define GTOP_TRAJ_REPORT 12   // = include/gtop.h
 // report[b] of the trajectories (coeff, T) as include/gtop.h lays it out: the getTraj samples looked up as
 // edt_query_kernel<false> looks (pos, tau) up, tau = t0[b * t0_stride] + eval_t (t0 NULL = 0) — with no boxes static only
-// (gtop_validate.hip's second object, -DGTOP_REPORT_POLY_TU, holds the _poly launcher: forwarded to on `kind` as above)
-using GtopTrajReportLauncher = hipError_t(const GtopGrid &g, const double *rec, const GtopBoxList &boxes, int B, int m,
-                                          const double *coeff, const double *T, int t_stride, double dt_sample,
-                                          const double *t0, int t0_stride, double margin, double *report,
-                                          int simds /* of the device: sizes the launch */, hipStream_t stream);
-GtopTrajReportLauncher gtop_launch_traj_report, gtop_launch_traj_report_poly;
+hipError_t gtop_launch_traj_report(const GtopGrid &g, const double *rec, const GtopBoxList &boxes, int B, int m,
+                                   const double *coeff, const double *T, int t_stride, double dt_sample, const double *t0,
+                                   int t0_stride, double margin, double *report,
+                                   int simds /* of the device: sizes the launch */, hipStream_t stream);
 // pass[b] (may be NULL) and best[2] = {passing row of least cost (lowest index on a tie, -1 if none), passing rows};
 // two launches; workspace: GTOP_SELECT_PARTIALS x GTOP_SELECT_PARTIAL_BYTES bytes of device memory
 #define GTOP_SELECT_PARTIALS 256

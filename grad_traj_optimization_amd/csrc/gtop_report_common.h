@@ -1,16 +1,24 @@
-// gtop_report_common.h — the device helpers the trajectory report (gtop_validate.hip) and the per-segment report
-// (gtop_segments.hip) share: the polynomial's derivatives, the wavefront maximum and the staging of the box list in
-// LDS.  One statement of each, so that the two kernels form the same velocity, acceleration and distance bit for bit
-// (the library is built with -ffp-contract=on: the same source expression rounds the same way wherever it is inlined).
+// gtop_report_common.h — the sample loop of the kernels that walk a trajectory's getTraj samples one wavefront at a time,
+// lanes over the samples 64 at a time: the trajectory report (traj_report_kernel, gtop_validate.hip), the per-segment
+// report (traj_segments_kernel, gtop_segments.hip) and the post-processing (eval_trajectories_kernel, gtop_setup.hip).
+// What such a kernel does per sample is stated HERE, once: (a) the chunk's accumulated sample times, (b) the segment
+// walk, (c) position, velocity and acceleration, (d) the distance to the static field and the moving boxes — so count,
+// times, positions, velocities, accelerations and distances are the same bits in every one of them (the library is
+// built with -ffp-contract=on: the same source expression rounds the same way wherever it is inlined).  A kernel keeps
+// what it does with a sample: its reductions, its stores.
 #ifndef GTOP_REPORT_COMMON_H_
 #define GTOP_REPORT_COMMON_H_
 
 #include <hip/hip_runtime.h>
 
+#include "gtop_device_common.h"   // poly_eval
+#include "gtop_edt_lookup.h"
+
 constexpr int kValBoxChunk = 64;   // boxes staged in LDS per pass (4.5 KiB: 32 one-wavefront workgroups fit a CU)
-// The polynomial list's object: 32 rows of 24 per pass, the most the cost term takes: 6 KiB — 26 one-wavefront
-// workgroups of LDS per CU, where the kernel's 120 VGPRs admit 16.
+// A polynomial list: 32 rows of 24 per pass, the most the cost term takes: 6 KiB — 26 one-wavefront workgroups of LDS
+// per CU, where the kernel's 120 VGPRs admit 16.
 constexpr int kValBoxChunkPoly = 32;
+template <bool POLY> constexpr int kValBoxChunkOf = POLY ? kValBoxChunkPoly : kValBoxChunk;
 
 // first and second derivative of sum_j c[j] t^j.  Evaluation order (the quantity is fixed by the interface, the order
 // is this kernel's): the terms from the highest power down, as poly_eval sums the value, each term (j c_j) * t^(j-1)
@@ -39,24 +47,108 @@ __device__ __forceinline__ double wave_max(double v) {
   return v;
 }
 
-// boxes b0 .. b0 + nb - 1 into LDS as rows of p0, vel, scale, by the whole workgroup.  (With one wavefront per workgroup
-// the barriers order that wavefront's own LDS reads and writes and nothing else.)
-// POLY: box_p0 is the list's [nbox][kBoxRowPoly] rows, copied as they are.
-template <bool POLY, int ROW>
-__device__ __forceinline__ void stage_boxes(double (*bx)[ROW], const double *__restrict__ box_p0,
-                                            const double *__restrict__ box_vel, const double *__restrict__ box_scale,
-                                            int b0, int nb, int tid, int nthreads) {
-  __syncthreads();
-  if constexpr (POLY) {
-    for (int q = tid; q < nb * ROW; q += nthreads) (&bx[0][0])[q] = box_p0[(size_t)b0 * ROW + q];
-  } else {
-    for (int q = tid; q < nb * 9; q += nthreads) {
-      const int bb = q / 9, f = q - 9 * bb, k = f % 3;
-      const size_t e = 3 * (size_t)(b0 + bb) + k;
-      bx[bb][f] = f < 3 ? box_p0[e] : (f < 6 ? box_vel[e] : box_scale[e]);
+// ---- (a) the sample times ----
+// getTraj (polynomial_traj.hpp:69-78) accumulates the sample time (eval_t += dt_sample) and tests eval_t <= time_sum, so
+// the time of sample k is that sum, not k * dt_sample.  A wavefront's loop carries base_t, the time of its chunk's
+// sample 0, and runs `while (base_t <= time_sum)`.
+// The time of sample `skip` by the same additions, one after the other: base_t of a wavefront's first chunk (0 for the
+// only wavefront of a trajectory).
+__device__ __forceinline__ double sample_time_of(int skip, double dt_sample) {
+  double base_t = 0.0;
+  for (int i = 0; i < skip; ++i) base_t += dt_sample;
+  return base_t;
+}
+// One chunk: eval_t, the accumulated time of the lane's sample; live, whether that sample exists (monotone in the lane
+// index); next_base, base_t of this wavefront's next chunk, `stride` samples on (64 times the wavefronts that share the
+// trajectory).
+struct ChunkTimes {
+  double eval_t, next_base;
+  bool live;
+};
+__device__ __forceinline__ ChunkTimes chunk_times(double base_t, double dt_sample, int lane, int stride, double time_sum) {
+  ChunkTimes c;
+  c.eval_t = base_t;
+  for (int i = 0; i < lane; ++i) c.eval_t += dt_sample;
+  c.next_base = base_t;
+  for (int i = 0; i < stride; ++i) c.next_base += dt_sample;
+  c.live = c.eval_t <= time_sum;
+  return c;
+}
+
+// ---- (b) the segment walk ----
+// polynomial_traj.hpp:48-51: the segment trajectory time t falls into; t becomes the time inside it.  The reference
+// walks off the end when t == time_sum exactly; here the last segment is extended instead.
+// (unsigned, and to be kept so where it indexes the coefficients: through the inlined call the compiler no longer sees
+// that the index is non-negative, and a signed one costs a sign extension in the address and a different schedule —
+// 8 % of eval_trajectories_kernel's time at 1 024 trajectories.)
+__device__ __forceinline__ unsigned segment_of(const double *ts, int m, double &t) {
+  unsigned idx = 0;
+  while ((int)idx < m - 1 && ts[idx] <= t) {
+    t -= ts[idx];
+    ++idx;
+  }
+  return idx;
+}
+
+// ---- (c) position, velocity, acceleration ----
+// of the sample at time t of the segment with the coefficient row seg = [cx0..5 | cy0..5 | cz0..5], and the running
+// maxima they enter: per axis (vax, aax) and of the squared norms (vmax2, amax2: sqrt is monotone, taken by the caller
+// once at the end).
+__device__ __forceinline__ void sample_motion(const double *seg, double t, double p[3], double &vax, double &aax,
+                                              double &vmax2, double &amax2) {
+  double v[3], a[3];
+  for (int k = 0; k < 3; ++k) {
+    const double *c = seg + 6 * k;
+    p[k] = poly_eval(c, t);
+    v[k] = poly_vel(c, t);
+    a[k] = poly_acc(c, t);
+    vax = fmax(vax, fabs(v[k]));
+    aax = fmax(aax, fabs(a[k]));
+  }
+  vmax2 = fmax(vmax2, v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+  amax2 = fmax(amax2, a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
+}
+
+// ---- (d) the distance ----
+// evaluateEDTWithGrad(pos, tau)'s value at the lane's sample, as edt_query_kernel<false, POLY> forms it:
+// tau = start + eval_t with boxes and -1 (static only) without; d = -1 out of the map.  bx holds the list's first
+// kValBoxChunkOf<POLY> boxes, staged by the caller before its loop.  A longer list is restaged chunk by chunk HERE
+// (RESTAGE), inside the sample loop, which only a one-wavefront workgroup can do: stage_boxes' barriers then sit in a
+// loop that a workgroup's wavefronts leave at different times.  Wave-uniform control flow around the call.
+// (A dead lane looks p = 0 up: clamped indices, memory-safe.)
+struct SampleDistance {
+  double d;
+  bool out;
+};
+template <bool POLY, bool RESTAGE>
+__device__ __forceinline__ SampleDistance sample_distance(const GtopGrid &g, const double *__restrict__ rec,
+                                                          double (*bx)[kBoxRowOf<POLY>], int nbox,
+                                                          const double *__restrict__ box_p0,
+                                                          const double *__restrict__ box_vel,
+                                                          const double *__restrict__ box_scale, bool use_boxes,
+                                                          double start, double eval_t, bool live, const double p[3],
+                                                          int lane) {
+  constexpr int kChunk = kValBoxChunkOf<POLY>;
+  const double tau = use_boxes ? start + eval_t : -1.0;
+  const bool out = gtop_edt_out_of_map(g, p);
+  const bool dyn = live & !out & (tau >= 0.0);
+  int idx[3];
+  double diff[3], values[2][2][2];
+  gtop_edt_corners(g, rec, p, idx, diff, values);
+  double vmax = gtop_edt_vmax(values);
+  for (int b0 = 0; b0 < nbox; b0 += kChunk) {
+    const int nb = min(kChunk, nbox - b0);
+    if constexpr (RESTAGE)
+      if (nbox > kChunk) stage_boxes<POLY>(bx, box_p0, box_vel, box_scale, b0, nb, lane, 64);   // wave-uniform
+    if (dyn) {
+      for (int q = 0; q < nb; ++q) {
+        double bmin[3], bmax[3];
+        gtop_edt_box_faces_of<POLY>(bx[q], tau, bmin, bmax);
+        gtop_edt_box_min(g, bmin, bmax, idx, values, vmax);
+      }
     }
   }
-  __syncthreads();
+  return {out ? -1.0 : gtop_edt_trilinear(diff, values).d, out};
 }
 
 #endif  // GTOP_REPORT_COMMON_H_

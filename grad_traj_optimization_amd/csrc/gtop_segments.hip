@@ -4,9 +4,10 @@
 // The whole-trajectory report (traj_report_kernel, gtop_validate.hip) says THAT a row fails and at which sample its
 // clearance is least; a caller who wants to repair the row — insert a waypoint, stretch a time — needs the same figures
 // per segment.  The samples, the segment each one belongs to, positions, velocities, accelerations and distances are
-// that kernel's statement for statement: the accumulated eval_t, the walk `while (idx < m-1 && ts[idx] <= t)` with the
-// last segment extended, poly_eval / poly_vel / poly_acc, the lookup of gtop_edt_lookup.h at tau = t0[b] + eval_t with
-// boxes and -1 without.  The same source expressions in a library built with -ffp-contract=on: the same bits.
+// that kernel's: both take them from the one statement of the sample loop in gtop_report_common.h (the accumulated
+// eval_t, the segment walk with the last segment extended, poly_eval / poly_vel / poly_acc, the lookup of
+// gtop_edt_lookup.h at tau = t0[b] + eval_t with boxes and -1 without), so they are the same bits.  This file holds
+// what is done with a sample here: the reduction per segment.
 //
 // One WAVEFRONT per trajectory, lanes over the samples 64 at a time.  A sample's segment never falls as the sample
 // index rises, so the members of one segment are a run of lanes.  Inside a chunk the wavefront loops over the distinct
@@ -67,8 +68,8 @@ traj_segments_kernel(const GtopGrid g, const double *__restrict__ rec, int nbox,
                      const double *__restrict__ coeff, const double *__restrict__ T, int t_stride, double dt_sample,
                      const double *__restrict__ t0, int t0_stride, double margin,
                      double *__restrict__ seg_report /*[B][m][GTOP_SEG_REPORT]*/) {
-  constexpr int kChunk = POLY ? kValBoxChunkPoly : kValBoxChunk, kRow = POLY ? kBoxRowPoly : kBoxRowConstVel;
-  __shared__ double bx[kChunk][kRow];   // p0, vel, scale; POLY: the list's rows
+  constexpr int kChunk = kValBoxChunkOf<POLY>;
+  __shared__ double bx[kChunk][kBoxRowOf<POLY>];   // p0, vel, scale; POLY: the list's rows
   const int b = blockIdx.x, lane = threadIdx.x;
   if (b >= B) return;
   const double *cf = coeff + (size_t)b * m * 18;   // row s = [cx0..5 | cy0..5 | cz0..5], ascending powers
@@ -89,54 +90,18 @@ traj_segments_kernel(const GtopGrid g, const double *__restrict__ rec, int nbox,
   double base_t = 0.0;                              // the time of the chunk's sample 0
   int first = 0;                                    // its index
   while (base_t <= time_sum) {                      // wave-uniform
-    double eval_t = base_t;
-    for (int i = 0; i < lane; ++i) eval_t += dt_sample;          // the accumulated time of sample first + lane
-    double next_base = base_t;
-    for (int i = 0; i < 64; ++i) next_base += dt_sample;
-    const bool live = eval_t <= time_sum;           // monotone in the lane index
+    const auto [eval_t, next_base, live] = chunk_times(base_t, dt_sample, lane, 64, time_sum);   // sample first + lane
     double p[3] = {0, 0, 0};
     int seg = -1;
     double v2 = 0.0, a2 = 0.0, vax = 0.0, aax = 0.0;   // this sample's; squared norms: sqrt is monotone, taken at the store
     if (live) {
       double t = eval_t;
-      int idx = 0;
-      while (idx < m - 1 && ts[idx] <= t) {   // polynomial_traj.hpp:48-51, as eval_trajectories_kernel walks it
-        t -= ts[idx];
-        ++idx;
-      }
+      const unsigned idx = segment_of(ts, m, t);
       seg = idx;
-      double v[3], a[3];
-      for (int k = 0; k < 3; ++k) {
-        const double *c = cf + idx * 18 + 6 * k;
-        p[k] = poly_eval(c, t);
-        v[k] = poly_vel(c, t);
-        a[k] = poly_acc(c, t);
-        vax = fmax(vax, fabs(v[k]));
-        aax = fmax(aax, fabs(a[k]));
-      }
-      v2 = fmax(v2, v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
-      a2 = fmax(a2, a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
+      sample_motion(cf + idx * 18, t, p, vax, aax, v2, a2);
     }
-    // evaluateEDTWithGrad(pos, tau)'s value, as edt_query_kernel<false> and traj_report_kernel form it
-    const double tau = use_boxes ? start + eval_t : -1.0;
-    const bool out = gtop_edt_out_of_map(g, p);
-    const bool dyn = live & !out & (tau >= 0.0);
-    int idx[3];
-    double diff[3], values[2][2][2];
-    gtop_edt_corners(g, rec, p, idx, diff, values);   // (a dead lane looks p = 0 up: clamped indices, memory-safe)
-    double vmax = gtop_edt_vmax(values);
-    for (int b0 = 0; b0 < nbox; b0 += kChunk) {
-      const int nb = min(kChunk, nbox - b0);
-      if (nbox > kChunk) stage_boxes<POLY>(bx, box_p0, box_vel, box_scale, b0, nb, lane, 64);   // wave-uniform
-      if (dyn) {
-        for (int q = 0; q < nb; ++q) {
-          double bmin[3], bmax[3];
-          gtop_edt_box_faces_of<POLY>(bx[q], tau, bmin, bmax);
-          gtop_edt_box_min(g, bmin, bmax, idx, values, vmax);
-        }
-      }
-    }
-    const double d = out ? -1.0 : gtop_edt_trilinear(diff, values).d;
+    const auto [d, out] = sample_distance<POLY, true>(g, rec, bx, nbox, box_p0, box_vel, box_scale, use_boxes, start,
+                                                      eval_t, live, p, lane);
 
     // ---- the chunk's segments, in rising order ----
     unsigned long long todo = __ballot(live);

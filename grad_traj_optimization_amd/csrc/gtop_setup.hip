@@ -19,6 +19,7 @@
 
 #include "gtop_device_common.h"
 #include "gtop_kernels.h"
+#include "gtop_report_common.h"   // the sample times and the segment walk, shared with the reports
 
 #pragma clang fp contract(off)   // keep the reference's unfused arithmetic (bit-exact setup)
 
@@ -65,7 +66,8 @@ setup_paths_kernel(int B, int m, const double *__restrict__ wp, double mean_v, d
 //     reference accumulates the sample time (eval_t += 0.01) and tests eval_t <= time_sum, so the time of sample
 //     k is that sum, not k*dt: every chunk starts from the carried accumulated value and lane l adds dt l times
 //     (64 predicated additions per chunk) — sample count and sample
-//     times are the reference's exactly.  A lane's neighbour's point arrives through a wavefront shuffle, the
+//     times are the reference's exactly.  (Times and segment walk: chunk_times and segment_of of gtop_report_common.h,
+//     which the trajectory reports run too.)  A lane's neighbour's point arrives through a wavefront shuffle, the
 //     previous chunk's last point through a broadcast; the length is a wavefront sum (summation order differs from
 //     the serial sum: ~1e-16).
 //   * getAccCost, getJerk, getMeanAndMaxVel/Acc (:96-204): one lane per segment, then wavefront sums / maxima.
@@ -88,21 +90,13 @@ eval_trajectories_kernel(int B, int m, const double *__restrict__ coeff, const d
   // ---- getTraj + getLength ----
   double length = 0.0, base_t = 0.0, carry[3] = {0, 0, 0};
   int nsamp = 0;
-  bool first_chunk = true;
+  bool later_chunk = false;
   while (base_t <= time_sum) {                      // wave-uniform: base_t is the time of the chunk's sample 0
-    double eval_t = base_t;
-    for (int i = 0; i < lane; ++i) eval_t += dt_sample;          // the accumulated time of sample chunk*64 + lane
-    double next_base = base_t;
-    for (int i = 0; i < 64; ++i) next_base += dt_sample;
-    const bool live = eval_t <= time_sum;           // monotone in the lane index
+    const auto [eval_t, next_base, live] = chunk_times(base_t, dt_sample, lane, 64, time_sum);   // sample chunk*64 + lane
     double pn[3] = {0, 0, 0};
     if (live) {
       double t = eval_t;
-      int idx = 0;
-      while (idx < m - 1 && ts[idx] <= t) {   // :48-51; the reference walks off the end when t == time_sum exactly,
-        t -= ts[idx];                          // here the last segment is extended instead
-        ++idx;
-      }
+      const unsigned idx = segment_of(ts, m, t);   // :48-51
       for (int a = 0; a < 3; ++a) pn[a] = poly_eval(cf + idx * 18 + 6 * a, t);
       if (samples && nsamp + lane < max_samples) {
         double *o = samples + ((size_t)b * max_samples + nsamp + lane) * 3;
@@ -116,7 +110,7 @@ eval_trajectories_kernel(int B, int m, const double *__restrict__ coeff, const d
       pl[a] = lane == 0 ? carry[a] : up;
     }
     double seg = 0.0;
-    if (live && !(first_chunk && lane == 0)) {
+    if (live && (lane != 0 || later_chunk)) {   // (the trajectory's first sample has no predecessor)
       const double dx = pn[0] - pl[0], dy = pn[1] - pl[1], dz = pn[2] - pl[2];
       seg = sqrt(dx * dx + dy * dy + dz * dz);
     }
@@ -125,7 +119,7 @@ eval_trajectories_kernel(int B, int m, const double *__restrict__ coeff, const d
     const int cnt = __popcll(mask);
     nsamp += cnt;
     for (int a = 0; a < 3; ++a) carry[a] = __shfl(pn[a], cnt - 1);   // (cnt >= 1: lane 0 is live)
-    first_chunk = false;
+    later_chunk = true;
     base_t = next_base;
   }
 

@@ -9,12 +9,13 @@
 // lookup EDTEnvironment::evaluateEDTWithGrad (src/edt_environment.cpp:76-122).
 //
 // (1) traj_report_kernel: one WAVEFRONT per trajectory (a few for small batches,
-//     see the kernel), lanes over the samples 64 at a time — the structure of eval_trajectories_kernel (gtop_setup.hip), whose
-//     sample loop this is statement for statement (accumulated eval_t, the segment
-//     walk, poly_eval), so count, times and positions are the bits
-//     gtop_sample_trajectories_device stores.  Each sample's distance is the `dist`
-//     of edt_query_kernel<false> (gtop_edt.hip) for (pos, tau), through the shared
-//     lookup of gtop_edt_lookup.h: the same bits again.  Nothing per sample goes to
+//     see the kernel), lanes over the samples 64 at a time.  What happens per sample
+//     is stated once, in gtop_report_common.h: the accumulated eval_t and the segment
+//     walk are eval_trajectories_kernel's (gtop_setup.hip) too, so count, times and
+//     positions are the bits gtop_sample_trajectories_device stores.  Each sample's
+//     distance is the `dist` of edt_query_kernel<false, POLY> (gtop_edt.hip) for
+//     (pos, tau), through the shared lookup of gtop_edt_lookup.h: the same bits again.
+//     This file holds what the report does with a sample.  Nothing per sample goes to
 //     HBM: per sample one 64-byte gather, ~100 fp64 operations and the box loop; per
 //     trajectory 96 bytes out.
 // (2) select_kernel / select_finish_kernel: the pass test per row and the passing
@@ -28,21 +29,7 @@
 #include "gtop_device_common.h"
 #include "gtop_edt_lookup.h"
 #include "gtop_kernels.h"
-#include "gtop_report_common.h"   // poly_vel, poly_acc, wave_max, stage_boxes, kValBoxChunk[Poly]
-
-// This file is compiled TWICE (csrc/Makefile), as gtop_kernels.hip is: as it stands — the report kernel for
-// constant-velocity box lists, the selection kernels and the launchers the C-ABI layer calls — and with
-// -DGTOP_REPORT_POLY_TU into an object of its own that holds only the report kernel for POLYNOMIAL box lists
-// (gtop_set_moving_box_polynomials; rows of kBoxRowPoly = 24 doubles, gtop_edt_lookup.h) behind a launcher named
-// gtop_launch_traj_report_poly, which the first object's launcher forwards to.  Two objects so that the kernels of the
-// first keep their names and their code, and a constant-velocity launch stages the rows it always staged.
-#ifdef GTOP_REPORT_POLY_TU
-#define traj_report_kernel traj_report_poly_kernel
-#define gtop_launch_traj_report gtop_launch_traj_report_poly
-constexpr bool kReportPoly = true;
-#else
-constexpr bool kReportPoly = false;
-#endif
+#include "gtop_report_common.h"   // the sample loop's four parts, wave_max, kValBoxChunk[Poly]
 
 namespace {
 
@@ -65,16 +52,17 @@ struct ReportPartial {
   int dmin_i, below_i, nsamp;
 };
 
-template <int W>
+// POLY: the list is a polynomial one (gtop_set_moving_box_polynomials): box_p0 is its [nbox][kBoxRowPoly] rows
+// (gtop_edt_lookup.h), box_vel and box_scale are not read.
+template <int W, bool POLY>
 __global__ void __launch_bounds__(64 * W)
 traj_report_kernel(const GtopGrid g, const double *__restrict__ rec, int nbox, const double *__restrict__ box_p0,
                    const double *__restrict__ box_vel, const double *__restrict__ box_scale, int B, int m,
                    const double *__restrict__ coeff, const double *__restrict__ T, int t_stride, double dt_sample,
                    const double *__restrict__ t0, int t0_stride, double margin,
                    double *__restrict__ report /*[B][GTOP_TRAJ_REPORT]*/) {
-  constexpr bool POLY = kReportPoly;
-  constexpr int kChunk = POLY ? kValBoxChunkPoly : kValBoxChunk, kRow = POLY ? kBoxRowPoly : kBoxRowConstVel;
-  __shared__ double bx[kChunk][kRow];   // p0, vel, scale; POLY: the list's rows
+  constexpr int kChunk = kValBoxChunkOf<POLY>;
+  __shared__ double bx[kChunk][kBoxRowOf<POLY>];   // p0, vel, scale; POLY: the list's rows
   __shared__ ReportPartial part[W];
   const int b = blockIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   if (b >= B) return;
@@ -92,56 +80,18 @@ traj_report_kernel(const GtopGrid g, const double *__restrict__ rec, int nbox, c
   int dmin_i = 0x7fffffff, below_i = 0x7fffffff, n_below = 0, n_out = 0;
   double vmax2 = 0.0, amax2 = 0.0, vax = 0.0, aax = 0.0;   // squared norms: sqrt is monotone, taken once at the end
 
-  double base_t = 0.0;                              // the time of this wavefront's first chunk's sample 0
-  for (int i = 0; i < 64 * w; ++i) base_t += dt_sample;
+  double base_t = sample_time_of(64 * w, dt_sample);   // the time of this wavefront's first chunk's sample 0
   int first = 64 * w, nsamp = 0;                    // index of the chunk's sample 0; samples this wavefront saw
   while (base_t <= time_sum) {                      // wave-uniform
-    double eval_t = base_t;
-    for (int i = 0; i < lane; ++i) eval_t += dt_sample;          // the accumulated time of sample first + lane
-    double next_base = base_t;
-    for (int i = 0; i < 64 * W; ++i) next_base += dt_sample;
-    const bool live = eval_t <= time_sum;           // monotone in the lane index
+    const auto [eval_t, next_base, live] = chunk_times(base_t, dt_sample, lane, 64 * W, time_sum);   // sample first + lane
     double p[3] = {0, 0, 0};
     if (live) {
       double t = eval_t;
-      int idx = 0;
-      while (idx < m - 1 && ts[idx] <= t) {   // polynomial_traj.hpp:48-51, as eval_trajectories_kernel walks it
-        t -= ts[idx];
-        ++idx;
-      }
-      double v[3], a[3];
-      for (int k = 0; k < 3; ++k) {
-        const double *c = cf + idx * 18 + 6 * k;
-        p[k] = poly_eval(c, t);
-        v[k] = poly_vel(c, t);
-        a[k] = poly_acc(c, t);
-        vax = fmax(vax, fabs(v[k]));
-        aax = fmax(aax, fabs(a[k]));
-      }
-      vmax2 = fmax(vmax2, v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
-      amax2 = fmax(amax2, a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
+      const unsigned seg = segment_of(ts, m, t);
+      sample_motion(cf + seg * 18, t, p, vax, aax, vmax2, amax2);
     }
-    // evaluateEDTWithGrad(pos, tau)'s value, as edt_query_kernel<false> forms it
-    const double tau = use_boxes ? start + eval_t : -1.0;
-    const bool out = gtop_edt_out_of_map(g, p);
-    const bool dyn = live & !out & (tau >= 0.0);
-    int idx[3];
-    double diff[3], values[2][2][2];
-    gtop_edt_corners(g, rec, p, idx, diff, values);   // (a dead lane looks p = 0 up: clamped indices, memory-safe)
-    double vmax = gtop_edt_vmax(values);
-    for (int b0 = 0; b0 < nbox; b0 += kChunk) {
-      const int nb = min(kChunk, nbox - b0);
-      if constexpr (W == 1)
-        if (nbox > kChunk) stage_boxes<POLY>(bx, box_p0, box_vel, box_scale, b0, nb, lane, 64);   // wave-uniform
-      if (dyn) {
-        for (int q = 0; q < nb; ++q) {
-          double bmin[3], bmax[3];
-          gtop_edt_box_faces_of<POLY>(bx[q], tau, bmin, bmax);
-          gtop_edt_box_min(g, bmin, bmax, idx, values, vmax);
-        }
-      }
-    }
-    const double d = out ? -1.0 : gtop_edt_trilinear(diff, values).d;
+    const auto [d, out] = sample_distance<POLY, W == 1>(g, rec, bx, nbox, box_p0, box_vel, box_scale, use_boxes, start,
+                                                        eval_t, live, p, lane);
     if (live) {
       const int k = first + lane;
       if (d < dmin) {
@@ -214,7 +164,6 @@ traj_report_kernel(const GtopGrid g, const double *__restrict__ rec, int nbox, c
   }
 }
 
-#ifndef GTOP_REPORT_POLY_TU   // (the selection: the first object's alone)
 // ---- selection ----
 struct SelLimits {
   double max_vel, max_acc;
@@ -301,13 +250,9 @@ select_finish_kernel(int nparts, const SelPartial *__restrict__ part, int *__res
   }
 }
 
-#endif  // GTOP_REPORT_POLY_TU
-
 }  // namespace
 
-#ifndef GTOP_REPORT_POLY_TU
 static_assert(sizeof(SelPartial) == GTOP_SELECT_PARTIAL_BYTES, "the context sizes the selection workspace by this");
-#endif
 
 hipError_t gtop_launch_traj_report(const GtopGrid &g, const double *rec, const GtopBoxList &boxes, int B, int m,
                                    const double *coeff, const double *T, int t_stride, double dt_sample, const double *t0,
@@ -319,26 +264,26 @@ hipError_t gtop_launch_traj_report(const GtopGrid &g, const double *rec, const G
   // wavefronts only queue behind the resident ones, and each pays the 64 W dependent additions per chunk that carry
   // its sample time; see the kernel's comment
   const long long resident = (long long)kReportWavesPerSimd * (simds > 0 ? simds : 1);
-#ifndef GTOP_REPORT_POLY_TU
-  if (boxes.kind == GTOP_BOX_LIST_POLYNOMIAL && boxes.count > 0)   // the other object's kernel
-    return gtop_launch_traj_report_poly(g, rec, boxes, B, m, coeff, T, t_stride, dt_sample, t0, t0_stride, margin, report,
-                                        simds, stream);
-#endif
-  // (the kernel's own parameters: the polynomial object's reads the rows through the first pointer and not the others)
+  const bool poly = boxes.kind == GTOP_BOX_LIST_POLYNOMIAL && boxes.count > 0;
   const int nbox = boxes.count;
-  const double *box_p0 = kReportPoly ? boxes.rows : boxes.p0, *box_vel = boxes.vel, *box_scale = boxes.scale;
-  const int W = nbox > (kReportPoly ? kValBoxChunkPoly : kValBoxChunk) ? 1 : (4LL * B <= resident ? 4 : (2LL * B <= resident ? 2 : 1));
-#define GTOP_REPORT_LAUNCH(W_)                                                                                          \
-  hipLaunchKernelGGL(traj_report_kernel<W_>, dim3(B), dim3(64 * W_), 0, stream, g, rec, nbox, box_p0, box_vel, box_scale, \
-                     B, m, coeff, T, t_stride, dt_sample, t0, t0_stride, margin, report)
-  if (W == 4) GTOP_REPORT_LAUNCH(4);
-  else if (W == 2) GTOP_REPORT_LAUNCH(2);
-  else GTOP_REPORT_LAUNCH(1);
+  const double *box_p0 = poly ? boxes.rows : boxes.p0, *box_vel = boxes.vel, *box_scale = boxes.scale;
+  const int W = nbox > (poly ? kValBoxChunkPoly : kValBoxChunk) ? 1 : (4LL * B <= resident ? 4 : (2LL * B <= resident ? 2 : 1));
+#define GTOP_REPORT_LAUNCH(W_, POLY_)                                                                                    \
+  hipLaunchKernelGGL((traj_report_kernel<W_, POLY_>), dim3(B), dim3(64 * W_), 0, stream, g, rec, nbox, box_p0, box_vel,  \
+                     box_scale, B, m, coeff, T, t_stride, dt_sample, t0, t0_stride, margin, report)
+  if (poly) {
+    if (W == 4) GTOP_REPORT_LAUNCH(4, true);
+    else if (W == 2) GTOP_REPORT_LAUNCH(2, true);
+    else GTOP_REPORT_LAUNCH(1, true);
+  } else {
+    if (W == 4) GTOP_REPORT_LAUNCH(4, false);
+    else if (W == 2) GTOP_REPORT_LAUNCH(2, false);
+    else GTOP_REPORT_LAUNCH(1, false);
+  }
 #undef GTOP_REPORT_LAUNCH
   return hipGetLastError();
 }
 
-#ifndef GTOP_REPORT_POLY_TU
 hipError_t gtop_launch_select_best(int B, const double *report, const double *cost, double max_vel, double max_acc,
                                    int per_axis, int allow_out_of_map, const double *cert, int require,
                                    unsigned char *pass, int *best, void *workspace, hipStream_t stream) {
@@ -354,4 +299,3 @@ hipError_t gtop_launch_select_best(int B, const double *report, const double *co
   hipLaunchKernelGGL(select_finish_kernel, dim3(1), dim3(256), 0, stream, nblocks, part, best);
   return hipGetLastError();
 }
-#endif  // GTOP_REPORT_POLY_TU

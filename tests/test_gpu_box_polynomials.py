@@ -347,6 +347,76 @@ def test_a_list_frozen_at_one_time_is_a_list_of_parked_boxes(gtop, oracle_mod, w
     _reset(ctx)
 
 
+@pytest.mark.parametrize("nbox", [33, 49])
+def test_a_frozen_list_longer_than_one_stage_is_the_parked_list(gtop, oracle_mod, world, nbox):
+    """A POLYNOMIAL list of more boxes than one LDS stage holds — 33: the whole-trajectory report takes 32 a stage and
+    restages inside its sample loop; 49: the query takes 48 — under the frozen-list law: every box with t1 = t2 = T*,
+    against the same boxes parked at the twin's c(T*) with zero velocity through gtop_set_moving_boxes, a list that is
+    one stage in both kernels.  The report, the segment report, the query's distance and gradient and the coarse query
+    are bit-identical between the two kinds; the report's clearance is the query's minimum over the report's own
+    samples; and the LAST box, put on the middle waypoint of the row with the most clearance, decides that row's
+    clearance, so the boxes behind the first stage are read.  The (6, 8) case's 48 rows of 6 segments."""
+    mp, sdf, ctx = world
+    _reset(ctx)
+    k = poly_case(oracle_mod, mp, sdf, 6, 8)
+    b, t0 = k["b"], k["t0"]
+    B, margin = len(b.x), 0.3
+    lim = gtop.GtopLimits(margin=margin, use_boxes=1)
+    rng = np.random.default_rng(7000 + nbox)
+    coef, scale, _ = aimed_polynomials(b, t0, rng, nbox)
+    scale *= 0.4                                     # many boxes: smaller ones, so that rows keep some clearance
+    t_star = rng.uniform(1.0, 6.0, nbox)
+    frozen = np.stack([t_star, t_star], axis=1)
+    ctx.set_problem(b.T, b.Df)
+    ctx.set_start_times(t0)
+    # the list without its last box is one stage in the kernel the case is about; the last box goes where it matters
+    ctx.set_moving_box_polynomials(coef[:-1], scale[:-1], frozen[:-1])
+    rep_less, _, _ = ctx.validate_batch(b.x, lim)
+    row = int(np.argmax(rep_less[:, 1]))
+    assert rep_less[row, 1] > 0.0
+    coef[-1] = 0.0
+    coef[-1, :, 0], scale[-1] = b.waypoints[row, (b.m + 1) // 2], 0.8
+    parked = np.array([bpt.centres(coef[i:i + 1], t_star[i], fma_=bpt.fma_fraction)[0] for i in range(nbox)])
+    pos, tau, counts, times = _samples(ctx, b, t0)
+    dist_less, _ = ctx.edt_query(pos, tau)
+
+    def everything():
+        rep, _, _ = ctx.validate_batch(b.x, lim)
+        d, dg = ctx.edt_query(pos, tau)
+        return dict(report=rep, segments=ctx.validate_segments(b.x, lim), dist=d, dist_grad=dg,
+                    coarse=ctx.edt_coarse_query(pos, tau))
+
+    ctx.set_moving_boxes(parked, np.zeros((nbox, 3)), scale)
+    assert ctx.moving_box_kind() == (gtop.GtopContext.BOXES_CONST_VEL, nbox)
+    want = everything()
+    ctx.set_moving_box_polynomials(coef, scale, frozen)
+    assert ctx.moving_box_kind() == (gtop.GtopContext.BOXES_POLYNOMIAL, nbox)
+    got = everything()
+    for name in want:
+        assert np.array_equal(want[name], got[name]), name
+    # the report's clearance is the minimum of the query at the report's own samples
+    rep, dist = got["report"], got["dist"]
+    o = 0
+    for i in range(B):
+        d = dist[o:o + counts[i]]
+        j = int(np.argmin(d))
+        assert (rep[i, 0], rep[i, 1], rep[i, 2], rep[i, 3]) == (counts[i], d[j], times[i][j], j), i
+        below = np.flatnonzero(d <= margin)
+        assert rep[i, 4] == len(below) and rep[i, 5] == (times[i][below[0]] if len(below) else -1.0), i
+        o += counts[i]
+    # the last box of the list is read: it lowers its row's clearance, and nothing rises
+    print(f"{nbox} boxes: row {row}, clearance {rep_less[row, 1]:.3f} without the last box, {rep[row, 1]:.3f} with it")
+    assert np.all(rep[:, 1] <= rep_less[:, 1]) and rep[row, 1] < rep_less[row, 1]
+    assert np.all(dist <= dist_less) and np.any(dist < dist_less)
+    seg_row = got["segments"][row]
+    assert seg_row[:, 2].min() == rep[row, 1]
+    # the clamp acts: the same list running free gives another report
+    ctx.set_moving_box_polynomials(coef, scale)
+    free, _, _ = ctx.validate_batch(b.x, lim)
+    assert not np.array_equal(free, rep)
+    _reset(ctx)
+
+
 def test_report_clearance_is_the_minimum_of_the_query_and_matches_the_twin(gtop, oracle_mod, world):
     """The (6, 8) case.  (c) edt_query at the report's own samples: its minimum per trajectory IS report[:, 1], bit for
     bit, with the first index and time.  (4) validate_batch with use_boxes against tests/validate_twin.py fed the twin's

@@ -192,7 +192,7 @@ def test_report_kernels_use_no_scratch_memory(tmp_path):
     spec.loader.exec_module(kr)
     rows, _ = kr.analyse(asm_out=str(tmp_path / "gtop_validate.s"), source="gtop_validate.hip")
     names = sorted(r["kernel"] for r in rows)
-    assert names == ["select_finish_kernel", "select_kernel", "traj_report_kernel<1>", "traj_report_kernel<2>",
-                     "traj_report_kernel<4>"], names
+    assert names == ["select_finish_kernel", "select_kernel"] + [
+        f"traj_report_kernel<{w}, {poly}>" for w in (1, 2, 4) for poly in ("false", "true")], names
     bad = [r for r in rows if r["scratch"] or r["vgpr_spill"]]
     assert not bad, bad
