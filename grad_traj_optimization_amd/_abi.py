@@ -76,10 +76,20 @@ class GtopCertifyOpts(C.Structure):
         super().__init__(float(margin), int(max_depth), int(max_refine))
 
 
+class GtopCertifyMovingOpts(C.Structure):
+    """gtop_certify_moving_opts of include/gtop.h: GtopCertifyOpts' three fields, use_boxes (False: the static
+    certificate, bit for bit) and a reserved word that must be 0."""
+    _fields_ = [("margin", C.c_double), ("max_depth", C.c_int32), ("max_refine", C.c_int32), ("use_boxes", C.c_int32),
+                ("reserved", C.c_int32)]
+
+    def __init__(self, margin=0.0, max_depth=2, max_refine=256, use_boxes=True, reserved=0):
+        super().__init__(float(margin), int(max_depth), int(max_refine), int(bool(use_boxes)), int(reserved))
+
+
 _i, _d, _vp, _dp, _ip = C.c_int, C.c_double, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int)
 _i32p, _i64p = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
 _params, _stop, _limits, _retime = (C.POINTER(s) for s in (GtopParams, GtopStop, GtopLimits, GtopRetime))
-_certify = C.POINTER(GtopCertifyOpts)
+_certify, _certify_moving = C.POINTER(GtopCertifyOpts), C.POINTER(GtopCertifyMovingOpts)
 
 # Every entry point of include/gtop.h: name -> (the ABI version that introduced it, 0 when the header does not say;
 # restype; argtypes).
@@ -195,8 +205,18 @@ ENTRY_POINTS_10 = {
     "gtop_certify_batch": (10, _i, [_vp, _i, _dp, _certify, _dp]),
     "gtop_select_best_certified_device": (10, _i, [_vp, _i, _vp, _vp, _vp, _limits, _i, _vp, _vp, _vp]),
 }
-# the ABI version of the library this package is built with (gtop_abi_version() of the in-tree build)
+# the record of the library up to version 10: the two tables above
 LIBRARY_ABI_VERSION = max(since for table in (ENTRY_POINTS, ENTRY_POINTS_10) for since, _, _ in table.values())
+
+# The entry points of ABI version 11 (the certificate against the moving boxes; certify.py wraps them), a third table of
+# the same layout: the two above and their constants stay the records up to their versions.
+ENTRY_POINTS_11 = {
+    "gtop_certify_moving_device": (11, _i, [_vp, _i, _i, _vp, _vp, _i, _certify_moving, _vp, _vp]),
+    "gtop_certify_moving_batch": (11, _i, [_vp, _i, _dp, _certify_moving, _dp]),
+}
+# the ABI version of the library this package is built with (gtop_abi_version() of the in-tree build)
+BUILD_ABI_VERSION = max(since for table in (ENTRY_POINTS, ENTRY_POINTS_10, ENTRY_POINTS_11)
+                        for since, _, _ in table.values())
 
 
 def entry_points(abi):
@@ -207,6 +227,11 @@ def entry_points(abi):
 def entry_points_10(abi):
     """Likewise, of the second table."""
     return [name for name, (since, _, _) in ENTRY_POINTS_10.items() if since <= abi]
+
+
+def entry_points_11(abi):
+    """Likewise, of the third table."""
+    return [name for name, (since, _, _) in ENTRY_POINTS_11.items() if since <= abi]
 
 
 def library_path():
@@ -257,5 +282,8 @@ def load_library():
     for name in entry_points_10(L.gtop_abi_version() if other else LIBRARY_ABI_VERSION):   # (the same rule)
         f = getattr(L, name)
         _, f.restype, f.argtypes = ENTRY_POINTS_10[name]
+    for name in entry_points_11(L.gtop_abi_version() if other else BUILD_ABI_VERSION):
+        f = getattr(L, name)
+        _, f.restype, f.argtypes = ENTRY_POINTS_11[name]
     _lib = L
     return L

@@ -1,9 +1,11 @@
 """The continuous-time clearance certificate (include/gtop.h: gtop_certify_trajectories_device, gtop_certify_batch,
-gtop_select_best_certified_device) over a GtopContext.
+gtop_select_best_certified_device; gtop_certify_moving_device, gtop_certify_moving_batch) over a GtopContext.
 
 The sampled report (GtopContext.validate_device) says that none of the getTraj samples is within the margin; the
-certificate bounds the interpolated distance of the STATIC field over whole time intervals, so "SAFE" speaks about
-every point of the curve.  Moving boxes are not covered: combine it with the report's box figures.
+certificate bounds the interpolated distance over whole time intervals, so "SAFE" speaks about every point of the
+curve.  certify_device / certify_batch speak about the STATIC field; certify_moving_device / certify_moving_batch about
+the field AND the context's moving boxes (either kind of list) at the start times' clock, every point of the curve
+against every time of its interval.  Both give the same (B, 8) rows, which select_best_certified_device takes.
 
 Functions of a context, not methods of it: the device forms are built on the context's own argument helpers
 (GtopContext._trajectory, _dev, _out), so the device-argument rules stated there hold here unchanged."""
@@ -11,7 +13,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._abi import GtopCertifyOpts
+from ._abi import GtopCertifyMovingOpts, GtopCertifyOpts
 from ._lib import _f64, _p, _stream, _th
 
 # the columns of a certificate row (GTOP_CERT_REPORT of include/gtop.h)
@@ -27,6 +29,16 @@ def certify_device(ctx, coeff, T, opts, cert=None, stream=None):
     traj = ctx._trajectory(coeff, T)
     cert, pcert = ctx._out("cert", cert, (traj[0], len(CERT_REPORT)), coeff)
     ctx._chk(ctx._L.gtop_certify_trajectories_device(ctx._h, *traj, C.byref(opts), pcert, _stream(stream, coeff)))
+    return cert
+
+
+def certify_moving_device(ctx, coeff, T, opts, cert=None, stream=None):
+    """certify_device against the static field and the context's moving boxes: opts is a GtopCertifyMovingOpts
+    (use_boxes False, or no boxes set: certify_device's result, bit for bit).  The boxes, the start times and the field
+    are read when the launch runs; asynchronous, capturable."""
+    traj = ctx._trajectory(coeff, T)
+    cert, pcert = ctx._out("cert", cert, (traj[0], len(CERT_REPORT)), coeff)
+    ctx._chk(ctx._L.gtop_certify_moving_device(ctx._h, *traj, C.byref(opts), pcert, _stream(stream, coeff)))
     return cert
 
 
@@ -54,5 +66,15 @@ def certify_batch(ctx, x, opts):
     return cert
 
 
+def certify_moving_batch(ctx, x, opts):
+    """certify_batch against the static field and the context's moving boxes; opts: a GtopCertifyMovingOpts."""
+    x = _f64(x)
+    B = x.shape[0]
+    cert = np.empty((B, len(CERT_REPORT)))
+    ctx._chk(ctx._L.gtop_certify_moving_batch(ctx._h, B, _p(x), C.byref(opts), _p(cert)))
+    return cert
+
+
 __all__ = ["CERT_REPORT", "UNSAFE", "UNDECIDED", "SAFE", "REQUIRE_SAFE", "REQUIRE_NOT_UNSAFE", "GtopCertifyOpts",
-           "certify_device", "select_best_certified_device", "certify_batch"]
+           "GtopCertifyMovingOpts", "certify_device", "certify_moving_device", "select_best_certified_device",
+           "certify_batch", "certify_moving_batch"]

@@ -147,6 +147,18 @@ bool GradTrajOptimizer::validateTrajectory(const Limits &limits, Report *report)
   return pass != 0;
 }
 
+// a row of GTOP_CERT_REPORT doubles as a CertifyReport
+static void fill_certify_report(const double *r, GradTrajOptimizer::CertifyReport &report) {
+  report.verdict = (int)r[0];
+  report.lo = r[1];
+  report.hi = r[2];
+  report.hi_time = r[3];
+  report.first_violation_time = r[4];
+  report.n_undecided = (int)r[5];
+  report.n_refinements = (int)r[6];
+  report.time_sum = r[7];
+}
+
 bool GradTrajOptimizer::certifyTrajectory(const CertifyOptions &options, CertifyReport &report) {
   if (!ctx_ || m_ < 2 || dp_.empty()) {
     last_status_ = GTOP_ERR_STATE;
@@ -159,14 +171,24 @@ bool GradTrajOptimizer::certifyTrajectory(const CertifyOptions &options, Certify
   double r[GTOP_CERT_REPORT];
   last_status_ = gtop_certify_batch(ctx_, 1, dp_.data(), &opt, r);
   if (last_status_ != GTOP_OK) return false;
-  report.verdict = (int)r[0];
-  report.lo = r[1];
-  report.hi = r[2];
-  report.hi_time = r[3];
-  report.first_violation_time = r[4];
-  report.n_undecided = (int)r[5];
-  report.n_refinements = (int)r[6];
-  report.time_sum = r[7];
+  fill_certify_report(r, report);
+  return report.verdict == 1;
+}
+
+bool GradTrajOptimizer::certifyTrajectoryMoving(const CertifyOptions &options, CertifyReport &report) {
+  if (!ctx_ || m_ < 2 || dp_.empty()) {
+    last_status_ = GTOP_ERR_STATE;
+    return false;
+  }
+  gtop_certify_moving_opts opt{};
+  opt.margin = options.margin;
+  opt.max_depth = options.max_depth;
+  opt.max_refine = options.max_refine;
+  opt.use_boxes = 1;
+  double r[GTOP_CERT_REPORT];
+  last_status_ = gtop_certify_moving_batch(ctx_, 1, dp_.data(), &opt, r);
+  if (last_status_ != GTOP_OK) return false;
+  fill_certify_report(r, report);
   return report.verdict == 1;
 }
 

@@ -143,7 +143,8 @@ class GradTrajOptimizer {
   // The continuous-time clearance certificate of the trajectory at the current Dp (include/gtop.h,
   // gtop_certify_batch): where validateTrajectory speaks about the getTraj samples, this speaks about every point of
   // the curve — true iff the verdict is SAFE: the interpolated distance of the static field is above `margin` over
-  // the whole of [0, time_sum].  Moving obstacles are not covered.  false also when the call fails (ok() tells).
+  // the whole of [0, time_sum].  The static field alone: certifyTrajectoryMoving below takes the moving obstacles in.
+  // false also when the call fails (ok() tells).
   struct CertifyOptions {
     double margin = 0.0;
     int max_depth = 2, max_refine = 256;
@@ -156,6 +157,10 @@ class GradTrajOptimizer {
     double time_sum = 0.0;
   };
   bool certifyTrajectory(const CertifyOptions &options, CertifyReport &report);
+  // The same against the static field AND the boxes of setMovingObstacles / setMovingObstaclePredictions at
+  // setStartTime's clock (include/gtop.h, gtop_certify_moving_batch): true iff SAFE — every point of the curve keeps
+  // `margin` from the field and from every box at the time the curve is there.  Without boxes: certifyTrajectory.
+  bool certifyTrajectoryMoving(const CertifyOptions &options, CertifyReport &report);
 
   // The same figures per SEGMENT (include/gtop.h, gtop_validate_segments): rows->at(s) covers the getTraj samples that
   // fall into segment s; of `limits` margin, use_boxes and dt_sample are read.  false when the call fails.

@@ -7,7 +7,8 @@
 
 #include "gtop_ctx.h"
 
-#define GTOP_ABI_VERSION 10  // 10: gtop_certify_trajectories_device, gtop_certify_batch, gtop_select_best_certified_device
+#define GTOP_ABI_VERSION 11  // 11: gtop_certify_moving_device, gtop_certify_moving_batch
+                             // 10: gtop_certify_trajectories_device, gtop_certify_batch, gtop_select_best_certified_device
                              // 9: gtop_validate_segments[_device], gtop_reallocate_times[_device]
                              // 8: gtop_min_jerk_start_device, gtop_min_jerk_start
                              // 7: gtop_set_moving_box_polynomials, gtop_get_moving_box_kind, gtop_box_polynomial_centres

@@ -1,6 +1,7 @@
 // gtop_capi_boxes.cpp — the moving boxes of a context (constant-velocity and polynomial lists), the start times on
 // their clock, and what reads them beside the cost term: the distance queries, the trajectory report and the selection
-// — and, beside the report, the continuous-time certificate of the static field (gtop_certify.hip).
+// — and, beside the report, the continuous-time certificates (gtop_certify.hip): of the static field, and of the field
+// with the boxes.
 #include <cmath>
 #include <string>
 #include <vector>
@@ -420,6 +421,60 @@ int gtop_certify_batch(gtop_ctx *c, int B, const double *x, const gtop_certify_o
   if ((rc = stage_coefficients(c, B, x))) return rc;
   if ((rc = gtop_certify_trajectories_device(c, B, c->m, c->mma_g.data(), c->d_T.data(), c->t_stride, opt,
                                              c->val_rep.data(), c->stream)))
+    return rc;
+  HIPCHK(c, hipMemcpyAsync(cert, c->val_rep.data(), ncert * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return GTOP_OK;
+} GTOP_CATCH_STATUS(c)
+
+// ---- the certificate against the moving boxes too (gtop_certify.hip, traj_certify_moving_kernel) ----
+// problem_B: as validate_ready's
+static int certify_moving_ready(gtop_ctx *c, int B, int m, int time_stride, const gtop_certify_moving_opts *o,
+                                int problem_B) {
+  if (!o) return fail(c, GTOP_ERR_INVALID, "certify_moving: options is NULL");
+  if (o->reserved != 0) return fail(c, GTOP_ERR_INVALID, "certify_moving: reserved must be 0");
+  const gtop_certify_opts base = {o->margin, o->max_depth, o->max_refine};
+  if (int rc = certify_ready(c, B, m, time_stride, &base)) return rc;
+  if (!gtop_start_times_fit(c, B, problem_B))
+    return fail(c, GTOP_ERR_INVALID, "certify_moving: the number of start times does not match the batch");
+  return GTOP_OK;
+}
+
+static int certify_moving_on_stream(gtop_ctx *c, int B, int m, const void *d_coeff, const void *d_T, int time_stride,
+                                    const gtop_certify_moving_opts *opt, void *d_cert, hipStream_t s, int problem_B) {
+  if (int rc = certify_moving_ready(c, B, m, time_stride, opt, problem_B)) return rc;
+  if (B == 0) return GTOP_OK;
+  if (!d_coeff || !d_T || !d_cert) return fail(c, GTOP_ERR_INVALID, "certify_moving: NULL buffer");
+  HIPCHK(c, hipSetDevice(c->device));
+  const bool boxes = opt->use_boxes != 0;
+  const double *t0 = (boxes && c->t0_count > 0) ? c->t0_dev : nullptr;
+  HIPCHK(c, gtop_launch_traj_certify_moving(c->field.grid, c->field.rec64.data(), box_list(c, boxes ? c->nbox : 0), B, m,
+                                            static_cast<const double *>(d_coeff), static_cast<const double *>(d_T),
+                                            time_stride, t0, c->t0_count > 1 ? 1 : 0, opt->margin, opt->max_depth,
+                                            opt->max_refine, static_cast<double *>(d_cert), s));
+  return GTOP_OK;
+}
+
+int gtop_certify_moving_device(gtop_ctx *c, int B, int m, const void *d_coeff, const void *d_T, int time_stride,
+                               const gtop_certify_moving_opts *opt, void *d_cert, void *hip_stream) try {
+  if (!c) return GTOP_ERR_INVALID;
+  return certify_moving_on_stream(c, B, m, d_coeff, d_T, time_stride, opt, d_cert, static_cast<hipStream_t>(hip_stream), 0);
+} GTOP_CATCH_STATUS(c)
+
+int gtop_certify_moving_batch(gtop_ctx *c, int B, const double *x, const gtop_certify_moving_opts *opt,
+                              double *cert) try {
+  if (!c) return GTOP_ERR_INVALID;
+  if (c->B == 0) return fail(c, GTOP_ERR_STATE, "gtop_set_problem / gtop_set_paths has not been called");
+  if (B < 1 || B > c->B || !x || !cert)
+    return fail(c, GTOP_ERR_INVALID, "certify_moving_batch: 1 <= B <= problem batch, x and cert required");
+  int rc = certify_moving_ready(c, B, c->m, c->t_stride, opt, c->B);   // (before anything is staged)
+  if (rc) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t ncert = (size_t)B * GTOP_CERT_REPORT;
+  HIPCHK(c, c->val_rep.reserve(ncert));
+  if ((rc = stage_coefficients(c, B, x))) return rc;
+  if ((rc = certify_moving_on_stream(c, B, c->m, c->mma_g.data(), c->d_T.data(), c->t_stride, opt, c->val_rep.data(),
+                                     c->stream, c->B)))
     return rc;
   HIPCHK(c, hipMemcpyAsync(cert, c->val_rep.data(), ncert * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));

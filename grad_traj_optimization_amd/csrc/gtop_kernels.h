@@ -219,7 +219,7 @@ hipError_t gtop_launch_select_best(int B, const double *report, const double *co
                                    int per_axis, int allow_out_of_map, const double *cert, int require,
                                    unsigned char *pass, int *best, void *workspace, hipStream_t stream);
 
-// ---- continuous-time clearance certificate (gtop_certify.hip), fp64, static field -----------------
+// ---- continuous-time clearance certificate (gtop_certify.hip), fp64: the static field, and the field with the boxes ----
 #define GTOP_CERT_REPORT 8      // = include/gtop.h
 #define GTOP_CERT_MAX_DEPTH 3   // = include/gtop.h: levels 0 .. 3
 #define GTOP_CERT_REQUIRE_SAFE 1         // = include/gtop.h
@@ -234,6 +234,13 @@ hipError_t gtop_launch_select_best(int B, const double *report, const double *co
 hipError_t gtop_launch_traj_certify(const GtopGrid &g, const double *rec, int B, int m, const double *coeff,
                                     const double *T, int t_stride, double margin, int max_depth, int max_refine,
                                     double *cert, hipStream_t stream);
+// The same against the static field and the boxes over whole ranges of box time (include/gtop.h,
+// gtop_certify_moving_device): box time = t0[b * t0_stride] + trajectory time (t0 NULL = 0); both list kinds, any number
+// of boxes; no boxes: the launch above
+hipError_t gtop_launch_traj_certify_moving(const GtopGrid &g, const double *rec, const GtopBoxList &boxes, int B, int m,
+                                           const double *coeff, const double *T, int t_stride, const double *t0,
+                                           int t0_stride, double margin, int max_depth, int max_refine, double *cert,
+                                           hipStream_t stream);
 
 // ---- per-segment report (gtop_segments.hip) and segment-time reallocation (gtop_retime.hip), fp64 ------------
 #define GTOP_SEG_REPORT 10   // = include/gtop.h

@@ -89,7 +89,8 @@ const char *gtop_last_error(const gtop_ctx *ctx);
  * per-segment report and segment-time reallocation,
  * gtop_validate_segments[_device] / gtop_reallocate_times[_device]; 10: the
  * continuous-time clearance certificate, gtop_certify_trajectories_device /
- * gtop_certify_batch / gtop_select_best_certified_device;
+ * gtop_certify_batch / gtop_select_best_certified_device; 11: the certificate
+ * against the moving boxes, gtop_certify_moving_device / gtop_certify_moving_batch;
  * nothing of an earlier version changed meaning). */
 int gtop_abi_version(void);
 
@@ -923,8 +924,10 @@ int gtop_reallocate_times(gtop_ctx *ctx, const gtop_retime *opt, int B, double *
  * gives a lower bound of the distance over the interval from 8 trilinear values per
  * cell, for ANY field the library holds (an exact ESDF, a windowed one with its
  * 10000 sentinels, a signed one, arbitrary values of gtop_set_sdf): no Lipschitz
- * assumption is made.  The STATIC field only: moving boxes are NOT covered — combine
- * the certificate with the box figures of the sampled report.
+ * assumption is made.  These three entry points certify the STATIC field; the moving
+ * boxes are certified, over whole time intervals too, by gtop_certify_moving_device
+ * below (a sampled box figure has the same hole between two samples, and a wider
+ * one: a thin box needs only to cross the curve there).
  *
  * Per segment (time T) and axis k: A_k = 2|c2| + 6|c3|T + 12|c4|T^2 + 20|c5|T^3
  * bounds the acceleration.  An interval is [a, a + w] in the segment's local time.
@@ -998,6 +1001,76 @@ int gtop_select_best_certified_device(gtop_ctx *ctx, int B, const void *d_report
                                       const void *d_cert, const void *d_cost,
                                       const gtop_limits *limits, int require, void *d_pass,
                                       void *d_best, void *hip_stream);
+
+/* ---- the certificate against the moving boxes (ABI version 11) ----------- */
+/* For a row b the certified quantity is the `dist` gtop_edt_query_device returns for
+ * (x(t), tau = start + t): the trilinear form over corner values min(static, distance
+ * from the corner voxel's centre to the nearest box at tau), for either kind of box
+ * list (gtop_set_moving_boxes, gtop_set_moving_box_polynomials) and any number of
+ * boxes.  `start` is the row's start time under the rules of
+ * gtop_set_start_times[_device] (none: 0; one: shared; else one per row).  Two
+ * monotonicities of the lookup carry the bound: the trilinear weights lie in [0, 1]
+ * on the clamped local coordinates, so the form is non-decreasing in every corner
+ * value; and a corner's distance to a box does not grow when the box's faces move
+ * outwards (the subtraction, the squares, their sum and the sqrt round
+ * monotonically).  With each box replaced by an axis-aligned box that contains it at
+ * every tau of an interval, the vertex minimum per touched cell of the static
+ * certificate is a lower bound for every point and time of the interval — for any
+ * field, as before.
+ *
+ * The interval tree, the curve box, its cells and sub-boxes, the VIOLATION /
+ * CERTIFIED / OPEN rule, the budget, the order and the 8 columns of cert are those of
+ * gtop_certify_trajectories_device above.  New, per interval [a, a + w] of a segment
+ * with time Ts that starts at trajectory time t_off, all in plain fp64 operations:
+ *   d_mid = the `dist` the query returns for (p, start + t), t = t_off + tc as entry
+ *     3 has it, bit for bit; out of the map -1 and the boxes ignored, as the query.
+ *   ta = start + (t_off + a), tb = start + (t_off + (a + w)),
+ *   delta = 2^-40 (|start| + (t_off + Ts)), tau_a = ta - delta, tau_b = tb + delta.
+ *   The boxes are applied iff tau_b >= 0 (a wholly negative interval is static only,
+ *   as the query; one that straddles 0 takes the boxes over all of [tau_a, tau_b]).
+ *   Constant-velocity box: the query's faces at tau_a and at tau_b; per axis the
+ *     smaller lower and the larger upper face (the centre is a monotone function of
+ *     tau in floating point: no slack).
+ *   Polynomial box: tca, tcb = tau_a, tau_b clamped into the box's [t1, t2];
+ *     hh = 0.5 (tcb - tca), tm = tca + hh, M = max(|tca|, |tcb|); per axis
+ *     cm = the centre at tm (the fma Horner of gtop_box_polynomial_centres),
+ *     vq = ((((5 c5) tm + 4 c4) tm + 3 c3) tm + 2 c2) tm + c1,
+ *     Aq = 2|c2| + 6|c3| M + 12|c4| M^2 + 20|c5| M^3,
+ *     Qk = ((((|c5| M + |c4|) M + |c3|) M + |c2|) M + |c1|) M + |c0|,
+ *     rq = |vq| hh + 0.5 Aq hh hh, then rq (1 + 2^-40) + 2^-40 Qk;
+ *     faces (cm - rq) - half extent and (cm + rq) + half extent.  A cm or rq that is
+ *     not finite: the box covers everything (distance 0 at every corner).
+ *   lb: for each of the at most 8 cells the curve box touches, the static corner
+ *     values; V = the largest |static corner value| of the touched cells (taken
+ *     before any min: the query's form at any tau holds values between the lowered
+ *     and the static ones); then every corner lowered to its distance to every swept
+ *     box (with the query's exact skip, per cell); the 8 vertex values as in the
+ *     static certificate; lb = their least - 2^-46 (8 + C / res) V.
+ * DESIGN.md 5.15 bounds the roundings delta and 2^-40 Qk cover.
+ *
+ * cert is the same B x GTOP_CERT_REPORT row, so gtop_select_best_certified_device
+ * takes it unchanged.  With use_boxes == 0 or an empty box list the call launches the
+ * static kernel: the result is gtop_certify_trajectories_device's, bit for bit.
+ * use_boxes is independent of gtop_set_moving_cost.  gtop_certify_moving_device only
+ * enqueues one launch: no allocation, no synchronisation, capturable; the boxes, the
+ * start times and the field are read at replay (a captured launch keeps the list's
+ * kind and length).  gtop_certify_moving_batch stages as gtop_certify_batch does.
+ * Errors: those of gtop_certify_trajectories_device / gtop_certify_batch, and
+ * GTOP_ERR_INVALID for reserved != 0 and for a start-time count that is neither 0, 1
+ * nor B (for the batch form the problem's batch serves too, as for
+ * gtop_validate_batch).  fp64 only.  The gtop_group_* entry points do not forward
+ * it. */
+typedef struct {
+  double margin;
+  int32_t max_depth, max_refine; /* as gtop_certify_opts */
+  int32_t use_boxes;             /* 0: the static certificate, bit for bit */
+  int32_t reserved;              /* must be 0 */
+} gtop_certify_moving_opts;
+int gtop_certify_moving_device(gtop_ctx *ctx, int B, int m, const void *d_coeff, const void *d_T,
+                               int time_stride, const gtop_certify_moving_opts *opt, void *d_cert,
+                               void *hip_stream);
+int gtop_certify_moving_batch(gtop_ctx *ctx, int B, const double *x,
+                              const gtop_certify_moving_opts *opt, double *cert);
 
 /* ---- bookkeeping the reference keeps inside the callback ------------ */
 

@@ -14,8 +14,13 @@ taken, and the parent's own spread of (a) over the rounds is the yardstick for (
 The tool also runs the headline benchmark on both builds, alternating, and writes that line under the table.  It writes
 certify_time.{md,json}.
 
+With --boxes the subject is the certificate against the moving boxes (gtop_certify_moving_device) instead: 0, 8 and 32
+boxes of each kind of list fly through the map; the parent build gives the sampled report with the same boxes
+(use_boxes, dt_sample = 0.01) and the static certificate, this build the static certificate and the moving one; the
+static certificate of the two builds is compared inside the parent's own spread.  It writes certify_moving_time.{md,json}.
+
 usage: tools/certify_time.py [--parent-lib build_var/libgtop_parent.so] [--rounds 3] [--bench-rounds 2]
-                             [--out profiles/certify]"""
+                             [--out profiles/certify] [--boxes]"""
 import argparse
 import json
 import os
@@ -25,9 +30,29 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BATCHES = (1024, 16384)
 DT, MARGIN, EVALS = 0.01, 0.3, 20
+BOX_COUNTS = (0, 8, 32)
 
 
-def child(certify):
+def make_boxes(mp, n, poly, seed=7):
+    """n boxes of 0.5 .. 1.5 m that fly through the map at up to 1 m/s; polynomial: with a second and third order term,
+    every other one on a validity interval that ends at 3 s.  -> the arguments of the context's setter"""
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    lo, size = np.asarray(mp.origin, dtype=np.float64), np.asarray(mp.map_size, dtype=np.float64)
+    p0 = lo + rng.uniform(0.1, 0.9, (n, 3)) * size
+    vel = rng.uniform(-1.0, 1.0, (n, 3))
+    scale = rng.uniform(0.5, 1.5, (n, 3))
+    if not poly:
+        return p0, vel, scale
+    coef = np.zeros((n, 3, 6))
+    coef[:, :, 0], coef[:, :, 1] = p0, vel
+    coef[:, :, 2], coef[:, :, 3] = rng.uniform(-0.1, 0.1, (n, 3)), rng.uniform(-0.01, 0.01, (n, 3))
+    t_range = np.tile([-np.inf, np.inf], (n, 1))
+    t_range[::2] = (0.0, 3.0)
+    return coef, scale, t_range
+
+
+def child(certify, boxes=False):
     import time
 
     import numpy as np
@@ -78,6 +103,31 @@ def child(certify):
         report = torch.empty(B, 12, dtype=torch.float64, device=dev)
         lim = gtop.GtopLimits(margin=MARGIN)
         reps = 20 if B == 1024 else 5
+        if boxes:
+            cert = torch.empty(B, 8, dtype=torch.float64, device=dev)
+            static = gtop.GtopCertifyOpts(margin=MARGIN)
+            out[f"certificate, static B={B}"] = span(lambda: gtop.certify_device(ctx, coeff, T, static, cert=cert), reps)
+            with_boxes = gtop.GtopLimits(margin=MARGIN, use_boxes=True)
+            for poly in (False, True):
+                for n in BOX_COUNTS:
+                    kind = f"{n} {'polynomial' if poly else 'constant-velocity'} boxes B={B}"
+                    if poly:
+                        ctx.set_moving_box_polynomials(*make_boxes(mp, n, True))
+                    else:
+                        ctx.set_moving_boxes(*make_boxes(mp, n, False))
+                    if not certify:     # the parent build: the sampled report with the boxes
+                        out[f"report, {kind}"] = span(
+                            lambda: ctx.validate_device(coeff, T, with_boxes, dt_sample=DT, report=report), reps)
+                        continue
+                    mo = gtop.GtopCertifyMovingOpts(margin=MARGIN)
+                    out[f"certificate, {kind}"] = span(lambda: gtop.certify_moving_device(ctx, coeff, T, mo, cert=cert), reps)
+                    torch.cuda.synchronize()
+                    c = cert.cpu().numpy()
+                    out[f"mean refinements per row, {kind}"] = float(c[:, 6].mean())
+                    out[f"share safe, {kind}"] = float((c[:, 0] == 1).mean())
+                    assert np.all(c[:, 1] <= c[:, 2])
+            ctx.set_moving_boxes(*make_boxes(mp, 0, False))
+            continue
         out[f"report B={B}"] = span(lambda: ctx.validate_device(coeff, T, lim, dt_sample=DT, report=report), reps)
         if certify:
             cert = torch.empty(B, 8, dtype=torch.float64, device=dev)
@@ -119,16 +169,17 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "certify"))
     ap.add_argument("--bench-rounds", type=int, default=2, help="alternating bench.py runs per build (0 = none)")
     ap.add_argument("--child", choices=("certify", "report"))
+    ap.add_argument("--boxes", action="store_true", help="the certificate against the moving boxes (see above)")
     a = ap.parse_args()
     if a.child:
-        return child(a.child == "certify")
+        return child(a.child == "certify", a.boxes)
     if not os.path.exists(a.parent_lib):
         sys.exit(f"no parent build at {a.parent_lib}: make -C grad_traj_optimization_amd/csrc lib OUT=... on the parent commit")
     runs = {"parent": [], "this": []}
     for _ in range(a.rounds):                                   # alternating, one fresh process each
         for who in ("parent", "this"):
-            line = run_child(who, a.parent_lib, [os.path.abspath(__file__), "--child", "report" if who == "parent" else "certify"],
-                             "CERTIFY_TIME_JSON ", 400)
+            line = run_child(who, a.parent_lib, [os.path.abspath(__file__), "--child", "report" if who == "parent" else "certify",
+                                                 *(["--boxes"] if a.boxes else [])], "CERTIFY_TIME_JSON ", 400)
             runs[who].append(json.loads(line.split(" ", 1)[1]))
             print(f"{who}: done", flush=True)
     timed = lambda k: k.startswith(("report", "certificate"))
@@ -149,6 +200,8 @@ def main():
                       f"M evals/s: parent {fm(pv)}; this build {fm(tv)}; means {sum(tv) / len(tv) / (sum(pv) / len(pv)):.4f} of the "
                       f"parent's; the parent's own runs differ by {(max(pv) / min(pv) - 1) * 100:.2f} %, this build's by "
                       f"{(max(tv) / min(tv) - 1) * 100:.2f} %")
+    if a.boxes:
+        return write_moving(a, runs, best, spread, facts, bench, bench_line)
     lines = ["| B | (a) report, parent build, us | (b) report, this build, us | (b) / (a) | parent's spread of (a) | inside it "
              "| (c) certificate, us | (c) / (a) | level 0 only, us | mean refinements per row |",
              "|---|---|---|---|---|---|---|---|---|---|"]
@@ -177,6 +230,42 @@ def main():
             f.write("\nbench.py A/B in the same call: %s\n" % bench_line)
     print(table)
     print(json.dumps(facts))
+    if bench_line:
+        print(bench_line)
+
+
+def write_moving(a, runs, best, spread, facts, bench, bench_line):
+    """certify_moving_time.{md,json}: per batch and list, the parent's sampled report beside this build's certificate."""
+    lines = ["| B | list | report with boxes, parent build, us | moving certificate, this build, us | ratio "
+             "| mean refinements per row | share SAFE |", "|---|---|---|---|---|---|---|"]
+    static, failed = [], []
+    for B in BATCHES:
+        k = f"certificate, static B={B}"
+        pa, tb, sp = best["parent"][k], best["this"][k], spread[k]
+        ok = tb / pa - 1 <= sp
+        if not ok:
+            failed.append(f"B={B}")
+        static.append(f"- static certificate B={B}: parent {pa:.1f} us, this build {tb:.1f} us, ratio {tb / pa:.3f}; the "
+                      f"parent's own spread {sp * 100:.1f} %: {'inside' if ok else 'OUTSIDE'}")
+        for poly in ("constant-velocity", "polynomial"):
+            for n in BOX_COUNTS:
+                kind = f"{n} {poly} boxes B={B}"
+                r, c = best["parent"][f"report, {kind}"], best["this"][f"certificate, {kind}"]
+                lines.append(f"| {B} | {n} {poly} | {r:.1f} | {c:.1f} | {c / r:.2f} | "
+                             f"{facts[f'mean refinements per row, {kind}']:.2f} | {facts[f'share safe, {kind}']:.3f} |")
+    table = "\n".join(lines)
+    os.makedirs(a.out, exist_ok=True)
+    with open(os.path.join(a.out, "certify_moving_time.json"), "w") as f:
+        json.dump(dict(runs=runs, best_us=best, parent_spread=spread, facts=facts, static_outside_parent_spread=failed,
+                       rounds=a.rounds, bench_evals_per_s=bench, bench_line=bench_line), f, indent=1)
+    with open(os.path.join(a.out, "certify_moving_time.md"), "w") as f:
+        f.write("fp64, m = 6, 200^3 map, rows optimised for %d evaluations, margin %.1f, start time 0, report at dt_sample = "
+                "%.2f, certificates at max_depth 2 / max_refine 256; device-clock spans, minimum over %d alternating rounds "
+                "of one fresh process per library\n\n%s\n\n%s\n" % (EVALS, MARGIN, DT, a.rounds, table, "\n".join(static)))
+        if bench_line:
+            f.write("\nbench.py A/B in the same call: %s\n" % bench_line)
+    print(table)
+    print("\n".join(static))
     if bench_line:
         print(bench_line)
 
