@@ -15,8 +15,10 @@ from ._lib import (GTOP_F32, GTOP_F64, GtopError, GtopLimits, GtopParams, GtopRe
 from .certify import (CERT_REPORT, GtopCertifyMovingOpts, GtopCertifyOpts, certify_batch, certify_device,  # noqa: F401
                       certify_moving_batch, certify_moving_device, select_best_certified_device)
 from . import certify  # noqa: F401
+from .insert import INSERT_INFO, GtopInsert, insert_waypoints, insert_waypoints_device  # noqa: F401
+from . import insert  # noqa: F401
 
-__all__ = ["GTOP_F32", "GTOP_F64", "GtopError", "GtopLimits", "GtopParams", "GtopRetime", "OPTI_NODE_PARAMS",
+__all__ = ["INSERT_INFO", "GtopInsert", "insert", "insert_waypoints", "insert_waypoints_device","GTOP_F32", "GTOP_F64", "GtopError", "GtopLimits", "GtopParams", "GtopRetime", "OPTI_NODE_PARAMS",
            "GtopContext", "GtopGroup", "Rendezvous", "box_polynomial_centres", "library_path", "load_library",
            "CERT_REPORT", "GtopCertifyMovingOpts", "GtopCertifyOpts", "certify", "certify_batch", "certify_device",
            "certify_moving_batch", "certify_moving_device", "select_best_certified_device"]

@@ -86,10 +86,26 @@ class GtopCertifyMovingOpts(C.Structure):
         super().__init__(float(margin), int(max_depth), int(max_refine), int(bool(use_boxes)), int(reserved))
 
 
+class GtopInsert(C.Structure):
+    """gtop_insert of include/gtop.h: how insert_waypoints[_device] (insert.py) cuts one segment of every row in two.
+    mode 0 (AT_TIME): at the trajectory time `when` gives; mode 1 (LONGEST): the longest segment in the middle.
+    min_fraction in (0, 0.5] keeps that share of the segment on either side of the cut; push > 0 moves the new waypoint
+    that far up the static field's gradient where the distance is below push_below; bos, vos, aos bound the new
+    waypoint when lb / ub are given; reserved must be 0."""
+    AT_TIME, LONGEST = 0, 1
+    _fields_ = [("mode", C.c_int32), ("min_fraction", C.c_double), ("push", C.c_double), ("push_below", C.c_double),
+                ("bos", C.c_double), ("vos", C.c_double), ("aos", C.c_double), ("reserved", C.c_int32)]
+
+    def __init__(self, mode=1, min_fraction=0.1, push=0.0, push_below=0.0, bos=3.0, vos=8.0, aos=10.0, reserved=0):
+        super().__init__(int(mode), float(min_fraction), float(push), float(push_below), float(bos), float(vos),
+                         float(aos), int(reserved))
+
+
 _i, _d, _vp, _dp, _ip = C.c_int, C.c_double, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int)
 _i32p, _i64p = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
 _params, _stop, _limits, _retime = (C.POINTER(s) for s in (GtopParams, GtopStop, GtopLimits, GtopRetime))
 _certify, _certify_moving = C.POINTER(GtopCertifyOpts), C.POINTER(GtopCertifyMovingOpts)
+_insert = C.POINTER(GtopInsert)
 
 # Every entry point of include/gtop.h: name -> (the ABI version that introduced it, 0 when the header does not say;
 # restype; argtypes).
@@ -218,6 +234,17 @@ ENTRY_POINTS_11 = {
 BUILD_ABI_VERSION = max(since for table in (ENTRY_POINTS, ENTRY_POINTS_10, ENTRY_POINTS_11)
                         for since, _, _ in table.values())
 
+# The entry points of ABI version 12 (waypoint insertion; insert.py wraps them), a fourth table of the same layout: the
+# three above and their constants stay the records up to their versions (BUILD_ABI_VERSION: up to 11).
+ENTRY_POINTS_12 = {
+    "gtop_insert_waypoints_device": (12, _i, [_vp, _insert, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp,
+                                              _vp, _vp, _vp]),
+    "gtop_insert_waypoints": (12, _i, [_vp, _insert, _i, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
+}
+# the ABI version gtop_abi_version() of the in-tree build returns: the four tables
+CURRENT_ABI_VERSION = max(since for table in (ENTRY_POINTS, ENTRY_POINTS_10, ENTRY_POINTS_11, ENTRY_POINTS_12)
+                          for since, _, _ in table.values())
+
 
 def entry_points(abi):
     """The names a library of ABI version `abi` has."""
@@ -232,6 +259,11 @@ def entry_points_10(abi):
 def entry_points_11(abi):
     """Likewise, of the third table."""
     return [name for name, (since, _, _) in ENTRY_POINTS_11.items() if since <= abi]
+
+
+def entry_points_12(abi):
+    """Likewise, of the fourth table."""
+    return [name for name, (since, _, _) in ENTRY_POINTS_12.items() if since <= abi]
 
 
 def library_path():
@@ -285,5 +317,8 @@ def load_library():
     for name in entry_points_11(L.gtop_abi_version() if other else BUILD_ABI_VERSION):
         f = getattr(L, name)
         _, f.restype, f.argtypes = ENTRY_POINTS_11[name]
+    for name in entry_points_12(L.gtop_abi_version() if other else CURRENT_ABI_VERSION):
+        f = getattr(L, name)
+        _, f.restype, f.argtypes = ENTRY_POINTS_12[name]
     _lib = L
     return L

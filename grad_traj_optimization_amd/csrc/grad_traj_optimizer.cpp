@@ -252,6 +252,44 @@ bool GradTrajOptimizer::reallocateSegmentTime(const RetimeOptions &options) {
   return true;
 }
 
+bool GradTrajOptimizer::insertWaypoint(const InsertOptions &options, InsertInfo *info) {
+  if (!ctx_ || m_ < 2 || dp_.empty()) {
+    last_status_ = GTOP_ERR_STATE;
+    return false;
+  }
+  gtop_insert opt{};
+  opt.mode = options.mode;
+  opt.min_fraction = options.min_fraction;
+  opt.push = options.push;
+  opt.push_below = options.push_below;
+  const int m = m_ + 1, num_dp = 3 * m - 3;
+  std::vector<double> x((size_t)3 * num_dp), T(m);
+  double row[GTOP_INSERT_INFO];
+  last_status_ = gtop_insert_waypoints(ctx_, &opt, 1, dp_.data(), &options.when, nullptr, nullptr, x.data(), T.data(),
+                                       nullptr, nullptr, row);
+  if (last_status_ != GTOP_OK) return false;
+  last_status_ = gtop_set_problem(ctx_, 1, m, T.data(), m, df_.data());   // (refuses a time that is not > 0)
+  if (last_status_ != GTOP_OK) return false;
+  const int s = (int)row[0];
+  double p[3];
+  for (int a = 0; a < 3; ++a) p[a] = x[(size_t)a * num_dp + 3 * s];   // junction s + 1 of the new row
+  path_.insert(path_.begin() + 3 * (s + 1), p, p + 3);
+  m_ = m;
+  num_dp_ = num_dp;
+  segment_time_ = T;
+  dp_ = x;
+  coefficientsFromDerivatives(dp_);
+  if (info) {
+    info->segment = s;
+    info->local_time = row[1];
+    info->fell_back = row[2] != 0.0;
+    info->clamped = row[3] != 0.0;
+    info->distance = row[4];
+    info->pushed = row[5] != 0.0;
+  }
+  return true;
+}
+
 // Common tail of setPath / setKinoPath: Df, Dp (getInitialD,
 // src/qp_generator.cpp:407-451), initial coefficients (Px = A^-1 Dx,
 // :334-336 / :134-136), then the problem goes to the device.

@@ -186,6 +186,27 @@ class GradTrajOptimizer {
     Limits report;
   };
   bool reallocateSegmentTime(const RetimeOptions &options);
+  // One more waypoint on the trajectory at the current Dp (include/gtop.h, gtop_insert_waypoints): the segment that
+  // holds trajectory time `when` (GTOP_INSERT_AT_TIME — a Report's clearance_time, a CertifyReport's hi_time or
+  // first_violation_time; a time that is not in [0, inf) falls back to LONGEST) or the longest segment
+  // (GTOP_INSERT_LONGEST) is cut in two, the new junction takes the curve's position, velocity and acceleration there
+  // and, with push > 0 where the static distance is below push_below, is moved `push` up the field's gradient.  The
+  // object's path, Dp, segment_time and segment count become the new problem of one segment more — what
+  // optimizeTrajectory runs on next, its bounds around the new waypoint as around the others — and the coefficients
+  // are refreshed: without a push the curve is the old one.  false, and nothing changed, when the call fails.
+  struct InsertOptions {
+    int mode = GTOP_INSERT_LONGEST;
+    double when = -1.0;
+    double min_fraction = 0.1;          // the cut keeps this share of the segment on either side
+    double push = 0.0, push_below = 0.0;
+  };
+  struct InsertInfo {
+    int segment = -1;                   // the segment that was cut
+    double local_time = 0.0;            // where, in its own time
+    bool fell_back = false, clamped = false, pushed = false;
+    double distance = 0.0;              // the static distance at the new waypoint before the push (0 when push is off)
+  };
+  bool insertWaypoint(const InsertOptions &options, InsertInfo *info = nullptr);
 
   // extras (not in the reference)
   bool ok() const { return ctx_ != nullptr && last_status_ == GTOP_OK; }

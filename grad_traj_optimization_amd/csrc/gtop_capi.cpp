@@ -7,7 +7,8 @@
 
 #include "gtop_ctx.h"
 
-#define GTOP_ABI_VERSION 11  // 11: gtop_certify_moving_device, gtop_certify_moving_batch
+#define GTOP_ABI_VERSION 12  // 12: gtop_insert_waypoints_device, gtop_insert_waypoints
+                             // 11: gtop_certify_moving_device, gtop_certify_moving_batch
                              // 10: gtop_certify_trajectories_device, gtop_certify_batch, gtop_select_best_certified_device
                              // 9: gtop_validate_segments[_device], gtop_reallocate_times[_device]
                              // 8: gtop_min_jerk_start_device, gtop_min_jerk_start

@@ -6,7 +6,7 @@
 //   gtop_capi_problem.cpp  the problem set, path set-up, trajectory post-processing, default bounds
 //   gtop_capi_eval.cpp     the evaluation entry points and the batched optimizer
 //   gtop_capi_boxes.cpp    moving boxes, start times, queries, trajectory report and selection, per-segment report,
-//                          segment-time reallocation
+//                          segment-time reallocation, waypoint insertion
 // Host-side only: they own device buffers, fill kernel arguments, launch.  There is deliberately no CPU code path:
 // without a gfx950 device every entry point fails (GTOP_ERR_NO_DEVICE).
 #ifndef GTOP_CTX_H_
@@ -119,7 +119,8 @@ struct gtop_ctx {
   GtopDevBuf<unsigned char> sel_part;  // gtop_select_best_device: the partial results of its first stage (allocated at
                                        // gtop_create: the entry point itself must not allocate)
   GtopDevBuf<double> val_rep;  // gtop_validate_batch staging: report | cost, then pass and best behind them
-  GtopDevBuf<double> seg_rep;  // gtop_validate_segments / gtop_reallocate_times staging: segment report | T_out
+  GtopDevBuf<double> seg_rep;  // gtop_validate_segments / gtop_reallocate_times staging: segment report | T_out;
+                               // gtop_insert_waypoints': when | lb | ub | x_out | T_out | lb_out | ub_out | info
   GtopDevBuf<double> d_q;      // host-API staging of gtop_edt_query: pos | time | dist | grad; gtop_trajectory_samples'
                                // sample scratch too
   GtopPinnedBuf<double> pin;   // device-visible host staging for small host-buffer evaluations: x | cost | grad

@@ -110,23 +110,13 @@ edt_query_kernel(const GtopGrid g, const double *__restrict__ field, const doubl
   }
   // trilinear value and gradient, edt_environment.cpp:104-121 (= sdf_map.cpp:221-239)
   const GtopTrilinear tl = gtop_edt_trilinear(diff, values);
-  const double v00 = tl.v00, v01 = tl.v01, v10 = tl.v10, v11 = tl.v11, v0 = tl.v0, v1 = tl.v1, d = tl.d;
-  double gx, gy, gz;
-  {
-#pragma clang fp contract(off)   // the reference's unfused arithmetic: gtop_edt_lookup.h
-    gx = (1 - diff[2]) * (1 - diff[1]) * (values[1][0][0] - values[0][0][0]);
-    gx += (1 - diff[2]) * diff[1] * (values[1][1][0] - values[0][1][0]);
-    gx += diff[2] * (1 - diff[1]) * (values[1][0][1] - values[0][0][1]);
-    gx += diff[2] * diff[1] * (values[1][1][1] - values[0][1][1]);
-    gx *= g.res_inv;
-    gy = ((1 - diff[2]) * (v10 - v00) + diff[2] * (v11 - v01)) * g.res_inv;
-    gz = (v1 - v0) * g.res_inv;
-  }
-  if (live) dist[i] = out ? -1.0 : d;
+  double gr[3];
+  gtop_edt_gradient(g, diff, values, tl, gr);   // the reference's unfused arithmetic: gtop_edt_lookup.h
+  if (live) dist[i] = out ? -1.0 : tl.d;
   __syncthreads();   // every lane has read its position: the tile now carries the gradients out
-  xyz[3 * tid] = out ? 0.0 : gx;
-  xyz[3 * tid + 1] = out ? 0.0 : gy;
-  xyz[3 * tid + 2] = out ? 0.0 : gz;
+  xyz[3 * tid] = out ? 0.0 : gr[0];
+  xyz[3 * tid + 1] = out ? 0.0 : gr[1];
+  xyz[3 * tid + 2] = out ? 0.0 : gr[2];
   __syncthreads();
   for (int k = 0; k < 3; ++k) {
     const size_t e = 3 * row0 + tid + 256 * k;

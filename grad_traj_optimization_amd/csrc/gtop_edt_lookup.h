@@ -6,7 +6,8 @@
 // of a box list in LDS, the min over one box with the exact skip, and the
 // trilinear value.  The library is built with -ffp-contract=on, so the same source
 // expression rounds the same way wherever it is inlined: all of them get the same
-// distance, bit for bit.  The gradient stays with the query kernel.
+// distance, bit for bit.  The gradient (gtop_edt_gradient) is the query kernel's and the waypoint insertion's
+// (gtop_insert.hip).
 // The centre of a POLYNOMIAL box (gtop_set_moving_box_polynomials) is stated here once for those two kernels and for
 // the cost bodies (mov_min_boxes, gtop_wave_kernel.h).
 // The STATIC lookup (base index, diff, trilinear value; the gradient in gtop_edt.hip) is unfused, as poly_eval is:
@@ -184,6 +185,22 @@ __device__ __forceinline__ GtopTrilinear gtop_edt_trilinear(const double diff[3]
   r.v1 = (1 - diff[1]) * r.v01 + diff[1] * r.v11;
   r.d = (1 - diff[2]) * r.v0 + diff[2] * r.v1;
   return r;
+}
+
+// the gradient of that value, edt_environment.cpp:114-121 (= sdf_map.cpp:231-239), in the reference's unfused
+// arithmetic: what gtop_edt_query_device returns beside the distance, and what gtop_insert_waypoints_device pushes a
+// new waypoint along (gtop_insert.hip) — the same bits in both
+__device__ __forceinline__ void gtop_edt_gradient(const GtopGrid &g, const double diff[3], const double values[2][2][2],
+                                                  const GtopTrilinear &tl, double grad[3]) {
+#pragma clang fp contract(off)
+  double gx = (1 - diff[2]) * (1 - diff[1]) * (values[1][0][0] - values[0][0][0]);
+  gx += (1 - diff[2]) * diff[1] * (values[1][1][0] - values[0][1][0]);
+  gx += diff[2] * (1 - diff[1]) * (values[1][0][1] - values[0][0][1]);
+  gx += diff[2] * diff[1] * (values[1][1][1] - values[0][1][1]);
+  gx *= g.res_inv;
+  grad[0] = gx;
+  grad[1] = ((1 - diff[2]) * (tl.v10 - tl.v00) + diff[2] * (tl.v11 - tl.v01)) * g.res_inv;
+  grad[2] = (tl.v1 - tl.v0) * g.res_inv;
 }
 
 #endif  // GTOP_EDT_LOOKUP_H_

@@ -259,4 +259,18 @@ hipError_t gtop_launch_retime_limits(int B, int m, double *x, const double *T, i
                                      double max_vel, double max_acc, double max_ratio, int per_axis, int uniform,
                                      int scale_x, double *T_out, hipStream_t stream);
 
+// ---- waypoint insertion (gtop_insert.hip), fp64 ------------------------------------------------------------------
+#define GTOP_INSERT_AT_TIME 0   // = include/gtop.h
+#define GTOP_INSERT_LONGEST 1   // = include/gtop.h
+#define GTOP_INSERT_INFO 6      // = include/gtop.h
+// One segment of every row cut in two as include/gtop.h states it: x_out, lb_out, ub_out [B][9m], T_out [B][m + 1],
+// info [B][GTOP_INSERT_INFO].  when is read under AT_TIME only; lb, ub, lb_out, ub_out all or none; info may be NULL;
+// g and rec (the fp64 corner records) are read only when push > 0.  One wavefront per trajectory, one launch.
+hipError_t gtop_launch_insert_waypoints(const GtopGrid &g, const double *rec, int mode, double min_fraction, double push,
+                                        double push_below, double bos, double vos, double aos, int B, int m,
+                                        const double *x, const double *coeff, const double *T, int t_stride,
+                                        const double *when, int when_stride, const double *lb, const double *ub,
+                                        double *x_out, double *T_out, double *lb_out, double *ub_out, double *info,
+                                        hipStream_t stream);
+
 #endif  // GTOP_KERNELS_H_

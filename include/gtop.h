@@ -91,6 +91,7 @@ const char *gtop_last_error(const gtop_ctx *ctx);
  * continuous-time clearance certificate, gtop_certify_trajectories_device /
  * gtop_certify_batch / gtop_select_best_certified_device; 11: the certificate
  * against the moving boxes, gtop_certify_moving_device / gtop_certify_moving_batch;
+ * 12: waypoint insertion, gtop_insert_waypoints_device / gtop_insert_waypoints;
  * nothing of an earlier version changed meaning). */
 int gtop_abi_version(void);
 
@@ -1071,6 +1072,112 @@ int gtop_certify_moving_device(gtop_ctx *ctx, int B, int m, const void *d_coeff,
                                void *hip_stream);
 int gtop_certify_moving_batch(gtop_ctx *ctx, int B, const double *x,
                               const gtop_certify_moving_opts *opt, double *cert);
+
+/* ---- waypoint insertion (ABI version 12) --------------------------------- */
+/* (Not in the reference: the number of segments m is fixed by setPath.)  The
+ * per-segment report names two remedies for a row that fails; stretching a time is
+ * gtop_reallocate_times, this is the other.  A row whose curve runs through an
+ * obstacle has no free variable where the collision is: the call cuts ONE segment s
+ * of each of the B rows at a local time tl, which gives a problem of m + 1 segments
+ * for every row (the batch stays rectangular).  The new junction carries the old
+ * curve's position, velocity and acceleration at the cut.  A quintic is fixed by its
+ * six end conditions, so in exact arithmetic the two new segments are the old one
+ * restricted to [0, tl] and [tl, Ts]: the trajectory is unchanged, and the optimizer
+ * gains nine free variables where they are needed.  Optionally the new waypoint is
+ * pushed up the static field's gradient.  Df is not touched.
+ *
+ * d_x is B x 9(m-1) and d_coeff B x m x 18 (gtop_coefficients_device of the same x,
+ * Df and T), d_T B x m or m (time_stride m or 0).  d_x_out, d_lb_out and d_ub_out are
+ * B x 9m in the layout x[i + axis * 3m]; d_T_out is B x (m+1), per trajectory also
+ * when time_stride == 0.  Under GTOP_INSERT_AT_TIME the trajectory time of row b's
+ * cut is the double d_when[b * when_stride], when_stride >= 1: a caller points at a
+ * column of a device report — report + 2 with stride GTOP_TRAJ_REPORT (the time of
+ * the least clearance), cert + 3 or cert + 4 with stride GTOP_CERT_REPORT.  d_when is
+ * not read under GTOP_INSERT_LONGEST.  d_lb and d_ub (the bounds of x): both or
+ * neither; d_lb_out and d_ub_out are required exactly when they are given.  d_info
+ * (B x GTOP_INSERT_INFO) is optional.
+ *
+ * The rule per row, every step ONE rounded fp64 operation in the order written,
+ * nothing fused (csrc/gtop_insert.hip):
+ *   1. AT_TIME: t = when.  If !(t >= 0 && t < inf) — NaN, inf, the -1 of "no
+ *      violation" in cert[4] — the row falls back to LONGEST and info[2] = 1.
+ *   2. AT_TIME: s = the segment the walk `while (idx < m-1 && ts[idx] <= t)
+ *      t -= ts[idx++]` of the reports ends in (the last segment extended), tl = the
+ *      remaining t, Ts = T[s].
+ *   3. LONGEST: s = the FIRST index of the largest T[s] (a later segment replaces
+ *      the current one only on strict >), tl = 0.5 * Ts.
+ *   4. lo = min_fraction * Ts, hi = Ts - lo, tl = fmin(fmax(tl, lo), hi); info[3] = 1
+ *      if that changed tl.
+ *   5. T_out[s] = tl, T_out[s+1] = Ts - tl; the other times are copied, shifted by
+ *      one behind s.
+ *   6. Per axis, c the coefficients of segment s: p = the getTraj point, ((((0 +
+ *      t5 c5) + t4 c4) + t3 c3) + t2 c2) + tl c1) + c0 with t2 = tl tl, t3 = t2 tl,
+ *      t4 = t2 t2, t5 = t4 tl.  When `when` is a report's entry 2 and the clamp is
+ *      idle, the new waypoint IS that sample, bit for bit.
+ *   7. v = ((((5 c5) tl + 4 c4) tl + 3 c3) tl + 2 c2) tl + c1,
+ *      a = (((20 c5) tl + 12 c4) tl + 6 c3) tl + 2 c2, the integer factor applied to
+ *      the coefficient first.
+ *   8. push > 0 only (otherwise no field is needed): (d, g) = what
+ *      gtop_edt_query_device returns for (p, -1), bit for bit.  n = sqrt(gx gx +
+ *      gy gy + gz gz), summed left to right.  Unless the point is out of the map, or
+ *      d >= push_below, or n == 0: p_k = p_k + (push * g_k) / n.  v and a stay.
+ *      info[4] = d (0 when push is off), info[5] = pushed, 0 or 1.  The pushed point
+ *      is NOT tested against the map or the field: push is a start for the
+ *      optimizer, which the next report judges.
+ *   9. Junction k' = 1 .. m of the output: k' <= s is old junction k'; k' == s + 1
+ *      is the new (p, v, a); k' > s + 1 is old junction k' - 1.
+ *  10. Bounds: old entries are copied by the same map; the new waypoint takes
+ *      gtop_default_bounds' rule around the FINAL p: p -+ bos, -+vos, -+aos.  The new
+ *      v and a are the old curve's and may lie beyond vos / aos: that is legal
+ *      input, gtop_optimize_device_ex clamps its start point into the bounds.
+ *  11. info[0] = s, info[1] = tl.
+ * A row's bits depend on that row's inputs only: not on B, on its index, or on
+ * time_stride.  A NaN or zero segment time gives garbage in that row only; the call
+ * stays memory-safe.
+ *
+ * The loop is coefficients -> report / certify -> insert -> optimise on m + 1:
+ *   gtop_coefficients_device, gtop_validate_trajectories_device or
+ *   gtop_certify_trajectories_device, gtop_insert_waypoints_device,
+ *   [gtop_min_jerk_start_device,] gtop_optimize_device_ex on (x_out, T_out, m + 1),
+ *   gtop_coefficients_device, gtop_validate_trajectories_device,
+ *   gtop_select_best_device
+ * — all on one stream, capturable as one graph.
+ *
+ * One wavefront per trajectory; every output entry is written exactly once.  The
+ * device form only enqueues one launch: no allocation, no synchronisation,
+ * capturable; the field is read at replay.  Outputs must not overlap inputs or each
+ * other.  GTOP_ERR_INVALID, nothing launched: opt NULL, an unknown mode, reserved
+ * != 0, min_fraction outside (0, 0.5] or NaN, a non-finite push or push_below, with
+ * bounds a bos, vos or aos that is negative or not finite, lb without ub (or ub
+ * without lb), bounds without their outputs (or outputs without bounds), B < 0, m
+ * outside 2 .. 226 (m + 1 must be servable), a time_stride that is neither 0 nor m,
+ * when_stride < 1 under AT_TIME, and for B > 0 a NULL x, coeff, T, x_out or T_out,
+ * or a NULL when under AT_TIME.  push > 0 without a resident fp64 field:
+ * GTOP_ERR_STATE.  B = 0 launches nothing.
+ * gtop_insert_waypoints serves the first B rows of the context's problem at free
+ * variables x (1 <= B <= the problem's batch; GTOP_ERR_STATE when none is set), the
+ * coefficients staged as gtop_validate_batch stages them; when may be NULL under
+ * LONGEST (one entry per row otherwise), lb / ub / lb_out / ub_out and info as above.
+ * The context's problem is NOT changed: pass T_out to gtop_set_problem(B, m + 1,
+ * T_out, m + 1, Df).  fp64 only; not forwarded by groups. */
+#define GTOP_INSERT_AT_TIME 0 /* cut at the trajectory time d_when gives */
+#define GTOP_INSERT_LONGEST 1 /* cut the longest segment in the middle */
+typedef struct {
+  int32_t mode;
+  double min_fraction;     /* in (0, 0.5]: the cut keeps this share of the segment on either side */
+  double push, push_below; /* push <= 0: off; else the step up the gradient where the distance is below push_below */
+  double bos, vos, aos;    /* bounds of the new waypoint, read only when lb / ub are given */
+  int32_t reserved;        /* must be 0 */
+} gtop_insert;
+#define GTOP_INSERT_INFO 6
+int gtop_insert_waypoints_device(gtop_ctx *ctx, const gtop_insert *opt, int B, int m, const void *d_x,
+                                 const void *d_coeff, const void *d_T, int time_stride,
+                                 const void *d_when, int when_stride, const void *d_lb,
+                                 const void *d_ub, void *d_x_out, void *d_T_out, void *d_lb_out,
+                                 void *d_ub_out, void *d_info, void *hip_stream);
+int gtop_insert_waypoints(gtop_ctx *ctx, const gtop_insert *opt, int B, const double *x,
+                          const double *when, const double *lb, const double *ub, double *x_out,
+                          double *T_out, double *lb_out, double *ub_out, double *info);
 
 /* ---- bookkeeping the reference keeps inside the callback ------------ */
 
