@@ -211,59 +211,22 @@ ENTRY_POINTS = {
     "gtop_group_read_gathered": (0, _i, [_vp, _i, _dp, _dp]),
     "gtop_group_device_buffers": (0, _i, [_vp, _i] + [C.POINTER(_vp)] * 6),
     "gtop_group_optimize_batch_ex": (0, _i, [_vp, _i, _dp, _dp, _dp, _stop, _dp, _i32p, _i32p]),
-}
-ABI_VERSION = max(since for since, _, _ in ENTRY_POINTS.values())
-
-# The entry points of ABI version 10 (the continuous-time clearance certificate; certify.py wraps them), in a table of
-# their own: ENTRY_POINTS and ABI_VERSION above are the record of the library up to version 9.  Same layout.
-ENTRY_POINTS_10 = {
     "gtop_certify_trajectories_device": (10, _i, [_vp, _i, _i, _vp, _vp, _i, _certify, _vp, _vp]),
     "gtop_certify_batch": (10, _i, [_vp, _i, _dp, _certify, _dp]),
     "gtop_select_best_certified_device": (10, _i, [_vp, _i, _vp, _vp, _vp, _limits, _i, _vp, _vp, _vp]),
-}
-# the record of the library up to version 10: the two tables above
-LIBRARY_ABI_VERSION = max(since for table in (ENTRY_POINTS, ENTRY_POINTS_10) for since, _, _ in table.values())
-
-# The entry points of ABI version 11 (the certificate against the moving boxes; certify.py wraps them), a third table of
-# the same layout: the two above and their constants stay the records up to their versions.
-ENTRY_POINTS_11 = {
     "gtop_certify_moving_device": (11, _i, [_vp, _i, _i, _vp, _vp, _i, _certify_moving, _vp, _vp]),
     "gtop_certify_moving_batch": (11, _i, [_vp, _i, _dp, _certify_moving, _dp]),
-}
-# the ABI version of the library this package is built with (gtop_abi_version() of the in-tree build)
-BUILD_ABI_VERSION = max(since for table in (ENTRY_POINTS, ENTRY_POINTS_10, ENTRY_POINTS_11)
-                        for since, _, _ in table.values())
-
-# The entry points of ABI version 12 (waypoint insertion; insert.py wraps them), a fourth table of the same layout: the
-# three above and their constants stay the records up to their versions (BUILD_ABI_VERSION: up to 11).
-ENTRY_POINTS_12 = {
     "gtop_insert_waypoints_device": (12, _i, [_vp, _insert, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp,
                                               _vp, _vp, _vp]),
     "gtop_insert_waypoints": (12, _i, [_vp, _insert, _i, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
 }
-# the ABI version gtop_abi_version() of the in-tree build returns: the four tables
-CURRENT_ABI_VERSION = max(since for table in (ENTRY_POINTS, ENTRY_POINTS_10, ENTRY_POINTS_11, ENTRY_POINTS_12)
-                          for since, _, _ in table.values())
+# the ABI version this package speaks: gtop_abi_version() of the in-tree build
+ABI_VERSION = max(since for since, _, _ in ENTRY_POINTS.values())
 
 
 def entry_points(abi):
     """The names a library of ABI version `abi` has."""
     return [name for name, (since, _, _) in ENTRY_POINTS.items() if since <= abi]
-
-
-def entry_points_10(abi):
-    """Likewise, of the second table."""
-    return [name for name, (since, _, _) in ENTRY_POINTS_10.items() if since <= abi]
-
-
-def entry_points_11(abi):
-    """Likewise, of the third table."""
-    return [name for name, (since, _, _) in ENTRY_POINTS_11.items() if since <= abi]
-
-
-def entry_points_12(abi):
-    """Likewise, of the fourth table."""
-    return [name for name, (since, _, _) in ENTRY_POINTS_12.items() if since <= abi]
 
 
 def library_path():
@@ -311,14 +274,5 @@ def load_library():
     for name in entry_points(L.gtop_abi_version() if other else ABI_VERSION):
         f = getattr(L, name)
         _, f.restype, f.argtypes = ENTRY_POINTS[name]
-    for name in entry_points_10(L.gtop_abi_version() if other else LIBRARY_ABI_VERSION):   # (the same rule)
-        f = getattr(L, name)
-        _, f.restype, f.argtypes = ENTRY_POINTS_10[name]
-    for name in entry_points_11(L.gtop_abi_version() if other else BUILD_ABI_VERSION):
-        f = getattr(L, name)
-        _, f.restype, f.argtypes = ENTRY_POINTS_11[name]
-    for name in entry_points_12(L.gtop_abi_version() if other else CURRENT_ABI_VERSION):
-        f = getattr(L, name)
-        _, f.restype, f.argtypes = ENTRY_POINTS_12[name]
     _lib = L
     return L

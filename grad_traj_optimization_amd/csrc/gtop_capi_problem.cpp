@@ -5,6 +5,16 @@
 #include "gtop_ctx.h"
 #include "gtop_minjerk_plan.h"
 
+// (gtop_ctx.h) what every host form that goes from x to coefficients stages
+int gtop_stage_coefficients(gtop_ctx *c, int B, const double *x) {
+  const int m = c->m;
+  const size_t n = 9 * (size_t)(m - 1), ncoef = (size_t)B * m * 18;
+  HIPCHK(c, c->mma_g.reserve(ncoef > (size_t)B * n ? ncoef : (size_t)B * n));
+  HIPCHK(c, hipMemcpyAsync(c->d_x.data(), x, (size_t)B * n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  return gtop_coefficients_device(c, B, m, c->d_x.data(), c->d_Df.data(), c->d_T.data(), c->t_stride, c->mma_g.data(),
+                                  c->stream);
+}
+
 extern "C" {
 
 int gtop_set_problem(gtop_ctx *c, int B, int m, const double *segment_time, int time_stride,
@@ -162,19 +172,15 @@ int gtop_trajectory_stats(gtop_ctx *c, int B, const double *x, double dt_sample,
 int gtop_trajectory_samples(gtop_ctx *c, int B, const double *x, double dt_sample, double *coeff, double *stats,
                             double *samples, int max_samples) try {
   if (!c) return GTOP_ERR_INVALID;
-  if (c->B == 0) return fail(c, GTOP_ERR_STATE, "gtop_set_problem / gtop_set_paths has not been called");
-  if (B < 1 || B > c->B || !x || (!coeff && !stats && !samples) || max_samples < 0 || (samples && max_samples == 0))
-    return fail(c, GTOP_ERR_INVALID, "trajectory_stats: 1 <= B <= problem batch, x and an output required");
+  int rc;
+  if ((rc = gtop_problem_rows(c, B, x && (coeff || stats || samples) && max_samples >= 0 && !(samples && max_samples == 0),
+                              "trajectory_stats: 1 <= B <= problem batch, x and an output required")))
+    return rc;
   HIPCHK(c, hipSetDevice(c->device));
   const int m = c->m;
-  const size_t n = 9 * (size_t)(m - 1), ncoef = (size_t)B * m * 18;
-  int rc;
-  HIPCHK(c, c->mma_g.reserve(ncoef > (size_t)B * n ? ncoef : (size_t)B * n));   // coefficient scratch
+  const size_t ncoef = (size_t)B * m * 18;
   HIPCHK(c, c->mma_f.reserve((size_t)B * GTOP_TRAJ_STATS));
-  HIPCHK(c, hipMemcpyAsync(c->d_x.data(), x, (size_t)B * n * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  if ((rc = gtop_coefficients_device(c, B, m, c->d_x.data(), c->d_Df.data(), c->d_T.data(), c->t_stride, c->mma_g.data(),
-                                     c->stream)))
-    return rc;
+  if ((rc = gtop_stage_coefficients(c, B, x))) return rc;
   if (coeff) HIPCHK(c, hipMemcpyAsync(coeff, c->mma_g.data(), ncoef * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   if (stats || samples) {
     const size_t ns = samples ? (size_t)B * max_samples * 3 : 0;

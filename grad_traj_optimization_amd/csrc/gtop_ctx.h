@@ -5,8 +5,9 @@
 //   gtop_capi_field.cpp    the distance field: uploads, the ESDF builder, window updates, the corner records
 //   gtop_capi_problem.cpp  the problem set, path set-up, trajectory post-processing, default bounds
 //   gtop_capi_eval.cpp     the evaluation entry points and the batched optimizer
-//   gtop_capi_boxes.cpp    moving boxes, start times, queries, trajectory report and selection, per-segment report,
-//                          segment-time reallocation, waypoint insertion
+//   gtop_capi_boxes.cpp    moving boxes (both list kinds), the cost switch, start times, distance queries
+//   gtop_capi_report.cpp   the sampled reports (whole and per segment), both selections, both certificates
+//   gtop_capi_remedy.cpp   the remedies for a row that fails: segment-time reallocation, waypoint insertion
 // Host-side only: they own device buffers, fill kernel arguments, launch.  There is deliberately no CPU code path:
 // without a gfx950 device every entry point fails (GTOP_ERR_NO_DEVICE).
 #ifndef GTOP_CTX_H_
@@ -191,7 +192,45 @@ static inline bool gtop_moving_active(const gtop_ctx *c) { return c->moving_cost
 static inline bool gtop_start_times_fit(const gtop_ctx *c, int B, int problem_B) {
   return c->t0_count <= 1 || c->t0_count == B || c->t0_count == problem_B;
 }
+// The start times as a launch takes them: NULL when none are set (or the launch reads no boxes), else the list and its
+// stride (0: one value shared by the batch).
+struct GtopStartTimes {
+  const double *t0;
+  int stride;
+};
+static inline GtopStartTimes gtop_start_times(const gtop_ctx *c, bool boxes = true) {
+  return {(boxes && c->t0_count > 0) ? c->t0_dev : nullptr, c->t0_count > 1 ? 1 : 0};
+}
 // What a moving-mode launch of B trajectories hands the kernels; the checks every road shares.
 int gtop_moving_args(gtop_ctx *c, int B, int problem_B, GtopMovingArgs *mov);
+// the first `count` boxes of the list as the query, report and certificate launchers take it (gtop_kernels.h)
+static inline GtopBoxList gtop_box_list(const gtop_ctx *c, int count) {
+  const double *b = c->boxes.data();
+  const size_t n3 = (size_t)c->nbox * 3;
+  if (c->box_kind == GTOP_BOXES_POLYNOMIAL) return {GTOP_BOX_LIST_POLYNOMIAL, count, nullptr, nullptr, nullptr, b};
+  return {GTOP_BOX_LIST_CONST_VEL, count, b, b + n3, b + 2 * n3, nullptr};
+}
+
+// ---- the host forms over the problem set (gtop_capi_problem.cpp, _report.cpp, _remedy.cpp) ----
+// How every one of them opens: a problem is set ...
+static inline int gtop_problem_set(gtop_ctx *c) {
+  if (c->B == 0) return fail(c, GTOP_ERR_STATE, "gtop_set_problem / gtop_set_paths has not been called");
+  return GTOP_OK;
+}
+// ... and the call is of its first B rows with the buffers the form requires (`given`); `what`: the entry's own text.
+static inline int gtop_problem_rows(gtop_ctx *c, int B, bool given, const char *what) {
+  if (int rc = gtop_problem_set(c)) return rc;
+  if (B < 1 || B > c->B || !given) return fail(c, GTOP_ERR_INVALID, what);
+  return GTOP_OK;
+}
+// x of the problem's first B rows -> d_x -> their coefficients, left in mma_g (the coefficient scratch); no
+// synchronisation (gtop_capi_problem.cpp)
+int gtop_stage_coefficients(gtop_ctx *c, int B, const double *x);
+// What a sampled report of B rows asks of its arguments and of the context, before anything is staged or launched;
+// problem_B as gtop_start_times_fit's (gtop_capi_report.cpp)
+int gtop_validate_ready(gtop_ctx *c, int B, int m, int time_stride, double dt_sample, const gtop_limits *lim, int problem_B);
+// x of the problem's first B rows -> their coefficients -> the segment report in seg_rep (room for T_out behind it); no
+// synchronisation (gtop_capi_report.cpp)
+int gtop_segments_staged(gtop_ctx *c, int B, const double *x, double dt_sample, const gtop_limits *limits);
 
 #endif  // GTOP_CTX_H_

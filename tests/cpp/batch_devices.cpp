@@ -10,43 +10,24 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
-#include <fstream>
 #include <string>
 #include <vector>
 
 #include "grad_traj_optimizer.hpp"
+#include "scene_file.h"
 
 using namespace gtop_amd;
-
-static bool read_points(std::istream &in, std::vector<Vec3> &out) {
-  size_t count = 0;
-  if (!(in >> count)) return false;
-  out.resize(count);
-  for (Vec3 &p : out)
-    if (!(in >> p[0] >> p[1] >> p[2])) return false;
-  return true;
-}
 
 int main(int argc, char **argv) {
   if (argc < 5) {
     std::fprintf(stderr, "usage: %s <scene.txt> <B> <max_evals> <device> [<device> ...]\n", argv[0]);
     return 1;
   }
-  Vec3 map_size{}, origin{};
-  double resolution = 0.0;
-  std::vector<Vec3> obstacles, waypoints;
-  {
-    std::ifstream in(argv[1]);
-    std::string key;
-    while (in >> key) {
-      if (key == "map_size") in >> map_size[0] >> map_size[1] >> map_size[2];
-      else if (key == "origin") in >> origin[0] >> origin[1] >> origin[2];
-      else if (key == "resolution") in >> resolution;
-      else if (key == "obstacles") read_points(in, obstacles);
-      else if (key == "waypoints") read_points(in, waypoints);
-      else return 1;
-    }
-  }
+  scene_file::Scene sc;
+  if (!scene_file::read_scene(argv[1], sc, scene_file::LENIENT)) return 1;
+  const Vec3 &map_size = sc.map_size, &origin = sc.origin;
+  const double resolution = sc.resolution;
+  const std::vector<Vec3> &obstacles = sc.obstacles, &waypoints = sc.waypoints;
   const int B = std::atoi(argv[2]);
   std::vector<int> devices;
   bool ragged = false, fp32 = false;

@@ -7,38 +7,19 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
-#include <fstream>
 #include <string>
 #include <vector>
 
 #include "grad_traj_optimizer.hpp"
+#include "scene_file.h"
 
 using namespace gtop_amd;
+using scene_file::put_list;
 
 namespace {
 
-bool read_points(std::istream &in, std::vector<Vec3> &out) {
-  size_t count = 0;
-  if (!(in >> count)) return false;
-  out.resize(count);
-  for (Vec3 &p : out)
-    if (!(in >> p[0] >> p[1] >> p[2])) return false;
-  return true;
-}
-
 // the JSON is collected and printed at the end: the optimizer reports on stdout while it runs
 std::string json;
-
-void put_list(const char *name, const double *v, size_t count, const char *tail) {
-  json += std::string("\"") + name + "\": [";
-  char buf[64];
-  for (size_t i = 0; i < count; ++i) {
-    if (std::isinf(v[i])) std::snprintf(buf, sizeof buf, "%s%sInfinity", i ? ", " : "", v[i] < 0 ? "-" : "");
-    else std::snprintf(buf, sizeof buf, "%s%.17g", i ? ", " : "", v[i]);
-    json += buf;
-  }
-  json += std::string("]") + tail;
-}
 
 void put_certificate(const char *name, GradTrajOptimizer &opt, double margin, int max_depth, int max_refine) {
   GradTrajOptimizer::CertifyOptions o;
@@ -50,7 +31,7 @@ void put_certificate(const char *name, GradTrajOptimizer &opt, double margin, in
   const double row[8] = {(double)r.verdict, r.lo, r.hi, r.hi_time, r.first_violation_time, (double)r.n_undecided,
                          (double)r.n_refinements, r.time_sum};
   json += std::string("\"") + name + "\": {\"safe\": " + (safe ? "1" : "0") + ", \"ok\": " + (opt.ok() ? "1" : "0") + ", ";
-  put_list("cert", row, 8, "},\n");
+  put_list(json, "cert", row, 8, "},\n");
 }
 
 }  // namespace
@@ -60,24 +41,8 @@ int main(int argc, char **argv) {
     std::fprintf(stderr, "usage: %s <scene.txt> [max_evals]\n", argv[0]);
     return 1;
   }
-  Vec3 map_size{}, origin{};
-  double resolution = 0.0;
-  std::vector<Vec3> obstacles, waypoints;
-  std::ifstream in(argv[1]);
-  std::string key;
-  while (in >> key) {
-    bool good = true;
-    if (key == "map_size") good = bool(in >> map_size[0] >> map_size[1] >> map_size[2]);
-    else if (key == "origin") good = bool(in >> origin[0] >> origin[1] >> origin[2]);
-    else if (key == "resolution") good = bool(in >> resolution);
-    else if (key == "obstacles") good = read_points(in, obstacles);
-    else if (key == "waypoints") good = read_points(in, waypoints);
-    else good = false;
-    if (!good) {
-      std::fprintf(stderr, "scene file: bad entry '%s'\n", key.c_str());
-      return 1;
-    }
-  }
+  scene_file::Scene sc;
+  if (!scene_file::read_scene(argv[1], sc)) return 1;
   GradTrajOptimizer::Config cfg;
   cfg.max_evals = argc > 2 ? std::atoi(argv[2]) : 20;
   cfg.time_limit_2 = 5.0;            // evaluation-capped so the run is reproducible
@@ -93,16 +58,16 @@ int main(int argc, char **argv) {
     const bool safe = opt.certifyTrajectory(GradTrajOptimizer::CertifyOptions(), r);
     json += std::string("\"no_path\": {\"safe\": ") + (safe ? "1" : "0") + ", \"ok\": " + (opt.ok() ? "1" : "0") + "},\n";
   }
-  opt.initSDFMap(map_size, origin, resolution);
-  opt.updateSDFMap(obstacles);
-  opt.setPath(waypoints);
+  opt.initSDFMap(sc.map_size, sc.origin, sc.resolution);
+  opt.updateSDFMap(sc.obstacles);
+  opt.setPath(sc.waypoints);
   opt.optimizeTrajectory(OPT_SECOND_STEP);
   const bool solved = opt.ok();
   put_certificate("tight", opt, 0.05, 2, 256);
   put_certificate("wide", opt, 2.0, 2, 256);
   put_certificate("level0", opt, 0.05, 0, 0);
   put_certificate("bad_depth", opt, 0.05, 4, 256);
-  put_list("x", opt.freeDerivatives().data(), opt.freeDerivatives().size(), ",\n");
+  put_list(json, "x", opt.freeDerivatives().data(), opt.freeDerivatives().size(), ",\n");
   json += "\"done\": 1}\n";
   std::fputs(json.c_str(), stdout);
   return solved ? 0 : 2;

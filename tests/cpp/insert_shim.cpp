@@ -9,37 +9,19 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
-#include <fstream>
 #include <string>
 #include <vector>
 
 #include "grad_traj_optimizer.hpp"
+#include "scene_file.h"
 
 using namespace gtop_amd;
+using scene_file::put_list;
 
 namespace {
 
-bool read_points(std::istream &in, std::vector<Vec3> &out) {
-  size_t count = 0;
-  if (!(in >> count)) return false;
-  out.resize(count);
-  for (Vec3 &p : out)
-    if (!(in >> p[0] >> p[1] >> p[2])) return false;
-  return true;
-}
-
 // the JSON is collected and printed at the end: the optimizer reports on stdout while it runs
 std::string json;
-
-void put_list(const char *name, const double *v, size_t count, const char *tail) {
-  json += std::string("\"") + name + "\": [";
-  char buf[64];
-  for (size_t i = 0; i < count; ++i) {
-    std::snprintf(buf, sizeof buf, "%s%.17g", i ? ", " : "", v[i]);
-    json += buf;
-  }
-  json += std::string("]") + tail;
-}
 
 // x, segment times, coefficients and the whole-trajectory report of the object's current state
 bool put_state(const char *name, GradTrajOptimizer &opt, const GradTrajOptimizer::Limits &lim,
@@ -53,15 +35,15 @@ bool put_state(const char *name, GradTrajOptimizer &opt, const GradTrajOptimizer
   const bool ok = opt.ok();
   const double rep[4] = {(double)r.n_samples, r.clearance, r.clearance_time, r.time_sum};
   json += std::string("\"") + name + "\": {\"ok\": " + (ok ? "1" : "0") + ", ";
-  put_list("x", opt.freeDerivatives().data(), opt.freeDerivatives().size(), ", ");
-  put_list("segment_time", T.data(), T.size(), ", ");
-  put_list("coeff", coeff.a.data(), coeff.a.size(), ", ");
+  put_list(json, "x", opt.freeDerivatives().data(), opt.freeDerivatives().size(), ", ");
+  put_list(json, "segment_time", T.data(), T.size(), ", ");
+  put_list(json, "coeff", coeff.a.data(), coeff.a.size(), ", ");
   if (info) {
     const double row[6] = {(double)info->segment, info->local_time, (double)info->fell_back, (double)info->clamped,
                            info->distance, (double)info->pushed};
-    put_list("info", row, 6, ", ");
+    put_list(json, "info", row, 6, ", ");
   }
-  put_list("report", rep, 4, "");
+  put_list(json, "report", rep, 4, "");
   json += std::string("}") + tail;
   return ok;
 }
@@ -73,24 +55,8 @@ int main(int argc, char **argv) {
     std::fprintf(stderr, "usage: %s <scene.txt> [max_evals]\n", argv[0]);
     return 1;
   }
-  Vec3 map_size{}, origin{};
-  double resolution = 0.0;
-  std::vector<Vec3> obstacles, waypoints;
-  std::ifstream in(argv[1]);
-  std::string key;
-  while (in >> key) {
-    bool good = true;
-    if (key == "map_size") good = bool(in >> map_size[0] >> map_size[1] >> map_size[2]);
-    else if (key == "origin") good = bool(in >> origin[0] >> origin[1] >> origin[2]);
-    else if (key == "resolution") good = bool(in >> resolution);
-    else if (key == "obstacles") good = read_points(in, obstacles);
-    else if (key == "waypoints") good = read_points(in, waypoints);
-    else good = false;
-    if (!good) {
-      std::fprintf(stderr, "scene file: bad entry '%s'\n", key.c_str());
-      return 1;
-    }
-  }
+  scene_file::Scene sc;
+  if (!scene_file::read_scene(argv[1], sc)) return 1;
   GradTrajOptimizer::Limits lim;
   lim.margin = 0.3;
   GradTrajOptimizer::Config cfg;
@@ -102,9 +68,9 @@ int main(int argc, char **argv) {
     std::fprintf(stderr, "%s\n", opt.lastError());
     return 2;
   }
-  opt.initSDFMap(map_size, origin, resolution);
-  opt.updateSDFMap(obstacles);
-  opt.setPath(waypoints);
+  opt.initSDFMap(sc.map_size, sc.origin, sc.resolution);
+  opt.updateSDFMap(sc.obstacles);
+  opt.setPath(sc.waypoints);
   opt.optimizeTrajectory(OPT_SECOND_STEP);
   bool all_ok = opt.ok();
   json += "{\n";

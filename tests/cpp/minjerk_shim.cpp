@@ -6,24 +6,16 @@
 //
 //   gtop_minjerk_shim <scene.txt>
 #include <cstdio>
-#include <fstream>
 #include <string>
 #include <vector>
 
 #include "grad_traj_optimizer.hpp"
+#include "scene_file.h"
 
 using namespace gtop_amd;
+using scene_file::put_list;
 
 namespace {
-
-bool read_points(std::istream &in, std::vector<Vec3> &out) {
-  size_t count = 0;
-  if (!(in >> count)) return false;
-  out.resize(count);
-  for (Vec3 &p : out)
-    if (!(in >> p[0] >> p[1] >> p[2])) return false;
-  return true;
-}
 
 Matrix rows_of(const std::vector<Vec3> &pts) {
   Matrix mat((int)pts.size(), 3);
@@ -36,18 +28,6 @@ Matrix rows_of(const std::vector<Vec3> &pts) {
 // to stdout themselves
 std::string json;
 
-void put(const char *fmt, double v) {
-  char buf[64];
-  std::snprintf(buf, sizeof buf, fmt, v);
-  json += buf;
-}
-
-void put_list(const char *name, const double *v, size_t count, const char *tail) {
-  json += std::string("\"") + name + "\": [";
-  for (size_t i = 0; i < count; ++i) put(i ? ", %.17g" : "%.17g", v[i]);
-  json += std::string("]") + tail;
-}
-
 }  // namespace
 
 int main(int argc, char **argv) {
@@ -55,32 +35,10 @@ int main(int argc, char **argv) {
     std::fprintf(stderr, "usage: %s <scene.txt>\n", argv[0]);
     return 1;
   }
-  std::vector<Vec3> obstacles, waypoints, vel, acc;
-  std::vector<double> seg_time;
-  Vec3 skip{};
-  double resolution = 0.0;
-  std::ifstream in(argv[1]);
-  std::string key;
-  while (in >> key) {
-    bool good = true;
-    if (key == "map_size" || key == "origin") good = bool(in >> skip[0] >> skip[1] >> skip[2]);   // no map is needed
-    else if (key == "resolution") good = bool(in >> resolution);
-    else if (key == "obstacles") good = read_points(in, obstacles);
-    else if (key == "waypoints") good = read_points(in, waypoints);
-    else if (key == "velocities") good = read_points(in, vel);
-    else if (key == "accelerations") good = read_points(in, acc);
-    else if (key == "segment_times") {
-      size_t count = 0;
-      good = bool(in >> count);
-      seg_time.resize(good ? count : 0);
-      for (double &t : seg_time) good = good && bool(in >> t);
-    } else good = false;
-    if (!good) {
-      std::fprintf(stderr, "scene file: bad entry '%s'\n", key.c_str());
-      return 1;
-    }
-  }
-  const bool kino = !seg_time.empty();
+  scene_file::Scene sc;   // (no map is needed: map_size, origin, resolution and obstacles are read and left)
+  if (!scene_file::read_scene(argv[1], sc, scene_file::KINO)) return 1;
+  const std::vector<Vec3> &waypoints = sc.waypoints;
+  const bool kino = !sc.seg_time.empty();
   json += kino ? "{\"kino\": 1,\n" : "{\"kino\": 0,\n";
   bool all_ok = true;
   for (int guess = 0; guess < 2; ++guess) {
@@ -91,7 +49,7 @@ int main(int argc, char **argv) {
       std::fprintf(stderr, "%s\n", opt.lastError());
       return 2;
     }
-    if (kino) opt.setKinoPath(rows_of(waypoints), rows_of(vel), rows_of(acc), seg_time);
+    if (kino) opt.setKinoPath(rows_of(waypoints), rows_of(sc.vel), rows_of(sc.acc), sc.seg_time);
     else opt.setPath(waypoints);
     all_ok = all_ok && opt.ok();
     std::vector<double> T;
@@ -99,10 +57,10 @@ int main(int argc, char **argv) {
     Matrix coeff;
     opt.getCoefficient(coeff);
     json += std::string("\"guess") + (guess ? "1" : "0") + "\": {\"ok\": " + (opt.ok() ? "1" : "0") + ", ";
-    put_list("segment_times", T.data(), T.size(), ", ");
-    put_list("x", opt.freeDerivatives().data(), opt.freeDerivatives().size(), ", ");
+    put_list(json, "segment_times", T.data(), T.size(), ", ");
+    put_list(json, "x", opt.freeDerivatives().data(), opt.freeDerivatives().size(), ", ");
     const bool batch_too = !kino && waypoints.size() >= 4;
-    put_list("coeff", coeff.a.data(), coeff.a.size(), batch_too ? ", " : "");
+    put_list(json, "coeff", coeff.a.data(), coeff.a.size(), batch_too ? ", " : "");
     if (batch_too) {
       // GradTrajBatch forms its own start points: the whole list and its first four waypoints (two segment counts,
       // one device problem each); before an optimisation getCoefficient gives the start point's coefficients
@@ -113,8 +71,8 @@ int main(int argc, char **argv) {
       Matrix c0, c1;
       batch.getCoefficient(0, c0);
       batch.getCoefficient(1, c1);
-      put_list("batch_coeff0", c0.a.data(), c0.a.size(), ", ");
-      put_list("batch_coeff1", c1.a.data(), c1.a.size(), "");
+      put_list(json, "batch_coeff0", c0.a.data(), c0.a.size(), ", ");
+      put_list(json, "batch_coeff1", c1.a.data(), c1.a.size(), "");
     }
     json += guess ? "}\n" : "},\n";
   }

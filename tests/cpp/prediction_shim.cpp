@@ -9,24 +9,16 @@
 //   gtop_prediction_shim <scene.txt> [max_evals = 40] [optimize_on_device = 0]
 #include <cstdio>
 #include <cstdlib>
-#include <fstream>
+#include <array>
 #include <string>
 #include <vector>
 
 #include "grad_traj_optimizer.hpp"
+#include "scene_file.h"
 
 using namespace gtop_amd;
 
 namespace {
-
-bool read_points(std::istream &in, std::vector<Vec3> &out) {
-  size_t count = 0;
-  if (!(in >> count)) return false;
-  out.resize(count);
-  for (Vec3 &p : out)
-    if (!(in >> p[0] >> p[1] >> p[2])) return false;
-  return true;
-}
 
 std::string list_json(const char *name, const std::vector<double> &v) {
   std::string out = std::string("\"") + name + "\": [";
@@ -53,21 +45,12 @@ int main(int argc, char **argv) {
     std::fprintf(stderr, "usage: %s <scene.txt> [max_evals] [optimize_on_device]\n", argv[0]);
     return 1;
   }
-  Vec3 map_size{}, origin{};
-  double resolution = 0.0, start_time = 0.0;
-  std::vector<Vec3> obstacles, waypoints, scale;
+  double start_time = 0.0;
+  std::vector<Vec3> scale;
   std::vector<GradTrajOptimizer::Poly3> coef;
   std::vector<std::array<double, 2>> t_range;
-  std::ifstream in(argv[1]);
-  std::string key;
-  while (in >> key) {
-    bool good = true;
-    if (key == "map_size") good = bool(in >> map_size[0] >> map_size[1] >> map_size[2]);
-    else if (key == "origin") good = bool(in >> origin[0] >> origin[1] >> origin[2]);
-    else if (key == "resolution") good = bool(in >> resolution);
-    else if (key == "obstacles") good = read_points(in, obstacles);
-    else if (key == "waypoints") good = read_points(in, waypoints);
-    else if (key == "start_time") good = bool(in >> start_time);
+  const auto more = [&](const std::string &key, std::istream &in, bool &good) {
+    if (key == "start_time") good = bool(in >> start_time);
     else if (key == "predictions") {
       size_t count = 0;
       good = bool(in >> count);
@@ -78,12 +61,11 @@ int main(int argc, char **argv) {
         for (double &c : coef[b]) good = good && bool(in >> c);
         good = good && bool(in >> t_range[b][0] >> t_range[b][1] >> scale[b][0] >> scale[b][1] >> scale[b][2]);
       }
-    } else good = false;
-    if (!good) {
-      std::fprintf(stderr, "scene file: bad entry '%s'\n", key.c_str());
-      return 1;
-    }
-  }
+    } else return false;
+    return true;
+  };
+  scene_file::Scene sc;
+  if (!scene_file::read_scene(argv[1], sc, 0, more)) return 1;
   GradTrajOptimizer::Config cfg;
   cfg.max_evals = argc > 2 ? std::atoi(argv[2]) : 40;
   cfg.time_limit_2 = 5.0;          // evaluation-capped so the run is reproducible
@@ -93,9 +75,9 @@ int main(int argc, char **argv) {
     std::fprintf(stderr, "%s\n", opt.lastError());
     return 2;
   }
-  opt.initSDFMap(map_size, origin, resolution);
-  opt.updateSDFMap(obstacles);
-  opt.setPath(waypoints);
+  opt.initSDFMap(sc.map_size, sc.origin, sc.resolution);
+  opt.updateSDFMap(sc.obstacles);
+  opt.setPath(sc.waypoints);
   // a list the interface refuses (t1 > t2) is reported and changes nothing
   std::vector<std::array<double, 2>> backwards = t_range;
   if (!backwards.empty()) backwards[0] = {1.0, 0.0};

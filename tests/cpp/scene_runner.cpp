@@ -9,57 +9,15 @@
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
-#include <fstream>
 #include <string>
 #include <vector>
 
 #include "grad_traj_optimizer.hpp"
+#include "scene_file.h"
 
 using namespace gtop_amd;
 
 namespace {
-
-struct Scene {
-  Vec3 map_size{}, origin{};
-  double resolution = 0.0;
-  std::vector<Vec3> obstacles, waypoints, vel, acc;
-  std::vector<double> seg_time;   // with vel/acc: the kinodynamic form (setKinoPath)
-};
-
-bool read_points(std::istream &in, std::vector<Vec3> &out) {
-  size_t count = 0;
-  if (!(in >> count)) return false;
-  out.resize(count);
-  for (Vec3 &p : out)
-    if (!(in >> p[0] >> p[1] >> p[2])) return false;
-  return true;
-}
-
-bool read_scene(const char *file, Scene &sc) {
-  std::ifstream in(file);
-  std::string key;
-  while (in >> key) {
-    bool good = true;
-    if (key == "map_size") good = bool(in >> sc.map_size[0] >> sc.map_size[1] >> sc.map_size[2]);
-    else if (key == "origin") good = bool(in >> sc.origin[0] >> sc.origin[1] >> sc.origin[2]);
-    else if (key == "resolution") good = bool(in >> sc.resolution);
-    else if (key == "obstacles") good = read_points(in, sc.obstacles);
-    else if (key == "waypoints") good = read_points(in, sc.waypoints);
-    else if (key == "velocities") good = read_points(in, sc.vel);
-    else if (key == "accelerations") good = read_points(in, sc.acc);
-    else if (key == "segment_times") {
-      size_t count = 0;
-      good = bool(in >> count);
-      sc.seg_time.resize(good ? count : 0);
-      for (double &t : sc.seg_time) good = good && bool(in >> t);
-    } else good = false;
-    if (!good) {
-      std::fprintf(stderr, "scene file: bad entry '%s'\n", key.c_str());
-      return false;
-    }
-  }
-  return sc.resolution > 0.0 && sc.waypoints.size() >= 3;
-}
 
 Matrix rows_of(const std::vector<Vec3> &pts) {
   Matrix mat((int)pts.size(), 3);
@@ -81,8 +39,9 @@ int main(int argc, char **argv) {
     std::fprintf(stderr, "usage: %s <scene.txt> [max_evals] [optimize_on_device]\n", argv[0]);
     return 1;
   }
-  Scene sc;
-  if (!read_scene(argv[1], sc)) return 1;
+  scene_file::Scene sc;
+  if (!scene_file::read_scene(argv[1], sc, scene_file::KINO)) return 1;
+  if (!(sc.resolution > 0.0 && sc.waypoints.size() >= 3)) return 1;
 
   GradTrajOptimizer::Config cfg;   // defaults = launch/opti_node.launch:3-28 of the reference
   cfg.max_evals = argc > 2 ? std::atoi(argv[2]) : 60;

@@ -6,24 +6,15 @@
 //   gtop_validate_shim <scene.txt> [max_evals = 40] [optimize_on_device = 0]
 #include <cstdio>
 #include <cstdlib>
-#include <fstream>
 #include <string>
 #include <vector>
 
 #include "grad_traj_optimizer.hpp"
+#include "scene_file.h"
 
 using namespace gtop_amd;
 
 namespace {
-
-bool read_points(std::istream &in, std::vector<Vec3> &out) {
-  size_t count = 0;
-  if (!(in >> count)) return false;
-  out.resize(count);
-  for (Vec3 &p : out)
-    if (!(in >> p[0] >> p[1] >> p[2])) return false;
-  return true;
-}
 
 // one state's JSON entry, as text (printed at the end: the optimizer reports on stdout while it runs)
 std::string state_json(const char *name, GradTrajOptimizer &opt, const GradTrajOptimizer::Limits &lim, bool comma) {
@@ -52,24 +43,8 @@ int main(int argc, char **argv) {
     std::fprintf(stderr, "usage: %s <scene.txt> [max_evals] [optimize_on_device]\n", argv[0]);
     return 1;
   }
-  Vec3 map_size{}, origin{};
-  double resolution = 0.0;
-  std::vector<Vec3> obstacles, waypoints;
-  std::ifstream in(argv[1]);
-  std::string key;
-  while (in >> key) {
-    bool good = true;
-    if (key == "map_size") good = bool(in >> map_size[0] >> map_size[1] >> map_size[2]);
-    else if (key == "origin") good = bool(in >> origin[0] >> origin[1] >> origin[2]);
-    else if (key == "resolution") good = bool(in >> resolution);
-    else if (key == "obstacles") good = read_points(in, obstacles);
-    else if (key == "waypoints") good = read_points(in, waypoints);
-    else good = false;   // (the kinodynamic entries are not used here)
-    if (!good) {
-      std::fprintf(stderr, "scene file: bad entry '%s'\n", key.c_str());
-      return 1;
-    }
-  }
+  scene_file::Scene sc;
+  if (!scene_file::read_scene(argv[1], sc)) return 1;
   GradTrajOptimizer::Config cfg;
   cfg.max_evals = argc > 2 ? std::atoi(argv[2]) : 40;
   cfg.time_limit_2 = 5.0;          // evaluation-capped so the run is reproducible
@@ -85,9 +60,9 @@ int main(int argc, char **argv) {
   // before a path is set there is nothing to validate: refused, not a crash
   const bool early = opt.validateTrajectory(lim);
   const bool early_ok = opt.ok();
-  opt.initSDFMap(map_size, origin, resolution);
-  opt.updateSDFMap(obstacles);
-  opt.setPath(waypoints);
+  opt.initSDFMap(sc.map_size, sc.origin, sc.resolution);
+  opt.updateSDFMap(sc.obstacles);
+  opt.setPath(sc.waypoints);
   if (!opt.ok()) {
     std::fprintf(stderr, "%s\n", opt.lastError());
     return 2;

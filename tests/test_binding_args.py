@@ -12,6 +12,8 @@ parameter, set_sdf_device and set_start_times_device):
   5. the table of entry points and the selection by ABI version."""
 import ctypes as C
 import math
+import os
+import re
 import types
 
 import pytest
@@ -337,12 +339,33 @@ def test_entry_point_table():
              "gtop_group_set_gradient_mode": 6, "gtop_set_moving_box_polynomials": 7, "gtop_get_moving_box_kind": 7,
              "gtop_box_polynomial_centres": 7, "gtop_min_jerk_start_device": 8, "gtop_min_jerk_start": 8,
              "gtop_validate_segments_device": 9, "gtop_validate_segments": 9, "gtop_reallocate_times_device": 9,
-             "gtop_reallocate_times": 9}
+             "gtop_reallocate_times": 9, "gtop_certify_trajectories_device": 10, "gtop_certify_batch": 10,
+             "gtop_select_best_certified_device": 10, "gtop_certify_moving_device": 11, "gtop_certify_moving_batch": 11,
+             "gtop_insert_waypoints_device": 12, "gtop_insert_waypoints": 12}
     for name, entry in _abi.ENTRY_POINTS.items():
         since, restype, argtypes = entry
         assert name.startswith("gtop_") and isinstance(since, int) and since >= 0 and isinstance(argtypes, list), name
         assert since == later.get(name, 0), name
-    assert _abi.ABI_VERSION == 9
+    assert _abi.ABI_VERSION == 12
     assert set(_abi.ENTRY_POINTS) - set(_abi.entry_points(3)) == set(later)
     assert set(_abi.entry_points(_abi.ABI_VERSION)) == set(_abi.ENTRY_POINTS)
-    assert set(_abi.ENTRY_POINTS) - set(_abi.entry_points(8)) == {n for n, v in later.items() if v == 9}
+    assert set(_abi.ENTRY_POINTS) - set(_abi.entry_points(8)) == {n for n, v in later.items() if v >= 9}
+    for k in (9, 10, 11):
+        assert set(_abi.ENTRY_POINTS) - set(_abi.entry_points(k)) == {n for n, v in later.items() if v > k}
+
+
+def test_entry_point_table_is_the_header(gtop):
+    """One table: every function include/gtop.h declares and no other; one version: the library's own."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    header = open(os.path.join(root, "include", "gtop.h")).read()
+    header = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", header, flags=re.S))
+    declared = set(re.findall(r"\b(gtop_[a-z0-9_]+)\(", header))
+    assert declared - set(_abi.ENTRY_POINTS) == set() and set(_abi.ENTRY_POINTS) - declared == set()
+    assert len(declared) == 108
+    capi = open(os.path.join(root, "grad_traj_optimization_amd", "csrc", "gtop_capi.cpp")).read()
+    defined, = re.findall(r"^#define GTOP_ABI_VERSION (\d+)", capi, flags=re.M)
+    assert _abi.ABI_VERSION == int(defined)
+    gtop.load_library()   # (the HIP runtime it maps first; with GTOP_HIP_LIB this is another build)
+    in_tree = C.CDLL(os.path.join(root, "grad_traj_optimization_amd", "libgtop_hip.so"))
+    in_tree.gtop_abi_version.restype = C.c_int
+    assert in_tree.gtop_abi_version() == _abi.ABI_VERSION

@@ -31,11 +31,10 @@ def test_options_structure_and_constants():
     assert (o.margin, o.max_depth, o.max_refine) == (0.0, 2, 256)
     assert (OPTS.margin, OPTS.max_depth, OPTS.max_refine) == (0.25, 2, 64)
     assert len(certify.CERT_REPORT) == 8 and (certify.REQUIRE_SAFE, certify.REQUIRE_NOT_UNSAFE) == (1, 2)
-    assert set(_abi.ENTRY_POINTS_10) == {"gtop_certify_trajectories_device", "gtop_certify_batch",
-                                         "gtop_select_best_certified_device"}
-    assert all(since == 10 for since, _, _ in _abi.ENTRY_POINTS_10.values()) and _abi.LIBRARY_ABI_VERSION == 10
-    assert not set(_abi.ENTRY_POINTS_10) & set(_abi.ENTRY_POINTS)
-    assert _abi.entry_points_10(9) == [] and set(_abi.entry_points_10(10)) == set(_abi.ENTRY_POINTS_10)
+    names = {"gtop_certify_trajectories_device", "gtop_certify_batch", "gtop_select_best_certified_device"}
+    assert {n for n, (since, _, _) in _abi.ENTRY_POINTS.items() if since == 10} == names
+    assert all(_abi.ENTRY_POINTS[n][0] == 10 for n in names) and _abi.ABI_VERSION >= 10
+    assert not names & set(_abi.entry_points(9)) and set(_abi.entry_points(10)) - set(_abi.entry_points(9)) == names
 
 
 @pytest.mark.parametrize("t_shape,stride", T_FORMS)

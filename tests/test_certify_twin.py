@@ -35,9 +35,9 @@ def runs(oracle_mod, fields):
 def test_symbols_bindings_and_abi_version_exist(gtop):
     from grad_traj_optimization_amd import _abi, certify
     lib = gtop.load_library()
-    assert lib.gtop_abi_version() >= 10 and _abi.LIBRARY_ABI_VERSION >= 10
+    assert lib.gtop_abi_version() >= 10 and _abi.ABI_VERSION >= 10
     for name in ("gtop_certify_trajectories_device", "gtop_certify_batch", "gtop_select_best_certified_device"):
-        assert name in _abi.ENTRY_POINTS_10 and getattr(lib, name).argtypes is not None, name
+        assert _abi.ENTRY_POINTS[name][0] == 10 and getattr(lib, name).argtypes is not None, name
     for name in ("certify_device", "select_best_certified_device", "certify_batch", "GtopCertifyOpts", "CERT_REPORT"):
         assert hasattr(certify, name) and hasattr(gtop, name), name
     assert len(certify.CERT_REPORT) == ct.N_CERT

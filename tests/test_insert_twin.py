@@ -1,6 +1,6 @@
 """The numpy restatement of the waypoint insertion (tests/insert_twin.py), checked without a GPU:
 
-(1) the symbols, their bindings and the ABI constants;
+(1) the symbols, their bindings and the ABI version;
 (2) curve preservation in exact arithmetic: on rows whose fp64 inputs are exactly consistent (dyadic junction data,
     segment times that are powers of two, so the Hermite coefficients are doubles) the twin's new (p, v, a) lie within
     16 u of the exact values times their magnitudes, and — with the exact (p, v, a) and the exact times in their place
@@ -26,16 +26,15 @@ U = Fraction(1, 2 ** 53)
 def test_symbols_bindings_and_abi_constants(gtop):
     lib = gtop.load_library()
     assert lib.gtop_abi_version() >= 12
-    assert _abi.BUILD_ABI_VERSION == 11 and _abi.LIBRARY_ABI_VERSION == 10 and _abi.ABI_VERSION == 9
-    assert _abi.CURRENT_ABI_VERSION == 12
-    assert set(_abi.ENTRY_POINTS_12) == {"gtop_insert_waypoints_device", "gtop_insert_waypoints"}
-    for name in _abi.ENTRY_POINTS_12:
+    assert _abi.ABI_VERSION == 12
+    names = {"gtop_insert_waypoints_device", "gtop_insert_waypoints"}
+    assert {n for n, (since, _, _) in _abi.ENTRY_POINTS.items() if since == 12} == names
+    for name in names:
         assert getattr(lib, name).argtypes is not None, name
-    assert all(since == 12 for since, _, _ in _abi.ENTRY_POINTS_12.values())
-    assert not set(_abi.ENTRY_POINTS_12) & (set(_abi.ENTRY_POINTS) | set(_abi.ENTRY_POINTS_10) | set(_abi.ENTRY_POINTS_11))
-    assert _abi.entry_points_12(11) == [] and set(_abi.entry_points_12(12)) == set(_abi.ENTRY_POINTS_12)
-    assert len(_abi.ENTRY_POINTS_12["gtop_insert_waypoints_device"][2]) == 18
-    assert len(_abi.ENTRY_POINTS_12["gtop_insert_waypoints"][2]) == 12
+    assert all(_abi.ENTRY_POINTS[n][0] == 12 for n in names)
+    assert not names & set(_abi.entry_points(11)) and set(_abi.entry_points(12)) - set(_abi.entry_points(11)) == names
+    assert len(_abi.ENTRY_POINTS["gtop_insert_waypoints_device"][2]) == 18
+    assert len(_abi.ENTRY_POINTS["gtop_insert_waypoints"][2]) == 12
     for name in ("insert_waypoints_device", "insert_waypoints", "GtopInsert", "INSERT_INFO"):
         assert hasattr(insert, name) and hasattr(gtop, name), name
     assert [n for n, _ in insert.GtopInsert._fields_] == ["mode", "min_fraction", "push", "push_below", "bos", "vos",
