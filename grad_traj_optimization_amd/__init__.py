@@ -17,8 +17,13 @@ from .certify import (CERT_REPORT, GtopCertifyMovingOpts, GtopCertifyOpts, certi
 from . import certify  # noqa: F401
 from .insert import INSERT_INFO, GtopInsert, insert_waypoints, insert_waypoints_device  # noqa: F401
 from . import insert  # noqa: F401
+from .kinematics import (EXCEEDS, KIN_ABI_VERSION, KIN_ENTRY_POINTS, KIN_REPORT, KIN_SEG, UNDECIDED, WITHIN,  # noqa: F401
+                         GtopKinOpts, certify_kinematics_batch, certify_kinematics_device, select_best_kin_certified_device)
+from . import kinematics  # noqa: F401
 
-__all__ = ["INSERT_INFO", "GtopInsert", "insert", "insert_waypoints", "insert_waypoints_device","GTOP_F32", "GTOP_F64", "GtopError", "GtopLimits", "GtopParams", "GtopRetime", "OPTI_NODE_PARAMS",
+__all__ = ["EXCEEDS", "UNDECIDED", "WITHIN", "KIN_ABI_VERSION", "KIN_ENTRY_POINTS", "KIN_REPORT", "KIN_SEG", "GtopKinOpts", "kinematics",
+           "certify_kinematics_batch", "certify_kinematics_device", "select_best_kin_certified_device",
+"INSERT_INFO", "GtopInsert", "insert", "insert_waypoints", "insert_waypoints_device","GTOP_F32", "GTOP_F64", "GtopError", "GtopLimits", "GtopParams", "GtopRetime", "OPTI_NODE_PARAMS",
            "GtopContext", "GtopGroup", "Rendezvous", "box_polynomial_centres", "library_path", "load_library",
            "CERT_REPORT", "GtopCertifyMovingOpts", "GtopCertifyOpts", "certify", "certify_batch", "certify_device",
            "certify_moving_batch", "certify_moving_device", "select_best_certified_device"]

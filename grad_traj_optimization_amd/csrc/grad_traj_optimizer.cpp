@@ -192,6 +192,34 @@ bool GradTrajOptimizer::certifyTrajectoryMoving(const CertifyOptions &options, C
   return report.verdict == 1;
 }
 
+bool GradTrajOptimizer::certifyKinematics(const KinematicOptions &options, KinematicReport &report) {
+  if (!ctx_ || m_ < 2 || dp_.empty()) {
+    last_status_ = GTOP_ERR_STATE;
+    return false;
+  }
+  gtop_kin_opts opt{};
+  opt.max_vel = options.max_vel;
+  opt.max_acc = options.max_acc;
+  opt.per_axis = options.per_axis ? 1 : 0;
+  opt.max_depth = options.max_depth;
+  opt.max_refine = options.max_refine;
+  double r[GTOP_KIN_REPORT];
+  last_status_ = gtop_certify_kinematics_batch(ctx_, 1, dp_.data(), &opt, r, nullptr);
+  if (last_status_ != GTOP_OK) return false;
+  report.verdict = (int)r[0];
+  report.ub_vel = r[1];
+  report.lo_vel = r[2];
+  report.lo_vel_time = r[3];
+  report.ub_acc = r[4];
+  report.lo_acc = r[5];
+  report.lo_acc_time = r[6];
+  report.first_violation_time = r[7];
+  report.n_undecided = (int)r[8];
+  report.n_refinements = (int)r[9];
+  report.time_sum = r[10];
+  return report.verdict == 1;
+}
+
 bool GradTrajOptimizer::segmentReport(const Limits &limits, std::vector<SegmentReport> *rows) {
   if (!ctx_ || m_ < 2 || dp_.empty()) {
     last_status_ = GTOP_ERR_STATE;

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "gtop.h"
+#include "gtop_kinematics.h"
 
 #define OPT_INITIAL_TRY 0
 #define OPT_FIRST_STEP 1
@@ -161,6 +162,25 @@ class GradTrajOptimizer {
   // setStartTime's clock (include/gtop.h, gtop_certify_moving_batch): true iff SAFE — every point of the curve keeps
   // `margin` from the field and from every box at the time the curve is there.  Without boxes: certifyTrajectory.
   bool certifyTrajectoryMoving(const CertifyOptions &options, CertifyReport &report);
+  // The continuous-time KINEMATIC certificate of the trajectory at the current Dp (include/gtop_kinematics.h,
+  // gtop_certify_kinematics_batch): where Report's max_vel_* / max_acc_* are maxima over the getTraj samples, ub_* here
+  // bound the figure over the whole of [0, time_sum] — true iff the verdict is WITHIN: the chosen figures (the norms, or
+  // under per_axis the largest |component|) keep max_vel / max_acc at every time.  A limit <= 0 is off.  false also
+  // when the call fails (ok() tells).
+  struct KinematicOptions {
+    double max_vel = 0.0, max_acc = 0.0;
+    bool per_axis = false;
+    int max_depth = 2, max_refine = 256;
+  };
+  struct KinematicReport {
+    int verdict = 0;                                   // -1 EXCEEDS, 0 UNDECIDED, +1 WITHIN
+    double ub_vel = 0.0, lo_vel = 0.0, lo_vel_time = 0.0;   // certified upper bound; largest midpoint figure and its time
+    double ub_acc = 0.0, lo_acc = 0.0, lo_acc_time = 0.0;
+    double first_violation_time = -1.0;
+    int n_undecided = 0, n_refinements = 0;
+    double time_sum = 0.0;
+  };
+  bool certifyKinematics(const KinematicOptions &options, KinematicReport &report);
 
   // The same figures per SEGMENT (include/gtop.h, gtop_validate_segments): rows->at(s) covers the getTraj samples that
   // fall into segment s; of `limits` margin, use_boxes and dt_sample are read.  false when the call fails.

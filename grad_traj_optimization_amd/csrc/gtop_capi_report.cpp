@@ -39,25 +39,35 @@ int report_on_stream(gtop_ctx *c, bool per_segment, const char *who, int B, int 
   return GTOP_OK;
 }
 
-// Both selections: of the rows that pass the report, or (certified) of those whose certificate row passes `require`
-// too.  d_cert and require are read only then.
-int select_on_stream(gtop_ctx *c, bool certified, int B, const void *d_report, const void *d_cert, const void *d_cost,
-                     const gtop_limits *limits, int require, void *d_pass, void *d_best, void *hip_stream) {
+// Every selection: of the rows that pass the report (family 0), of those whose clearance certificate row passes
+// `require` too (1), or (2, include/gtop_kinematics.h) of those whose kinematic certificate row passes it as well, with
+// the clearance certificate optional.  d_cert, d_kin and require are read only by the family that has them.
+const char *const kSelectNeeds[3] = {"select_best: need B >= 0, best, and report and cost for B > 0",
+                                     "select_best_certified: need B >= 0, best, and report, cert and cost for B > 0",
+                                     "select_best_kin_certified: need B >= 0, best, and report, kin and cost for B > 0"};
+
+}  // namespace
+
+int gtop_select_on_stream(gtop_ctx *c, int family, int B, const void *d_report, const void *d_cert, const void *d_kin,
+                          const void *d_cost, const gtop_limits *limits, int require, void *d_pass, void *d_best,
+                          void *hip_stream) {
   if (int rc = check_limits(c, limits)) return rc;
-  if (certified && require != GTOP_CERT_REQUIRE_SAFE && require != GTOP_CERT_REQUIRE_NOT_UNSAFE)
-    return fail(c, GTOP_ERR_INVALID, "select_best_certified: require is neither SAFE nor NOT_UNSAFE");
-  if (B < 0 || !d_best || (B > 0 && (!d_report || !d_cost || (certified && !d_cert))))
-    return fail(c, GTOP_ERR_INVALID,
-                certified ? "select_best_certified: need B >= 0, best, and report, cert and cost for B > 0"
-                          : "select_best: need B >= 0, best, and report and cost for B > 0");
+  if (family != 0 && require != GTOP_CERT_REQUIRE_SAFE && require != GTOP_CERT_REQUIRE_NOT_UNSAFE)
+    return fail(c, GTOP_ERR_INVALID, family == 1 ? "select_best_certified: require is neither SAFE nor NOT_UNSAFE"
+                                                 : "select_best_kin_certified: require is neither SAFE nor NOT_UNSAFE");
+  if (B < 0 || !d_best || (B > 0 && (!d_report || !d_cost || (family == 1 && !d_cert) || (family == 2 && !d_kin))))
+    return fail(c, GTOP_ERR_INVALID, kSelectNeeds[family]);
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, gtop_launch_select_best(B, static_cast<const double *>(d_report), static_cast<const double *>(d_cost),
                                     limits->max_vel, limits->max_acc, limits->per_axis != 0, limits->allow_out_of_map != 0,
-                                    certified ? static_cast<const double *>(d_cert) : nullptr, certified ? require : 0,
+                                    family != 0 ? static_cast<const double *>(d_cert) : nullptr,
+                                    family == 2 ? static_cast<const double *>(d_kin) : nullptr, family != 0 ? require : 0,
                                     static_cast<unsigned char *>(d_pass), static_cast<int *>(d_best), c->sel_part.data(),
                                     static_cast<hipStream_t>(hip_stream)));
   return GTOP_OK;
 }
+
+namespace {
 
 // ---- the certificates.  One path serves the static entries and the moving ones: a static entry's three options go
 // through it as moving options with the boxes off (gtop_launch_traj_certify_moving launches the static kernel for no
@@ -100,22 +110,28 @@ int certify_on_stream(gtop_ctx *c, bool moving, int B, int m, const void *d_coef
   return GTOP_OK;
 }
 
+// the options of either family as the host path carries them
+struct CertifyJob {
+  bool moving;
+  const gtop_certify_moving_opts *opt;
+};
+
 // the same of the problem's first B rows, from x to cert on the host; rows_text: the entry's opening refusal
 int certify_host(gtop_ctx *c, bool moving, const char *rows_text, int B, const double *x,
                  const gtop_certify_moving_opts *opt, double *cert) {
-  int rc;
-  if ((rc = gtop_problem_rows(c, B, x && cert, rows_text))) return rc;
-  if ((rc = certify_ready(c, moving, B, c->m, c->t_stride, opt, c->B))) return rc;   // (before anything is staged)
-  HIPCHK(c, hipSetDevice(c->device));
-  const size_t ncert = (size_t)B * GTOP_CERT_REPORT;
-  HIPCHK(c, c->val_rep.reserve(ncert));
-  if ((rc = gtop_stage_coefficients(c, B, x))) return rc;
-  if ((rc = certify_on_stream(c, moving, B, c->m, c->mma_g.data(), c->d_T.data(), c->t_stride, opt, c->val_rep.data(),
-                              c->stream, c->B)))
-    return rc;
-  HIPCHK(c, hipMemcpyAsync(cert, c->val_rep.data(), ncert * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return GTOP_OK;
+  const CertifyJob job = {moving, opt};
+  return gtop_certificate_host(
+      c, rows_text, B, x, cert != nullptr, &job,
+      [](gtop_ctx *c, int B, const void *j) {
+        const CertifyJob *job = static_cast<const CertifyJob *>(j);
+        return certify_ready(c, job->moving, B, c->m, c->t_stride, job->opt, c->B);
+      },
+      [](gtop_ctx *c, int B, const void *j, double *d_rows, double *) {
+        const CertifyJob *job = static_cast<const CertifyJob *>(j);
+        return certify_on_stream(c, job->moving, B, c->m, c->mma_g.data(), c->d_T.data(), c->t_stride, job->opt, d_rows,
+                                 c->stream, c->B);
+      },
+      GTOP_CERT_REPORT, cert, 0, nullptr);
 }
 
 }  // namespace
@@ -128,6 +144,24 @@ int gtop_validate_ready(gtop_ctx *c, int B, int m, int time_stride, double dt_sa
   if (!gtop_start_times_fit(c, B, problem_B))
     return fail(c, GTOP_ERR_INVALID, "validate: the number of start times does not match the batch");
   return c->field.need_records64(c);
+}
+
+int gtop_certificate_host(gtop_ctx *c, const char *rows_text, int B, const double *x, bool given, const void *job,
+                          gtop_certificate_ready_fn ready, gtop_certificate_launch_fn launch, int row_cols, double *rows,
+                          int seg_cols, double *segs) {
+  int rc;
+  if ((rc = gtop_problem_rows(c, B, x && given, rows_text))) return rc;
+  if ((rc = ready(c, B, job))) return rc;   // (before anything is staged)
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t nrows = (size_t)B * row_cols, nsegs = segs ? (size_t)B * c->m * seg_cols : 0;
+  HIPCHK(c, c->val_rep.reserve(nrows + nsegs));
+  if ((rc = gtop_stage_coefficients(c, B, x))) return rc;
+  double *d_rows = c->val_rep.data(), *d_segs = segs ? d_rows + nrows : nullptr;
+  if ((rc = launch(c, B, job, d_rows, d_segs))) return rc;
+  HIPCHK(c, hipMemcpyAsync(rows, d_rows, nrows * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (segs) HIPCHK(c, hipMemcpyAsync(segs, d_segs, nsegs * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return GTOP_OK;
 }
 
 int gtop_segments_staged(gtop_ctx *c, int B, const double *x, double dt_sample, const gtop_limits *limits) {
@@ -151,14 +185,14 @@ int gtop_validate_trajectories_device(gtop_ctx *c, int B, int m, const void *d_c
 int gtop_select_best_device(gtop_ctx *c, int B, const void *d_report, const void *d_cost, const gtop_limits *limits,
                             void *d_pass, void *d_best, void *hip_stream) try {
   if (!c) return GTOP_ERR_INVALID;
-  return select_on_stream(c, false, B, d_report, nullptr, d_cost, limits, 0, d_pass, d_best, hip_stream);
+  return gtop_select_on_stream(c, 0, B, d_report, nullptr, nullptr, d_cost, limits, 0, d_pass, d_best, hip_stream);
 } GTOP_CATCH_STATUS(c)
 
 int gtop_select_best_certified_device(gtop_ctx *c, int B, const void *d_report, const void *d_cert, const void *d_cost,
                                       const gtop_limits *limits, int require, void *d_pass, void *d_best,
                                       void *hip_stream) try {
   if (!c) return GTOP_ERR_INVALID;
-  return select_on_stream(c, true, B, d_report, d_cert, d_cost, limits, require, d_pass, d_best, hip_stream);
+  return gtop_select_on_stream(c, 1, B, d_report, d_cert, nullptr, d_cost, limits, require, d_pass, d_best, hip_stream);
 } GTOP_CATCH_STATUS(c)
 
 int gtop_validate_batch(gtop_ctx *c, int B, const double *x, double dt_sample, const gtop_limits *limits,
@@ -183,7 +217,8 @@ int gtop_validate_batch(gtop_ctx *c, int B, const double *x, double dt_sample, c
   HIPCHK(c, hipMemcpyAsync(report, d_rep, nrep * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   if (cost) {
     HIPCHK(c, hipMemcpyAsync(d_cost, cost, (size_t)B * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    if ((rc = select_on_stream(c, false, B, d_rep, nullptr, d_cost, limits, 0, d_pass, d_best, c->stream))) return rc;
+    if ((rc = gtop_select_on_stream(c, 0, B, d_rep, nullptr, nullptr, d_cost, limits, 0, d_pass, d_best, c->stream)))
+      return rc;
     if (pass) HIPCHK(c, hipMemcpyAsync(pass, d_pass, (size_t)B, hipMemcpyDeviceToHost, c->stream));
     if (best) HIPCHK(c, hipMemcpyAsync(best, d_best, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
   }

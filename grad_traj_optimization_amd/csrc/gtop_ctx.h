@@ -8,6 +8,7 @@
 //   gtop_capi_boxes.cpp    moving boxes (both list kinds), the cost switch, start times, distance queries
 //   gtop_capi_report.cpp   the sampled reports (whole and per segment), both selections, both certificates
 //   gtop_capi_remedy.cpp   the remedies for a row that fails: segment-time reallocation, waypoint insertion
+//   gtop_capi_kinematics.cpp  the companion header include/gtop_kinematics.h: the kinematic certificate, its selection
 // Host-side only: they own device buffers, fill kernel arguments, launch.  There is deliberately no CPU code path:
 // without a gfx950 device every entry point fails (GTOP_ERR_NO_DEVICE).
 #ifndef GTOP_CTX_H_
@@ -232,5 +233,19 @@ int gtop_validate_ready(gtop_ctx *c, int B, int m, int time_stride, double dt_sa
 // x of the problem's first B rows -> their coefficients -> the segment report in seg_rep (room for T_out behind it); no
 // synchronisation (gtop_capi_report.cpp)
 int gtop_segments_staged(gtop_ctx *c, int B, const double *x, double dt_sample, const gtop_limits *limits);
+// The selection of every family (gtop_capi_report.cpp): 0 the rows that pass the report, 1 with the clearance
+// certificate's `require`, 2 with the kinematic certificate's too (d_cert optional then); the checks, then two launches
+int gtop_select_on_stream(gtop_ctx *c, int family, int B, const void *d_report, const void *d_cert, const void *d_kin,
+                          const void *d_cost, const gtop_limits *limits, int require, void *d_pass, void *d_best,
+                          void *hip_stream);
+// The ONE host path of the certificates (gtop_capi_report.cpp): the problem's first B rows at x -> their coefficients
+// -> `launch` on the context's stream into val_rep -> rows [B][row_cols] and, where segs is given, segs
+// [B][m][seg_cols] on the host.  `ready` states the entry's rules before anything is staged; `job` is the entry's own
+// (its options); rows_text: its opening refusal; given: the host buffers the form requires are there.
+typedef int (*gtop_certificate_ready_fn)(gtop_ctx *c, int B, const void *job);
+typedef int (*gtop_certificate_launch_fn)(gtop_ctx *c, int B, const void *job, double *d_rows, double *d_segs);
+int gtop_certificate_host(gtop_ctx *c, const char *rows_text, int B, const double *x, bool given, const void *job,
+                          gtop_certificate_ready_fn ready, gtop_certificate_launch_fn launch, int row_cols, double *rows,
+                          int seg_cols, double *segs);
 
 #endif  // GTOP_CTX_H_

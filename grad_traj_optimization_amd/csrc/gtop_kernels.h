@@ -214,10 +214,12 @@ hipError_t gtop_launch_traj_report(const GtopGrid &g, const double *rec, const G
 #define GTOP_SELECT_PARTIALS 256
 #define GTOP_SELECT_PARTIAL_BYTES 16
 // cert (may be NULL: gtop_select_best_device): the certificates of the rows, [B][GTOP_CERT_REPORT]; a row then also
-// needs verdict == +1 (require GTOP_CERT_REQUIRE_SAFE) or verdict != -1 (GTOP_CERT_REQUIRE_NOT_UNSAFE) to pass
+// needs verdict == +1 (require GTOP_CERT_REQUIRE_SAFE) or verdict != -1 (GTOP_CERT_REQUIRE_NOT_UNSAFE) to pass.
+// kin (may be NULL: both selections of include/gtop.h): the kinematic certificates, [B][GTOP_KIN_REPORT], held to the
+// same `require` (include/gtop_kinematics.h, gtop_select_best_kin_certified_device)
 hipError_t gtop_launch_select_best(int B, const double *report, const double *cost, double max_vel, double max_acc,
-                                   int per_axis, int allow_out_of_map, const double *cert, int require,
-                                   unsigned char *pass, int *best, void *workspace, hipStream_t stream);
+                                   int per_axis, int allow_out_of_map, const double *cert, const double *kin,
+                                   int require, unsigned char *pass, int *best, void *workspace, hipStream_t stream);
 
 // ---- continuous-time clearance certificate (gtop_certify.hip), fp64: the static field, and the field with the boxes ----
 #define GTOP_CERT_REPORT 8      // = include/gtop.h
@@ -258,6 +260,16 @@ hipError_t gtop_launch_retime_length(int B, int m, const double *x, const double
 hipError_t gtop_launch_retime_limits(int B, int m, double *x, const double *T, int t_stride, const double *seg_report,
                                      double max_vel, double max_acc, double max_ratio, int per_axis, int uniform,
                                      int scale_x, double *T_out, hipStream_t stream);
+
+// ---- continuous-time kinematic certificate (gtop_kinematics.hip), fp64 -------------------------------------------
+#define GTOP_KIN_REPORT 11   // = include/gtop_kinematics.h
+#define GTOP_KIN_SEG 10      // = include/gtop_kinematics.h; == GTOP_SEG_REPORT (checked in gtop_kinematics.hip)
+// kin[b] and (seg may be NULL) seg[b][s] of the trajectories (coeff, T) as include/gtop_kinematics.h lays them out:
+// certified upper and attained lower bounds of ‖v‖, ‖a‖, max|v_k|, max|a_k| over whole time intervals on the interval
+// tree of gtop_certify.hip, with its INFLATE and SLACK; one wavefront per trajectory, one launch
+hipError_t gtop_launch_traj_kinematics(int B, int m, const double *coeff, const double *T, int t_stride, double max_vel,
+                                       double max_acc, int per_axis, int max_depth, int max_refine, double *kin,
+                                       double *seg, hipStream_t stream);
 
 // ---- waypoint insertion (gtop_insert.hip), fp64 ------------------------------------------------------------------
 #define GTOP_INSERT_AT_TIME 0   // = include/gtop.h

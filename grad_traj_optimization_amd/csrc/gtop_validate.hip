@@ -206,7 +206,8 @@ constexpr int kSelBlocks = GTOP_SELECT_PARTIALS;
 
 __global__ void __launch_bounds__(256)
 select_kernel(int B, const double *__restrict__ report, const double *__restrict__ cost, SelLimits lim,
-              const double *__restrict__ cert /* NULL: no certificate asked for */, int require,
+              const double *__restrict__ cert /* NULL: no certificate asked for */,
+              const double *__restrict__ kin /* NULL: no kinematic certificate asked for */, int require,
               unsigned char *__restrict__ pass, SelPartial *__restrict__ part) {
   double c = INFINITY;
   int i = 0x7fffffff, n = 0;
@@ -221,6 +222,10 @@ select_kernel(int B, const double *__restrict__ report, const double *__restrict
     ok &= isfinite(cb);
     if (cert) {                                          // gtop_select_best_certified_device: the verdict, entry 0
       const double verdict = cert[(size_t)b * GTOP_CERT_REPORT];
+      ok &= require == GTOP_CERT_REQUIRE_SAFE ? verdict == 1.0 : verdict != -1.0;
+    }
+    if (kin) {                                           // gtop_select_best_kin_certified_device: likewise, WITHIN = +1
+      const double verdict = kin[(size_t)b * GTOP_KIN_REPORT];
       ok &= require == GTOP_CERT_REQUIRE_SAFE ? verdict == 1.0 : verdict != -1.0;
     }
     if (pass) pass[b] = ok ? 1 : 0;
@@ -285,14 +290,14 @@ hipError_t gtop_launch_traj_report(const GtopGrid &g, const double *rec, const G
 }
 
 hipError_t gtop_launch_select_best(int B, const double *report, const double *cost, double max_vel, double max_acc,
-                                   int per_axis, int allow_out_of_map, const double *cert, int require,
-                                   unsigned char *pass, int *best, void *workspace, hipStream_t stream) {
+                                   int per_axis, int allow_out_of_map, const double *cert, const double *kin,
+                                   int require, unsigned char *pass, int *best, void *workspace, hipStream_t stream) {
   const int nblocks = B > 0 ? min(kSelBlocks, (B + 255) / 256) : 0;   // (no rows: best = {-1, 0} by the second stage alone)
   const SelLimits lim = {max_vel, max_acc, per_axis, allow_out_of_map};
   SelPartial *part = static_cast<SelPartial *>(workspace);
   if (nblocks > 0) {
-    hipLaunchKernelGGL(select_kernel, dim3(nblocks), dim3(256), 0, stream, B, report, cost, lim, cert, require, pass,
-                       part);
+    hipLaunchKernelGGL(select_kernel, dim3(nblocks), dim3(256), 0, stream, B, report, cost, lim, cert, kin, require,
+                       pass, part);
   }
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;

@@ -96,6 +96,14 @@ class GradTrajOptimizer {
   /* grad_traj_optimizer.h:127-130 */
   void getCostCurve(std::vector<double> &cost, std::vector<double> &time) { impl_.getCostCurve(cost, time); }
 
+  /* not in the reference: the continuous-time kinematic certificate of the optimised trajectory
+   * (include/gtop_kinematics.h) — true iff max_vel / max_acc hold at every time of [0, time_sum] */
+  using KinematicOptions = gtop_amd::GradTrajOptimizer::KinematicOptions;
+  using KinematicReport = gtop_amd::GradTrajOptimizer::KinematicReport;
+  bool certifyKinematics(const KinematicOptions &options, KinematicReport &report) {
+    return impl_.certifyKinematics(options, report);
+  }
+
   /* not in the reference: the object underneath (status, last error, evaluation count, the gtop_ctx) */
   gtop_amd::GradTrajOptimizer &impl() { return impl_; }
 
