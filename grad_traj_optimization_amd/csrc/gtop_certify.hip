@@ -8,11 +8,9 @@
 // A box that contains the curve over an interval, cut along the (at most 8) cells it touches, therefore gives a lower
 // bound of the distance over that interval from 8 trilinear values per cell — whatever the field holds.
 //
-// One WAVEFRONT per trajectory, as the reports have it, no workgroup barrier, nothing per interval to HBM.  A segment is
-// cut into 64 intervals, one per lane; an interval that is neither certified nor in violation is replaced by its 64
-// children, depth-first in ascending time, while the depth and the trajectory's refinement budget allow.  The midpoint
-// distance is the `dist` of edt_query_kernel<false> for (p, -1) through the shared lookup of gtop_edt_lookup.h: the
-// same bits.
+// One WAVEFRONT per trajectory, as the reports have it, on the interval tree of gtop_interval_tree.h: 64 intervals of a
+// segment, or of an OPEN interval, per level.  The midpoint distance is the `dist` of edt_query_kernel<false> for
+// (p, -1) through the shared lookup of gtop_edt_lookup.h: the same bits.
 //
 // With boxes the certified quantity is the query's `dist` for (x(t), start + t): the trilinear form over corner values
 // min(static, distance from the corner voxel's centre to the nearest box).  The form does not decrease when a corner
@@ -33,6 +31,8 @@
 // The certifier's own arithmetic is unfused: interval ends, radii, cell ranges, sub-boxes and vertex values round as a
 // numpy restatement of them does (tests/certify_twin.py).  (poly_vel, included above, keeps the fmas it has everywhere.)
 #pragma clang fp contract(off)
+
+#include "gtop_interval_tree.h"   // the tree, the statuses, the segment's staging, a row's verdict
 
 namespace {
 
@@ -66,9 +66,35 @@ template <bool POLY> struct CertBoxList {
   double delta;                                // the segment's allowance on the ends of a range of box time
 };
 
-enum { kCertified = 0, kOpen = 1, kViolation = 2 };
-
 __device__ __forceinline__ double cert_clamp01(double u) { return fmin(fmax(u, 0.0), 1.0); }
+
+// Cell `cell` with the corner values `values`: vmin lowered by the trilinear values at the 8 vertices of the box
+// [blo, bhi] cut to the cell.
+__device__ __forceinline__ void cert_vertex_min(const GtopGrid &g, const int cell[3], const double values[2][2][2],
+                                                const double blo[3], const double bhi[3], double &vmin) {
+  double u[3][2];
+  for (int k = 0; k < 3; ++k) {                         // the box cut to the cell, in the cell's local coordinates
+    const double c0 = (cell[k] + 0.5) * g.res + g.origin[k];
+    u[k][0] = cert_clamp01((blo[k] - c0) * g.res_inv);
+    u[k][1] = cert_clamp01((bhi[k] - c0) * g.res_inv);
+  }
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const double diff[3] = {u[0][e >> 2], u[1][(e >> 1) & 1], u[2][e & 1]};
+    vmin = fmin(vmin, gtop_edt_trilinear(diff, values).d);
+  }
+}
+// The larger of V and the largest absolute corner value of a cell: what the rounding of its forms scales with.
+__device__ __forceinline__ double cert_corner_abs(const double values[2][2][2], double V) {
+#pragma unroll
+  for (int e = 0; e < 8; ++e) V = fmax(V, fabs(values[e >> 2][(e >> 1) & 1][e & 1]));
+  return V;
+}
+// The lower bound from the vertex minimum and the largest absolute corner value of the cells touched.
+__device__ __forceinline__ double cert_lb(double vmin, double vabs, double kappa) {
+  const double lb = vmin - kappa * vabs;
+  return lb == lb ? lb : -INFINITY;                     // (a NaN in the field certifies nothing)
+}
 
 // An axis-aligned box that contains the box of row `row` at every box time of [ta, tb] (include/gtop.h).
 // Constant velocity: the faces at either end; the centre is a monotone function of the time, so are the faces.
@@ -123,11 +149,9 @@ __device__ __forceinline__ double cert_moving_bound(const CertParams &P, const C
     const bool on = !bad && dx <= span[0] && dy <= span[1] && dz <= span[2];
     if (!__ballot(on)) continue;                        // wave-uniform
     const int cell[3] = {i0[0] + dx, i0[1] + dy, i0[2] + dz};
-    double values[2][2][2], u[3][2];
+    double values[2][2][2];
     gtop_edt_cell_values(g, P.rec, cell, values);       // (a lane that is not `on` reads a clamped cell: memory-safe)
-    double V = 0.0;                                     // of the STATIC values: what the forms at any time scale with
-#pragma unroll
-    for (int e = 0; e < 8; ++e) V = fmax(V, fabs(values[e >> 2][(e >> 1) & 1][e & 1]));
+    const double V = cert_corner_abs(values, 0.0);         // of the STATIC values: what the forms at any time scale with
     double vmax = gtop_edt_vmax(values);
 #pragma unroll 1
     for (int b0 = 0; b0 < X.nbox; b0 += kChunk) {
@@ -144,25 +168,11 @@ __device__ __forceinline__ double cert_moving_bound(const CertParams &P, const C
       }
     }
     if (on) {
-      for (int k = 0; k < 3; ++k) {                     // the box cut to the cell, in the cell's local coordinates
-        const double c0 = (cell[k] + 0.5) * g.res + g.origin[k];
-        u[k][0] = cert_clamp01((blo[k] - c0) * g.res_inv);
-        u[k][1] = cert_clamp01((bhi[k] - c0) * g.res_inv);
-      }
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const double diff[3] = {u[0][e >> 2], u[1][(e >> 1) & 1], u[2][e & 1]};
-        vmin = fmin(vmin, gtop_edt_trilinear(diff, values).d);
-      }
+      cert_vertex_min(g, cell, values, blo, bhi, vmin);
       vabs = fmax(vabs, V);
     }
   }
-  double lb = -INFINITY;
-  if (!bad) {
-    lb = vmin - P.kappa * vabs;
-    if (!(lb == lb)) lb = -INFINITY;                    // (a NaN in the field certifies nothing)
-  }
-  return lb;
+  return bad ? -INFINITY : cert_lb(vmin, vabs, P.kappa);
 }
 
 // One interval [a, a + w] of segment S: the midpoint's distance into R; returns the interval's status, its lower
@@ -227,62 +237,35 @@ __device__ __forceinline__ int cert_eval(const CertParams &P, const CertSeg &S, 
         const int dx = q >> 2, dy = (q >> 1) & 1, dz = q & 1;
         if (dx > span[0] || dy > span[1] || dz > span[2]) continue;
         const int cell[3] = {i0[0] + dx, i0[1] + dy, i0[2] + dz};
-        double values[2][2][2], u[3][2];
+        double values[2][2][2];
         gtop_edt_cell_values(g, P.rec, cell, values);
-        for (int k = 0; k < 3; ++k) {                   // the box cut to the cell, in the cell's local coordinates
-          const double c0 = (cell[k] + 0.5) * g.res + g.origin[k];
-          u[k][0] = cert_clamp01((blo[k] - c0) * g.res_inv);
-          u[k][1] = cert_clamp01((bhi[k] - c0) * g.res_inv);
-        }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const double diff[3] = {u[0][e >> 2], u[1][(e >> 1) & 1], u[2][e & 1]};
-          vmin = fmin(vmin, gtop_edt_trilinear(diff, values).d);
-          vabs = fmax(vabs, fabs(values[e >> 2][(e >> 1) & 1][e & 1]));
-        }
+        cert_vertex_min(g, cell, values, blo, bhi, vmin);
+        vabs = cert_corner_abs(values, vabs);
       }
-      lb = vmin - P.kappa * vabs;
-      if (!(lb == lb)) lb = -INFINITY;                  // (a NaN in the field certifies nothing)
+      lb = cert_lb(vmin, vabs, P.kappa);
     }
   }
   return viol ? kViolation : (lb > P.margin ? kCertified : kOpen);
 }
 
-// Level L of the refinement: the 64 intervals [base + j w, base + (j + 1) w], lane j's its own; then the OPEN ones in
-// ascending time, each replaced by its children while the depth and the budget allow.  nref and nund are wave-uniform.
-template <int L, class BOXES>
-__device__ __forceinline__ void cert_level(const CertParams &P, const CertSeg &S, const BOXES &X, double base, double w,
-                                           int lane, CertLane &R, int &nref, int &nund) {
-  const double a = base + (double)lane * w;
-  double lb;
-  const int st = cert_eval(P, S, X, a, w, lane, R, lb);
-  unsigned long long open = __ballot(st == kOpen);
-  bool leaf = st != kOpen;
-  if constexpr (L < GTOP_CERT_MAX_DEPTH) {
-    const double wc = 0.015625 * w;                     // w / 64
-    while (open) {                                      // wave-uniform
-      const int j = __ffsll((long long)open) - 1;
-      open &= open - 1;
-      if (L < P.max_depth && nref < P.max_refine) {
-        ++nref;
-        const double aj = __shfl(a, j);                 // the interval being refined, from its lane
-        cert_level<L + 1>(P, S, X, aj, wc, lane, R, nref, nund);
-      } else {
-        ++nund;
-        leaf |= lane == j;
-      }
-    }
-  } else {
-    nund += __popcll(open);
-    leaf = true;
+// What the clearance certificates add to the tree (gtop_interval_tree.h): an interval's lower bound, and a leaf's into
+// the lane's lo.
+template <class BOXES> struct CertNode {
+  struct Bound {
+    double lb;
+  };
+  const CertParams &P;
+  const CertSeg &S;
+  const BOXES &X;
+  CertLane &R;
+  __device__ __forceinline__ int eval(double a, double w, int lane, Bound &b) {
+    return cert_eval(P, S, X, a, w, lane, R, b.lb);
   }
-  if (leaf) R.lo = fmin(R.lo, lb);
-}
+  __device__ __forceinline__ void leaf(const Bound &b) { R.lo = fmin(R.lo, b.lb); }
+};
 
 // One trajectory, by one wavefront: its segments in order, then the wavefront's reductions and the row of the output.
-// seg_c: 18 doubles of LDS.  The segment's coefficients are wave-uniform, and as scalar loads they, the grid and the
-// masks of four levels overflow the scalar register file (17 SGPRs spilled).  Read back from LDS they are vector
-// registers.
+// seg_c: 18 doubles of LDS, the segment's coefficients (gtop_tree_stage_segment).
 template <class BOXES>
 __device__ __forceinline__ void cert_trajectory(const CertParams &P, BOXES &X, double *seg_c, int b, int lane, int m,
                                                 const double *__restrict__ coeff, const double *__restrict__ T,
@@ -295,9 +278,7 @@ __device__ __forceinline__ void cert_trajectory(const CertParams &P, BOXES &X, d
   for (int s = 0; s < m; ++s) {
     const double Ts = ts[s], T2 = Ts * Ts, T3 = T2 * Ts;
     CertSeg S;
-    __builtin_amdgcn_wave_barrier();                // (LDS operations of one wavefront complete in order)
-    if (lane < 18) seg_c[lane] = cf[s * 18 + lane];
-    __builtin_amdgcn_wave_barrier();
+    gtop_tree_stage_segment(seg_c, cf, s, lane);
     S.cf = seg_c;
     S.t_off = t_off;
     for (int k = 0; k < 3; ++k) {
@@ -310,7 +291,8 @@ __device__ __forceinline__ void cert_trajectory(const CertParams &P, BOXES &X, d
     }
     // the largest box time of the segment is what the ends of its ranges of box time round by
     if constexpr (BOXES::kMoving) X.delta = GTOP_CERT_SLACK * (fabs(X.start) + (t_off + Ts));
-    cert_level<0>(P, S, X, 0.0, 0.015625 * Ts, lane, R, nref, nund);
+    CertNode<BOXES> N = {P, S, X, R};
+    gtop_tree_level<0>(N, P.max_depth, P.max_refine, 0.0, 0.015625 * Ts, lane, nref, nund);
     t_off += Ts;
   }
 
@@ -326,9 +308,9 @@ __device__ __forceinline__ void cert_trajectory(const CertParams &P, BOXES &X, d
   }
   if (lane == 0) {
     double *o = cert + (size_t)b * GTOP_CERT_REPORT;
-    o[0] = vt != INFINITY ? -1.0 : (nund == 0 ? 1.0 : 0.0);
+    o[0] = gtop_tree_verdict(vt, nund);
     o[1] = lo; o[2] = hd; o[3] = ht;
-    o[4] = vt != INFINITY ? vt : -1.0;
+    o[4] = gtop_tree_first_violation(vt);
     o[5] = (double)nund; o[6] = (double)nref; o[7] = t_off;
   }
 }

@@ -7,10 +7,8 @@
 // bound of the derivative after that over the segment (Taylor's theorem about the midpoint).  It needs no field, no
 // parameters and no boxes.
 //
-// The interval tree is the clearance certificate's (gtop_certify.hip): one WAVEFRONT per trajectory, no workgroup
-// barrier, nothing per interval to HBM; a segment is cut into 64 intervals, one per lane; an interval that is neither
-// certified nor in violation is replaced by its 64 children, depth-first in ascending time, while the depth and the
-// trajectory's refinement budget allow.
+// The interval tree is the clearance certificate's (gtop_interval_tree.h): one WAVEFRONT per trajectory, 64 intervals
+// of a segment or of an OPEN interval per level.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -20,6 +18,8 @@
 // Every step is ONE rounded fp64 operation in the order the header writes it: a numpy restatement reproduces the bits
 // (tests/kinematics_twin.py).  The file writes its own Horner expressions for that reason.
 #pragma clang fp contract(off)
+
+#include "gtop_interval_tree.h"   // the tree, the statuses, the segment's staging, a row's verdict
 
 static_assert(GTOP_KIN_SEG == GTOP_SEG_REPORT, "a seg buffer is legal d_seg_report input to the LIMITS reallocation");
 
@@ -41,8 +41,6 @@ struct KinLane {
   double viol_t;
   bool sviol;                           // a violating midpoint in the segment
 };
-
-enum { kCertified = 0, kOpen = 1, kViolation = 2 };
 
 __device__ __forceinline__ double kin_max3(double a, double b, double c) { return fmax(fmax(a, b), c); }
 
@@ -91,44 +89,24 @@ __device__ __forceinline__ int kin_eval(const KinParams &P, const KinSeg &S, dou
   return viol ? kViolation : (cert ? kCertified : kOpen);
 }
 
-// Level L of the refinement, as cert_level of gtop_certify.hip: the 64 intervals [base + j w, base + (j + 1) w], lane
-// j's its own; then the OPEN ones in ascending time, each replaced by its children while the depth and the budget
-// allow.  nref and nund are wave-uniform.
-template <int L>
-__device__ __forceinline__ void kin_level(const KinParams &P, const KinSeg &S, double base, double w, int lane,
-                                          KinLane &R, int &nref, int &nund) {
-  const double a = base + (double)lane * w;
-  double ub[4];
-  const int st = kin_eval(P, S, a, w, R, ub);
-  unsigned long long open = __ballot(st == kOpen);
-  bool leaf = st != kOpen;
-  if constexpr (L < GTOP_CERT_MAX_DEPTH) {
-    const double wc = 0.015625 * w;                     // w / 64
-    while (open) {                                      // wave-uniform
-      const int j = __ffsll((long long)open) - 1;
-      open &= open - 1;
-      if (L < P.max_depth && nref < P.max_refine) {
-        ++nref;
-        const double aj = __shfl(a, j);                 // the interval being refined, from its lane
-        kin_level<L + 1>(P, S, aj, wc, lane, R, nref, nund);
-      } else {
-        ++nund;
-        leaf |= lane == j;
-      }
-    }
-  } else {
-    nund += __popcll(open);
-    leaf = true;
-  }
-  if (leaf) {
+// What the kinematic certificate adds to the tree (gtop_interval_tree.h): an interval's four upper bounds, and a leaf's
+// into the segment's.  The options and the segment are held by value: behind references the compiler forms the integer
+// multiples of the coefficients (21 products) a second time and reads six coefficients again, 2 % of the launch.
+struct KinNode {
+  struct Bound {
+    double ub[4];
+  };
+  const KinParams P;
+  const KinSeg S;
+  KinLane &R;
+  __device__ __forceinline__ int eval(double a, double w, int, Bound &b) { return kin_eval(P, S, a, w, R, b.ub); }
+  __device__ __forceinline__ void leaf(const Bound &b) {
 #pragma unroll
-    for (int f = 0; f < 4; ++f) R.sub[f] = fmax(R.sub[f], ub[f]);
+    for (int f = 0; f < 4; ++f) R.sub[f] = fmax(R.sub[f], b.ub[f]);
   }
-}
+};
 
-// One trajectory per 64-lane workgroup.  seg_c: the segment's coefficients are wave-uniform, and as scalar loads they
-// and the masks of four levels overflow the scalar register file in gtop_certify.hip's kernel of the same shape; read
-// back from LDS they are vector registers.
+// One trajectory per 64-lane workgroup.  seg_c: 18 doubles of LDS, the segment's coefficients (gtop_tree_stage_segment).
 __global__ void __launch_bounds__(64)
 traj_kinematics_kernel(const KinParams P, int B, int m, const double *__restrict__ coeff, const double *__restrict__ T,
                        int t_stride, double *__restrict__ kin /*[B][GTOP_KIN_REPORT]*/,
@@ -148,9 +126,7 @@ traj_kinematics_kernel(const KinParams P, int B, int m, const double *__restrict
   for (int s = 0; s < m; ++s) {
     const double Ts = ts[s], T2 = Ts * Ts;
     KinSeg S;
-    __builtin_amdgcn_wave_barrier();                // (LDS operations of one wavefront complete in order)
-    if (lane < 18) seg_c[lane] = cf[s * 18 + lane];
-    __builtin_amdgcn_wave_barrier();
+    gtop_tree_stage_segment(seg_c, cf, s, lane);
     S.cf = seg_c;
     S.t_off = t_off;
     for (int k = 0; k < 3; ++k) {
@@ -168,7 +144,8 @@ traj_kinematics_kernel(const KinParams P, int B, int m, const double *__restrict
     for (int f = 0; f < 4; ++f) R.slo[f] = R.sub[f] = -INFINITY;
     R.sviol = false;
     const int nref0 = nref, nund0 = nund;
-    kin_level<0>(P, S, 0.0, 0.015625 * Ts, lane, R, nref, nund);
+    KinNode N = {P, S, R};
+    gtop_tree_level<0>(N, P.max_depth, P.max_refine, 0.0, 0.015625 * Ts, lane, nref, nund);
     t_off += Ts;
 
     // ---- the segment's reductions and its row ----
@@ -211,10 +188,10 @@ traj_kinematics_kernel(const KinParams P, int B, int m, const double *__restrict
   }
   if (lane == 0) {
     double *o = kin + (size_t)b * GTOP_KIN_REPORT;
-    o[0] = vt != INFINITY ? -1.0 : (nund == 0 ? 1.0 : 0.0);
+    o[0] = gtop_tree_verdict(vt, nund);
     o[1] = ub_v; o[2] = lv; o[3] = lvt;
     o[4] = ub_a; o[5] = la; o[6] = lat;
-    o[7] = vt != INFINITY ? vt : -1.0;
+    o[7] = gtop_tree_first_violation(vt);
     o[8] = (double)nund; o[9] = (double)nref; o[10] = t_off;
   }
 }

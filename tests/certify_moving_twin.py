@@ -1,10 +1,9 @@
 """The certificate against the moving boxes (include/gtop.h: gtop_certify_moving_device) restated in numpy for ONE
-trajectory, on tests/certify_twin.py: its Field, trilinear, poly_eval and — unchanged — its interval recursion, status
-rule, budget and output row.  certify() runs certify_twin.certify with two of that module's names replaced for the
-duration of the call: the run class, by one that notes which intervals a level evaluates, and the box bound, by the one
-below.  Only what the header adds is stated here, in plain fp64 operations as the header has them: the range of box
-time of an interval, the swept faces of either kind of box, and the lower bound with corner values lowered to the
-distance to the swept boxes, V taken from the static values.
+trajectory, on tests/certify_twin.py: its Field, trilinear, poly_eval, its cell and vertex loop and — as a subclass of
+its node on the tree of tests/interval_tree_twin.py — its interval evaluation, status rule and output row.  Only what
+the header adds is stated here, in plain fp64 operations as the header has them: the range of box time of an interval,
+the swept faces of either kind of box, and the lower bound with corner values lowered to the distance to the swept
+boxes, V taken from the static values.
 
 Midpoint distances come through the C oracle's evaluateEDTWithGrad (oracle.Sdf.edt_query); a polynomial box is shown to
 it as a standing box at the centre gtop_box_polynomial_centres gives for that time.  numpy fuses nothing where the
@@ -12,8 +11,6 @@ kernel's shared lookup has fmas (a constant-velocity box's centre, the corner vo
 gtop_edt_box_min): the places tests/test_gpu_certify_moving.py bounds.
 
 Also here: the box lists and rows the tests share, the moving tunnelling case, and the mutants the tests must catch."""
-from unittest import mock
-
 import numpy as np
 
 from tests import certify_twin as ct
@@ -132,88 +129,38 @@ def box_min(field, cell, values, smin, smax):
 
 def moving_lower_bound(field, boxes, blo, bhi, tau_a, tau_b, mutant=None, gaps=None):
     """lb of the curve box [blo, bhi] over the box times [tau_a, tau_b], as the header states it."""
-    f = field
-    if f.out_of_map(blo) or f.out_of_map(bhi):
-        return -np.inf
-    i0, q0 = f.cell(blo)
-    i1, q1 = f.cell(bhi)
-    if gaps is not None:
-        for q in (*q0, *q1):
-            gaps.append(abs(q - np.rint(q)) / max(abs(q), 1.0))
-        for x, lim in ((blo, f.min_range + 1e-4), (bhi, f.max_range - 1e-4)):
-            gaps.extend(np.abs(x - lim) / np.maximum(np.abs(lim), 1.0))
-    span = i1 - i0
-    if np.any(span < 0) or np.any(span > 1):
-        return -np.inf
     apply = (tau_a if mutant == "tau_a" else tau_b) >= 0.0
     if apply:
         smin, smax = boxes.swept(tau_a, tau_b, mutant)
-    vmin, vabs = np.inf, 0.0
-    for dx in range(span[0] + 1):
-        for dy in range(span[1] + 1):
-            for dz in range(span[2] + 1):
-                cell = i0 + (dx, dy, dz)
-                v = f.corners(cell)
-                V = float(np.abs(v).max())               # of the static values
-                if apply:
-                    v = box_min(f, cell, v, smin, smax)
-                if mutant == "V_after":
-                    V = float(np.abs(v).max())
-                c0 = (cell + 0.5) * f.res + f.origin
-                u = [np.minimum(np.maximum(w, 0.0), 1.0) for w in ((blo - c0) * f.res_inv, (bhi - c0) * f.res_inv)]
-                for e in range(8):
-                    o = (e >> 2, (e >> 1) & 1, e & 1)
-                    vmin = min(vmin, ct.trilinear([u[o[0]][0], u[o[1]][1], u[o[2]][2]], v))
-                vabs = max(vabs, V)
-    lb = vmin - f.kappa * vabs
-    return lb if lb == lb else -np.inf
+
+    def lower(cell, v):
+        low = box_min(field, cell, v, smin, smax) if apply else v
+        return low, (low if mutant == "V_after" else v)      # V: of the static values
+    return ct.box_lower_bound(field, blo, bhi, gaps=gaps, lower=lower)
 
 
-class _Clock:
-    """What the recursion of certify_twin does not know: the boxes, the row's start time, and — noted by _Run.level
-    below before a level's 64 intervals are evaluated — where that level lies."""
+class Node(ct.Node):
+    """What the boxes add to the clearance node: the row's start time on the boxes' clock, midpoint distances at the
+    intervals' box times, and the lower bound over an interval's range of box time."""
 
-    def __init__(self, field, boxes, start, T, mutant):
-        self.field, self.boxes, self.start, self.T, self.mutant = field, boxes, np.float64(start), T, mutant
+    def __init__(self, field, boxes, start, margin, mutant):
+        super().__init__(field, margin, None)
+        self.boxes, self.start, self.box_mutant = boxes, np.float64(start), mutant
         self.ranges = {}          # (segment, a, w) -> (blo, bhi, tau_a, tau_b)
 
-    def begin_level(self, s, t_off, base, w):
-        self.s, self.t_off, self.base, self.w, self.j = s, t_off, base, w, 0
-        self.delta = ct.SLACK * (abs(self.start) + (t_off + self.T[s]))
+    def segment(self, c, Ts, t_off):
+        super().segment(c, Ts, t_off)
+        self.delta = ct.SLACK * (abs(self.start) + (t_off + Ts))
 
-    def midpoints(self, p):
-        a = self.base + np.arange(64, dtype=np.float64) * self.w
-        t = self.t_off + (a + 0.5 * self.w)
-        return lookup(self.field, self.boxes, p, self.start + t)
+    def midpoints(self, p, t):
+        return lookup(self.f, self.boxes, p, self.start + t)
 
-    def lower_bound(self, f, blo, bhi, mutant, mid, gaps):
-        """certify_twin.box_lower_bound's place: interval j of the level, in the order the level evaluates them."""
-        a = self.base + np.float64(self.j) * self.w
-        self.j += 1
+    def lower_bound(self, s, a, w, blo, bhi, mid):
         ta = self.start + (self.t_off + a)
-        tb = self.start + (self.t_off + (a + self.w))
+        tb = self.start + (self.t_off + (a + w))
         tau_a, tau_b = ta - self.delta, tb + self.delta
-        self.ranges[(self.s, a, self.w)] = (blo, bhi, tau_a, tau_b)
-        return moving_lower_bound(self.field, self.boxes, blo, bhi, tau_a, tau_b, self.mutant, gaps)
-
-
-class _FieldWithBoxes:
-    """The Field the recursion sees: the static one, its midpoint distances taken at the level's box times."""
-
-    def __init__(self, clock):
-        self._clock = clock
-
-    def __getattr__(self, name):
-        return getattr(self._clock.field, name)
-
-    def midpoint_distance(self, pts):
-        return self._clock.midpoints(pts)
-
-
-class _Run(ct._Run):
-    def level(self, L, s, c, A, E, t_off, base, w):
-        self.f._clock.begin_level(s, t_off, base, w)
-        super().level(L, s, c, A, E, t_off, base, w)
+        self.ranges[(s, a, w)] = (blo, bhi, tau_a, tau_b)
+        return moving_lower_bound(self.f, self.boxes, blo, bhi, tau_a, tau_b, self.box_mutant, self.gaps)
 
 
 def certify(field, boxes, coeff, T, t0, margin, max_depth=2, max_refine=256, mutant=None):
@@ -222,10 +169,9 @@ def certify(field, boxes, coeff, T, t0, margin, max_depth=2, max_refine=256, mut
     evaluated."""
     if boxes is None or boxes.n == 0:
         return ct.certify(field, coeff, T, margin, max_depth, max_refine)
-    clock = _Clock(field, boxes, t0, np.asarray(T, dtype=np.float64), mutant)
-    with mock.patch.object(ct, "_Run", _Run), mock.patch.object(ct, "box_lower_bound", clock.lower_bound):
-        cert, info = ct.certify(_FieldWithBoxes(clock), coeff, T, margin, max_depth, max_refine)
-    info["ranges"] = clock.ranges
+    node = Node(field, boxes, t0, np.float64(margin), mutant)
+    cert, info = ct.run(node, coeff, T, ct.Tree(max_depth, max_refine))
+    info["ranges"] = node.ranges
     return cert, info
 
 

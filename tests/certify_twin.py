@@ -3,18 +3,17 @@ ONE trajectory, statement by statement where the header fixes the arithmetic (in
 sub-boxes, vertex values: plain fp64 operations, nothing fused — numpy fuses nothing), from pieces that are already
 tested: midpoint distances come through the C oracle's evaluateEDTWithGrad (oracle.Sdf.edt_query), corner values from
 the field array.  The velocity is numpy's unfused sum where the kernel's poly_vel has fmas: the one place the two may
-differ in the last bits, which tests/test_gpu_certify.py bounds.
+differ in the last bits, which tests/test_gpu_certify.py bounds.  The tree is the shared walk of
+tests/interval_tree_twin.py; Node is what this certificate adds to it.
 
 Also here: the fields and trajectories the tests share (CASES, wall_case), and the mutants the tests must catch."""
 import numpy as np
 
+from tests.interval_tree_twin import CERTIFIED, INFLATE, OPEN, SLACK, VIOLATION, Tree, verdict, walk
+
 N_CERT = 8
-MAX_DEPTH = 3
-INFLATE = 1.0 + 2.0 ** -40
-SLACK = 2.0 ** -40
 KAPPA = 2.0 ** -46
 MUTANTS = ("no_A", "mid_cell", "floor", "lt", "budget")
-CERTIFIED, OPEN, VIOLATION = 0, 1, 2
 
 
 class Field:
@@ -95,8 +94,9 @@ def poly_vel(c, t):
     return s
 
 
-def box_lower_bound(field, blo, bhi, mutant=None, mid=None, gaps=None):
-    """lb of one box [blo, bhi] (3,) each, as the header states it.  mid: the midpoint (for the mid_cell mutant)."""
+def box_lower_bound(field, blo, bhi, mutant=None, mid=None, gaps=None, lower=None):
+    """lb of one box [blo, bhi] (3,) each, as the header states it.  mid: the midpoint (for the mid_cell mutant).
+    lower(cell, v) -> (the cell's corner values for the forms, those the allowance scales with): the moving boxes'."""
     f = field
     if f.out_of_map(blo) or f.out_of_map(bhi):
         return -np.inf
@@ -118,7 +118,9 @@ def box_lower_bound(field, blo, bhi, mutant=None, mid=None, gaps=None):
         for dy in range(span[1] + 1):
             for dz in range(span[2] + 1):
                 cell = i0 + (dx, dy, dz)
-                v = f.corners(cell)
+                v = V = f.corners(cell)
+                if lower is not None:
+                    v, V = lower(cell, v)
                 c0 = (cell + 0.5) * f.res + f.origin
                 u = [(blo - c0) * f.res_inv, (bhi - c0) * f.res_inv]
                 if mutant == "floor":
@@ -128,35 +130,52 @@ def box_lower_bound(field, blo, bhi, mutant=None, mid=None, gaps=None):
                 for e in range(8):
                     o = (e >> 2, (e >> 1) & 1, e & 1)
                     vmin = min(vmin, trilinear([u[o[0]][0], u[o[1]][1], u[o[2]][2]], v))
-                vabs = max(vabs, float(np.abs(v).max()))
+                vabs = max(vabs, float(np.abs(V).max()))
     lb = vmin - f.kappa * vabs
     return lb if lb == lb else -np.inf
 
 
-class _Run:
-    def __init__(self, field, margin, max_depth, max_refine, mutant):
-        self.f, self.margin, self.max_depth, self.max_refine, self.mutant = field, margin, max_depth, max_refine, mutant
+class Node:
+    """What the clearance certificate adds to the tree: an interval's midpoint distance and lower bound, a leaf's into lo."""
+
+    def __init__(self, field, margin, mutant):
+        self.f, self.margin, self.mutant = field, margin, mutant
         self.lo, self.hi, self.hi_t, self.viol_t = np.inf, np.inf, 0.0, np.inf
         self.hi_at = None          # (segment, local time) of the midpoint behind hi
-        self.nref = self.nund = 0
         self.gaps = []             # relative distances of every decision from a tie
         self.leaves = []           # (segment, a, w, lb, status)
 
-    def level(self, L, s, c, A, E, t_off, base, w):
-        f, lanes = self.f, np.arange(64, dtype=np.float64)
-        a = base + lanes * w
+    def segment(self, c, Ts, t_off):
+        """Segment coefficients c (3, 6) of duration Ts from trajectory time t_off: its acceleration bound and slack."""
+        self.c, self.t_off = c, t_off
+        T2 = Ts * Ts
+        T3 = T2 * Ts
+        q = np.abs(c)
+        self.A = 2.0 * q[:, 2] + 6.0 * q[:, 3] * Ts + 12.0 * q[:, 4] * T2 + 20.0 * q[:, 5] * T3
+        Pk = ((((q[:, 5] * Ts + q[:, 4]) * Ts + q[:, 3]) * Ts + q[:, 2]) * Ts + q[:, 1]) * Ts + q[:, 0]
+        self.E = SLACK * Pk + self.f.e_map
+
+    def midpoints(self, p, t):
+        """The distances of the 64 midpoints p at the trajectory times t."""
+        return self.f.midpoint_distance(p)
+
+    def lower_bound(self, s, a, w, blo, bhi, mid):
+        """lb of the interval [a, a + w] of segment s, whose curve box is [blo, bhi]."""
+        return box_lower_bound(self.f, blo, bhi, self.mutant, mid, self.gaps)
+
+    def evaluate(self, L, s, base, w, a):
         h = 0.5 * w
         tc = a + h
-        p = np.stack([poly_eval(c[k], tc) for k in range(3)], axis=1)
-        v = np.stack([poly_vel(c[k], tc) for k in range(3)], axis=1)
+        p = np.stack([poly_eval(self.c[k], tc) for k in range(3)], axis=1)
+        v = np.stack([poly_vel(self.c[k], tc) for k in range(3)], axis=1)
         if self.mutant == "no_A":
             r = np.abs(v) * h
         else:
-            r = np.abs(v) * h + 0.5 * A * h * h
-        r = r * INFLATE + E
+            r = np.abs(v) * h + 0.5 * self.A * h * h
+        r = r * INFLATE + self.E
         blo, bhi = p - r, p + r
-        d = f.midpoint_distance(p)
-        t = t_off + tc
+        t = self.t_off + tc
+        d = self.midpoints(p, t)
         status, lbs = [], []
         for j in range(64):
             if d[j] < self.hi or (d[j] == self.hi and t[j] < self.hi_t):
@@ -165,47 +184,36 @@ class _Run:
             self.gaps.append(abs(d[j] - self.margin) / max(abs(self.margin), abs(d[j]), 1e-300))
             if viol:
                 self.viol_t = min(self.viol_t, t[j])
-            lb = box_lower_bound(f, blo[j], bhi[j], self.mutant, p[j], self.gaps)
+            lb = self.lower_bound(s, a[j], w, blo[j], bhi[j], p[j])
             if np.isfinite(lb):
                 self.gaps.append(abs(lb - self.margin) / max(abs(self.margin), abs(lb), 1e-300))
             lbs.append(lb)
             status.append(VIOLATION if viol else (CERTIFIED if lb > self.margin else OPEN))
-        for j in range(64):
-            if status[j] != OPEN:
-                self.leaf(s, a[j], w, lbs[j], status[j])
-            elif L < MAX_DEPTH and L < self.max_depth and (self.nref < self.max_refine or self.mutant == "budget"):
-                self.nref += 1
-                self.level(L + 1, s, c, A, E, t_off, a[j], 0.015625 * w)
-            else:
-                self.nund += 1
-                self.leaf(s, a[j], w, lbs[j], OPEN)
+        return status, lbs
 
     def leaf(self, s, a, w, lb, status):
         self.lo = min(self.lo, lb)
         self.leaves.append((s, a, w, lb, status))
 
 
+def run(node, coeff, T, tree):
+    """The tree of every segment of one trajectory, coeff (m, 18), T (m,), with `node`: (cert (8,), info)."""
+    coeff = np.asarray(coeff, dtype=np.float64).reshape(-1, 3, 6)
+    T = np.asarray(T, dtype=np.float64)
+    t_off = np.float64(0.0)
+    for s in range(len(T)):
+        node.segment(coeff[s], T[s], t_off)
+        walk(node, 0, s, np.float64(0.0), 0.015625 * T[s], tree)
+        t_off = t_off + T[s]
+    safe, first = verdict(node.viol_t, tree.nund)
+    cert = np.array([safe, node.lo, node.hi, node.hi_t, first, tree.nund, tree.nref, t_off])
+    return cert, dict(hi_at=node.hi_at, tie=min(node.gaps), leaves=node.leaves)
+
+
 def certify(field, coeff, T, margin, max_depth=2, max_refine=256, mutant=None):
     """One trajectory's certificate: (cert (8,), info).  coeff (m, 18), T (m,).  info: hi_at = (segment, local time) of
     the midpoint behind hi, tie = the least relative distance of any decision from a tie, leaves."""
-    coeff = np.asarray(coeff, dtype=np.float64).reshape(-1, 3, 6)
-    T = np.asarray(T, dtype=np.float64)
-    run = _Run(field, np.float64(margin), int(max_depth), int(max_refine), mutant)
-    t_off = np.float64(0.0)
-    for s in range(len(T)):
-        Ts = T[s]
-        T2 = Ts * Ts
-        T3 = T2 * Ts
-        c = np.abs(coeff[s])
-        A = 2.0 * c[:, 2] + 6.0 * c[:, 3] * Ts + 12.0 * c[:, 4] * T2 + 20.0 * c[:, 5] * T3
-        Pk = ((((c[:, 5] * Ts + c[:, 4]) * Ts + c[:, 3]) * Ts + c[:, 2]) * Ts + c[:, 1]) * Ts + c[:, 0]
-        E = SLACK * Pk + field.e_map
-        run.level(0, s, coeff[s], A, E, t_off, np.float64(0.0), 0.015625 * Ts)
-        t_off = t_off + Ts
-    unsafe = run.viol_t != np.inf
-    cert = np.array([-1.0 if unsafe else (1.0 if run.nund == 0 else 0.0), run.lo, run.hi, run.hi_t,
-                     run.viol_t if unsafe else -1.0, run.nund, run.nref, t_off])
-    return cert, dict(hi_at=run.hi_at, tie=min(run.gaps), leaves=run.leaves)
+    return run(Node(field, np.float64(margin), mutant), coeff, T, Tree(max_depth, max_refine, budget=mutant == "budget"))
 
 
 def position(coeff, s, t):

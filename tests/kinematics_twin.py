@@ -6,11 +6,9 @@ Also here: the rows the tests share (random quintics, rest-to-rest rows, the han
 mutants the tests must catch."""
 import numpy as np
 
+from tests.interval_tree_twin import CERTIFIED, INFLATE, OPEN, SLACK, VIOLATION, Tree, verdict, walk
+
 N_KIN, N_SEG = 11, 10
-MAX_DEPTH = 3
-INFLATE = 1.0 + 2.0 ** -40
-SLACK = 2.0 ** -40
-CERTIFIED, OPEN, VIOLATION = 0, 1, 2
 # no_remainder: the J / S term dropped; child32: child width w / 32; ub_all: upper bounds over every interval, not the
 # leaves; ub_no_viol: not over violating leaves; lo_level0: lo from level 0 alone; swap_axis: per_axis read backwards
 MUTANTS = ("no_remainder", "child32", "ub_all", "ub_no_viol", "lo_level0", "swap_axis")
@@ -32,26 +30,35 @@ def norm3(a):
     return np.sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2])
 
 
-class _Run:
-    def __init__(self, max_vel, max_acc, per_axis, max_depth, max_refine, mutant):
-        self.max_vel, self.max_acc = np.float64(max_vel), np.float64(max_acc)
+class Node:
+    """What the kinematic certificate adds to the tree: an interval's midpoint figures and four upper bounds, a leaf's
+    into the segment's."""
+
+    def __init__(self, max_vel, max_acc, per_axis, mutant):
+        self.max_vel, self.max_acc, self.mutant = np.float64(max_vel), np.float64(max_acc), mutant
         self.per_axis = bool(per_axis) != (mutant == "swap_axis")
-        self.max_depth, self.max_refine, self.mutant = int(max_depth), int(max_refine), mutant
         self.iv, self.ia = (2, 3) if self.per_axis else (0, 1)
         self.lo_v, self.lo_v_t, self.lo_a, self.lo_a_t, self.viol_t = -np.inf, np.inf, -np.inf, np.inf, np.inf
-        self.nref = self.nund = 0
         self.leaves = []           # (segment, a, w, ub (4,), status)
         self.open0 = 0             # OPEN intervals at level 0, all segments
 
-    def start_segment(self):
+    def segment(self, c, Ts, t_off):
+        """Segment coefficients c (3, 6) of duration Ts from trajectory time t_off: its jerk and snap bounds and slacks."""
+        self.c, self.t_off = c, t_off
         self.slo, self.sub, self.sviol = np.full(4, -np.inf), np.full(4, -np.inf), False
+        T2 = Ts * Ts
+        q1, q2, q3, q4, q5 = (np.abs(c)[:, i] for i in range(1, 6))
+        self.J = 6.0 * q3 + 24.0 * q4 * Ts + 60.0 * q5 * T2
+        self.S = 24.0 * q4 + 120.0 * q5 * Ts
+        Vk = (((5.0 * q5 * Ts + 4.0 * q4) * Ts + 3.0 * q3) * Ts + 2.0 * q2) * Ts + q1
+        Ak = ((20.0 * q5 * Ts + 12.0 * q4) * Ts + 6.0 * q3) * Ts + 2.0 * q2
+        self.EV, self.EA = SLACK * Vk, SLACK * Ak
 
-    def level(self, L, s, c, J, S, EV, EA, t_off, base, w):
-        lanes = np.arange(64, dtype=np.float64)
-        a = base + lanes * w
+    def evaluate(self, L, s, base, w, a):
+        c, J, S, EV, EA = self.c, self.J, self.S, self.EV, self.EA
         h = 0.5 * w
         tc = a + h
-        t = t_off + tc
+        t = self.t_off + tc
         v, ac, Uv, Ua = [], [], [], []
         with np.errstate(all="ignore"):
             for k in range(3):
@@ -91,15 +98,7 @@ class _Run:
                 self.sub = np.fmax(self.sub, ub[j])
         if L == 0:
             self.open0 += status.count(OPEN)
-        for j in range(64):
-            if status[j] != OPEN:
-                self.leaf(s, a[j], w, ub[j], status[j])
-            elif L < MAX_DEPTH and L < self.max_depth and self.nref < self.max_refine:
-                self.nref += 1
-                self.level(L + 1, s, c, J, S, EV, EA, t_off, a[j], (0.03125 if self.mutant == "child32" else 0.015625) * w)
-            else:
-                self.nund += 1
-                self.leaf(s, a[j], w, ub[j], OPEN)
+        return status, ub
 
     def leaf(self, s, a, w, ub, status):
         if not (self.mutant == "ub_no_viol" and status == VIOLATION):
@@ -112,31 +111,23 @@ def certify(coeff, T, max_vel=0.0, max_acc=0.0, per_axis=False, max_depth=2, max
     (segment, a, w, the four ub, status), open0 = the OPEN intervals of level 0."""
     coeff = np.asarray(coeff, dtype=np.float64).reshape(-1, 3, 6)
     T = np.asarray(T, dtype=np.float64)
-    run = _Run(max_vel, max_acc, per_axis, max_depth, max_refine, mutant)
+    run = Node(max_vel, max_acc, per_axis, mutant)
+    tree = Tree(max_depth, max_refine, child32=mutant == "child32")
     seg = np.empty((len(T), N_SEG))
     t_off = np.float64(0.0)
     ub_v = ub_a = -np.inf
     with np.errstate(all="ignore"):
         for s in range(len(T)):
-            Ts = T[s]
-            T2 = Ts * Ts
-            q = np.abs(coeff[s])
-            q1, q2, q3, q4, q5 = (q[:, i] for i in range(1, 6))
-            J = 6.0 * q3 + 24.0 * q4 * Ts + 60.0 * q5 * T2
-            S = 24.0 * q4 + 120.0 * q5 * Ts
-            Vk = (((5.0 * q5 * Ts + 4.0 * q4) * Ts + 3.0 * q3) * Ts + 2.0 * q2) * Ts + q1
-            Ak = ((20.0 * q5 * Ts + 12.0 * q4) * Ts + 6.0 * q3) * Ts + 2.0 * q2
-            run.start_segment()
-            nref0, nund0 = run.nref, run.nund
-            run.level(0, s, coeff[s], J, S, SLACK * Vk, SLACK * Ak, t_off, np.float64(0.0), 0.015625 * Ts)
-            t_off = t_off + Ts
+            run.segment(coeff[s], T[s], t_off)
+            nref0, nund0 = tree.nref, tree.nund
+            walk(run, 0, s, np.float64(0.0), 0.015625 * T[s], tree)
+            t_off = t_off + T[s]
             ub_v, ub_a = np.fmax(ub_v, run.sub[run.iv]), np.fmax(ub_a, run.sub[run.ia])
-            seg[s, 0] = -1.0 if run.sviol else (1.0 if run.nund == nund0 else 0.0)
-            seg[s, 1] = run.nref - nref0
+            seg[s, 0] = -1.0 if run.sviol else (1.0 if tree.nund == nund0 else 0.0)
+            seg[s, 1] = tree.nref - nref0
             seg[s, 2:6], seg[s, 6:10] = run.slo, run.sub
-    bad = run.viol_t != np.inf
-    kin = np.array([-1.0 if bad else (1.0 if run.nund == 0 else 0.0), ub_v, run.lo_v, run.lo_v_t, ub_a, run.lo_a,
-                    run.lo_a_t, run.viol_t if bad else -1.0, run.nund, run.nref, t_off])
+    within, first = verdict(run.viol_t, tree.nund)
+    kin = np.array([within, ub_v, run.lo_v, run.lo_v_t, ub_a, run.lo_a, run.lo_a_t, first, tree.nund, tree.nref, t_off])
     return kin, seg, dict(leaves=run.leaves, open0=run.open0)
 
 

@@ -19,8 +19,15 @@ boxes of each kind of list fly through the map; the parent build gives the sampl
 (use_boxes, dt_sample = 0.01) and the static certificate, this build the static certificate and the moving one; the
 static certificate of the two builds is compared inside the parent's own spread.  It writes certify_moving_time.{md,json}.
 
+With --ab both builds run the same child, so that every launch of this build — the certificates included — stands beside
+the parent's from the same call, each inside or outside the parent's own spread: certify_ab.{md,json} (with --boxes:
+certify_moving_ab).  With --rows nothing is timed: one fresh child per library runs the three certificates (static,
+moving, kinematic) on the rows of the device tests — every kind of field, both kinds of box list, a list longer than a
+staging chunk, max_depth 0 .. 3, max_refine 0 / 1 / 256, limits on and off — and the two sets of output rows are
+compared bit for bit: certify_rows.json, exit status 1 unless every row is equal.
+
 usage: tools/certify_time.py [--parent-lib build_var/libgtop_parent.so] [--rounds 3] [--bench-rounds 2]
-                             [--out profiles/certify] [--boxes]"""
+                             [--out profiles/certify] [--boxes] [--ab | --rows]"""
 import argparse
 import json
 import os
@@ -149,6 +156,100 @@ def child(certify, boxes=False):
     print("CERTIFY_TIME_JSON " + json.dumps(out), flush=True)
 
 
+def child_rows(path):
+    """The output rows of the three certificates on the device tests' inputs (tests/*_twin.py), into an .npz."""
+    import itertools
+
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, ROOT)
+    import grad_traj_optimization_amd as gtop
+    from oracle import oracle
+    from tests import certify_moving_twin as cm
+    from tests import certify_twin as ct
+    from tests import kinematics_twin as kt
+
+    dev = lambda a: torch.tensor(np.ascontiguousarray(a), device="cuda:0")
+    host = lambda t: t.cpu().numpy()          # (waits for the launch: the context's setters below do not)
+    out = {}
+    sweep = list(itertools.product(range(4), (0, 1, 256)))
+    perm = np.random.default_rng(2).permutation(65) % 5
+    for kind, margin in zip(ct.FIELDS, (0.2, 0.2, 0.0, 0.3)):
+        field, mp = ct.make_field(oracle, kind)
+        ctx = gtop.GtopContext(0)
+        ctx.set_sdf(field.val, ct.GRID, mp.origin, ct.RES, mp.map_size)
+        c5, T5, _ = ct.make_rows(oracle, mp, 5, 3, 31)
+        batches = [(dev(c5[perm]), dev(T5[perm]), margin)]
+        for k, m, B, seed, mg, _, _ in ct.CASES.values():
+            if k == kind:
+                batches.append((*map(dev, ct.make_rows(oracle, mp, B, m, seed)[:2]), mg))
+        for i, (c, T, mg) in enumerate(batches):
+            for depth, refine in sweep:
+                out[f"static/{kind}/{i}/{depth}/{refine}"] = host(gtop.certify_device(ctx, c, T, gtop.GtopCertifyOpts(mg, depth, refine)))
+            if kind not in ("esdf", "signed"):
+                continue
+            ctx.set_start_times(np.linspace(0.0, 3.0, c.shape[0]))
+            for poly in (False, True):
+                few = cm.shared_boxes(mp, poly)
+                rng = np.random.default_rng(9)
+                shift = rng.uniform(-1.0, 1.0, (70, 3))
+                pick = np.arange(70) % 3
+                if poly:                                   # 70 boxes: past a staging chunk of either kind
+                    coef = few.coef[pick].copy()
+                    coef[:, :, 0] += shift
+                    many = cm.Boxes.polynomial(coef, few.scale[pick], few.t_range[pick])
+                else:
+                    many = cm.Boxes.const_vel(few.p0[pick] + shift, few.vel[pick], few.scale[pick])
+                for name, boxes, options in (("few", few, sweep), ("many", many, ((2, 16), (3, 1), (0, 0)))):
+                    boxes.set_on(ctx)
+                    for depth, refine in options:
+                        out[f"moving/{kind}/{i}/{poly}/{name}/{depth}/{refine}"] = host(gtop.certify_moving_device(
+                            ctx, c, T, gtop.GtopCertifyMovingOpts(mg, depth, refine)))
+            ctx.set_moving_boxes(np.zeros((0, 3)), np.zeros((0, 3)), np.zeros((0, 3)))
+            ctx.set_start_times(None)
+        ctx.close()
+    ctx = gtop.GtopContext(0)
+    ctx.set_sdf(np.full((24, 24, 24), 10.0), (24, 24, 24), (-6.0, -6.0, -6.0), 0.5)
+    for B, m, seed in kt.BATCHES:
+        coeff, T = kt.random_rows(B, m, seed)
+        mv, ma, _ = kt.batch_limits(coeff, T)
+        c, T = dev(coeff), dev(T)
+        small = B <= 3 and m <= 7
+        for (v, a), (depth, refine) in itertools.product(((0.0, 0.0), (mv, 0.0), (0.0, ma), (mv, ma)),
+                                                         sweep if small else ((2, 256), (3, 1), (0, 0))):
+            for per_axis in (False, True):
+                kin, seg = gtop.certify_kinematics_device(ctx, c, T, gtop.GtopKinOpts(v, a, per_axis, depth, refine))
+                key = f"kin/{B}/{m}/{v > 0}/{a > 0}/{per_axis}/{depth}/{refine}"
+                out[key], out[key + "/seg"] = host(kin), host(seg)
+    ctx.close()
+    np.savez_compressed(path, **out)
+    print("CERTIFY_ROWS_JSON " + json.dumps(dict(arrays=len(out), rows=int(sum(len(v.reshape(-1, v.shape[-1])) for v in out.values())))),
+          flush=True)
+
+
+def compare_rows(a):
+    """--rows: one child per library, the parent first; every output row of the two compared bit for bit."""
+    import numpy as np
+    os.makedirs(a.out, exist_ok=True)
+    files, counts = {}, {}
+    for who in ("parent", "this"):
+        files[who] = os.path.join(a.out, f"certify_rows_{who}.npz")
+        line = run_child(who, a.parent_lib, [os.path.abspath(__file__), "--child", "rows", "--dump", files[who]],
+                         "CERTIFY_ROWS_JSON ", 900)
+        counts[who] = json.loads(line.split(" ", 1)[1])
+        print(f"{who}: {counts[who]}", flush=True)
+    pa, th = np.load(files["parent"]), np.load(files["this"])
+    bits = lambda v: np.ascontiguousarray(v, dtype=np.float64).view(np.uint64)
+    differ = [k for k in pa.files if k not in th.files or pa[k].shape != th[k].shape or not np.array_equal(bits(pa[k]), bits(th[k]))]
+    differ += [k for k in th.files if k not in pa.files]
+    res = dict(counts, differing=differ, by_kind={p: sum(k.startswith(p) for k in pa.files) for p in ("static", "moving", "kin")})
+    with open(os.path.join(a.out, "certify_rows.json"), "w") as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps(res))
+    return 1 if differ else 0
+
+
 def run_child(who, parent_lib, args, prefix, timeout):
     env = dict(os.environ)
     if who == "parent":
@@ -168,17 +269,24 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "certify"))
     ap.add_argument("--bench-rounds", type=int, default=2, help="alternating bench.py runs per build (0 = none)")
-    ap.add_argument("--child", choices=("certify", "report"))
+    ap.add_argument("--child", choices=("certify", "report", "rows"))
+    ap.add_argument("--dump", help="(--child rows) the .npz to write")
     ap.add_argument("--boxes", action="store_true", help="the certificate against the moving boxes (see above)")
+    ap.add_argument("--ab", action="store_true", help="both builds run every launch (see above)")
+    ap.add_argument("--rows", action="store_true", help="compare the two builds' output rows bit for bit (see above)")
     a = ap.parse_args()
+    if a.child == "rows":
+        return child_rows(a.dump)
     if a.child:
         return child(a.child == "certify", a.boxes)
     if not os.path.exists(a.parent_lib):
         sys.exit(f"no parent build at {a.parent_lib}: make -C grad_traj_optimization_amd/csrc lib OUT=... on the parent commit")
+    if a.rows:
+        return compare_rows(a)
     runs = {"parent": [], "this": []}
     for _ in range(a.rounds):                                   # alternating, one fresh process each
         for who in ("parent", "this"):
-            line = run_child(who, a.parent_lib, [os.path.abspath(__file__), "--child", "report" if who == "parent" else "certify",
+            line = run_child(who, a.parent_lib, [os.path.abspath(__file__), "--child", "report" if who == "parent" and not a.ab else "certify",
                                                  *(["--boxes"] if a.boxes else [])], "CERTIFY_TIME_JSON ", 400)
             runs[who].append(json.loads(line.split(" ", 1)[1]))
             print(f"{who}: done", flush=True)
@@ -200,6 +308,8 @@ def main():
                       f"M evals/s: parent {fm(pv)}; this build {fm(tv)}; means {sum(tv) / len(tv) / (sum(pv) / len(pv)):.4f} of the "
                       f"parent's; the parent's own runs differ by {(max(pv) / min(pv) - 1) * 100:.2f} %, this build's by "
                       f"{(max(tv) / min(tv) - 1) * 100:.2f} %")
+    if a.ab:
+        return write_ab(a, runs, best, spread, bench, bench_line)
     if a.boxes:
         return write_moving(a, runs, best, spread, facts, bench, bench_line)
     lines = ["| B | (a) report, parent build, us | (b) report, this build, us | (b) / (a) | parent's spread of (a) | inside it "
@@ -230,6 +340,31 @@ def main():
             f.write("\nbench.py A/B in the same call: %s\n" % bench_line)
     print(table)
     print(json.dumps(facts))
+    if bench_line:
+        print(bench_line)
+
+
+def write_ab(a, runs, best, spread, bench, bench_line):
+    """certify[_moving]_ab.{md,json}: every launch, the parent build's least beside this build's, and the parent's spread."""
+    lines = ["| launch | parent build, us | this build, us | ratio | parent's spread | inside it |", "|---|---|---|---|---|---|"]
+    outside = []
+    for k, pa in best["parent"].items():
+        tb, sp = best["this"][k], spread[k]
+        if tb / pa - 1 > sp:
+            outside.append(k)
+        lines.append(f"| {k} | {pa:.1f} | {tb:.1f} | {tb / pa:.4f} | {sp * 100:.2f} % | {'NO' if k in outside else 'yes'} |")
+    table = "\n".join(lines)
+    name = os.path.join(a.out, "certify_moving_ab" if a.boxes else "certify_ab")
+    os.makedirs(a.out, exist_ok=True)
+    with open(name + ".json", "w") as f:
+        json.dump(dict(runs=runs, best_us=best, parent_spread=spread, outside_parent_spread=outside, rounds=a.rounds,
+                       bench_evals_per_s=bench, bench_line=bench_line), f, indent=1)
+    with open(name + ".md", "w") as f:
+        f.write("least of %d alternating rounds of one fresh process per library, the parent first; device-clock spans\n\n%s\n"
+                % (a.rounds, table))
+        if bench_line:
+            f.write("\nbench.py A/B in the same call: %s\n" % bench_line)
+    print(table)
     if bench_line:
         print(bench_line)
 
@@ -271,4 +406,4 @@ def write_moving(a, runs, best, spread, facts, bench, bench_line):
 
 
 if __name__ == "__main__":
-    main()
+    sys.exit(main())
