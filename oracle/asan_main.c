@@ -91,6 +91,27 @@ int main(void) {
     oracle_params p = {1.0, 5.0, 10.0, 0.5, 0.8, 0.0, 1.5, 2.5, 0.0, 1.5, 3.5, 2, 0};
     if (oracle_eval_batch(2, m, T2, m, Df2, &p, &S, x2, cost2, g2, 1, 1) < 0) rc = 1;
     if (oracle_eval_batch(2, m, T, 0, Df2, &p, &S, x2, cost2, g2, 1, 1) < 0) rc = 1;
+    {   /* gradient mode 1 and both kinds of box list, magnitudes and lowered counts, per-row and shared start times */
+      double bp0[6] = {path[0], path[1], path[2], path[3], path[4], path[5]}, bvel[6] = {0.3, -0.2, 0.0, -0.5, 0.1, 0.1};
+      double bscale[6] = {1.5, 1.7, 1.9, 1.1, 1.4, 1.6}, coef[36] = {0}, tr[4] = {0.2, 0.9, -1.0, 50.0}, t0[2] = {0.4, 1.7};
+      for (int b = 0; b < 2; ++b)
+        for (int a = 0; a < 3; ++a) {
+          coef[18 * b + 6 * a] = bp0[3 * b + a];
+          coef[18 * b + 6 * a + 1] = bvel[3 * b + a];
+          coef[18 * b + 6 * a + 5] = 1e-3;
+        }
+      double *mag2 = (double *)malloc(sizeof(double) * 2 * (2 * n + 6));
+      int low[2];
+      oracle_params pd = {1.0, 5.0, 10.0, 0.5, 0.8, 2.0, 1.5, 2.5, 1.5, 1.5, 3.5, 2, 1};
+      oracle_ext cv = {1, 2, 0, bp0, bvel, bscale, NULL, NULL}, po = {1, 2, 1, NULL, NULL, bscale, coef, tr};
+      oracle_ext po2 = {0, 2, 1, NULL, NULL, bscale, coef, NULL}, plain = {1, 0, 0, NULL, NULL, NULL, NULL, NULL};
+      if (oracle_eval_batch_ext(2, m, T2, m, Df2, &pd, &S, x2, &cv, t0, 1, cost2, g2, mag2, low, 1) < 0) rc = 1;
+      if (oracle_eval_batch_ext(2, m, T2, m, Df2, &pd, &S, x2, &po, t0, 0, cost2, g2, mag2, low, 1) < 0) rc = 1;
+      if (oracle_eval_batch_ext(2, m, T, 0, Df2, &p, &S, x2, &po2, NULL, 0, cost2, g2, NULL, NULL, 1) < 0) rc = 1;
+      if (oracle_eval_batch_ext(2, m, T2, m, Df2, &pd, &S, x2, &plain, NULL, 0, cost2, g2, mag2, NULL, 1) < 0) rc = 1;
+      if (!(oracle_cost_grad_ext(m, L, R, Df, T, &pd, &S, x, &cv, 0.3, g, NULL) >= 1e-3)) rc = 1;
+      free(mag2);
+    }
     free(path); free(T); free(L); free(R); free(Dp); free(x); free(g); free(coe); free(x2); free(g2); free(T2);
   }
   if (oracle_generator(1, (double[]){1.0}, NULL, NULL, NULL, NULL, NULL) == 0) rc = 1;   /* m = 1 must be rejected */

@@ -373,8 +373,8 @@ double oracle_sdf_query(const oracle_sdf *S, const double pos[3],
  * (|pos| + |idx_pos|) / res + 1, times the value's (gradient's) exact sensitivity to that weight.
  * margins: [0] distance of the cell coordinate (pos - res/2 - origin) / res to an integer (the floor of
  * sdf_map.cpp:201-204), [1] distance of pos to the in-map bounds (:55-69); both relative to their magnitudes. */
-static void sdf_query_mag(const oracle_sdf *S, const double pos[3], double *dmag, double gmag[3],
-                          double margins[2], double dgdp[3][3]) {
+static void sdf_query_mag_v(const oracle_sdf *S, const double pos[3], const double *vin, const double *vmin,
+                            double *dmag, double gmag[3], double margins[2], double dgdp[3][3]) {
   for (int k = 0; k < 3; ++k) dgdp[k][0] = dgdp[k][1] = dgdp[k][2] = 0;
   double mm = INFINITY;
   for (int i = 0; i < 3; ++i) {
@@ -402,8 +402,11 @@ static void sdf_query_mag(const oracle_sdf *S, const double pos[3], double *dmag
     wm[i] = (fabs(pos[i]) + fabs(ip)) * rinv + 1.0;
   }
   margins[0] = cm;
-  double v[8]; /* v[x*4 + y*2 + z] */
-  for (int c = 0; c < 8; c++) v[c] = sdf_get_distance(S, idx[0] + (c >> 2), idx[1] + ((c >> 1) & 1), idx[2] + (c & 1));
+  double v[8], vm[8]; /* v[x*4 + y*2 + z]; vm: the corner's own rounding-error magnitude (|v| for a stored value) */
+  for (int c = 0; c < 8; c++) {
+    v[c] = vin ? vin[c] : sdf_get_distance(S, idx[0] + (c >> 2), idx[1] + ((c >> 1) & 1), idx[2] + (c & 1));
+    vm[c] = vmin ? vmin[c] : fabs(v[c]);
+  }
   double w[3][2];
   for (int i = 0; i < 3; ++i) {
     w[i][0] = fabs(1 - diff[i]);
@@ -413,12 +416,12 @@ static void sdf_query_mag(const oracle_sdf *S, const double pos[3], double *dmag
   double val = 0, d[3] = {0, 0, 0}, ds[3] = {0, 0, 0}, dd[3][3] = {{0}};
   for (int c = 0; c < 8; c++) {
     const int b[3] = {c >> 2, (c >> 1) & 1, c & 1};
-    val += w[0][b[0]] * w[1][b[1]] * w[2][b[2]] * fabs(v[c]);
+    val += w[0][b[0]] * w[1][b[1]] * w[2][b[2]] * vm[c];
     for (int k = 0; k < 3; ++k) {
       if (b[k]) continue;
       const int o1 = (k + 1) % 3, o2 = (k + 2) % 3;
       const double wo = w[o1][b[o1]] * w[o2][b[o2]];
-      d[k] += wo * (fabs(v[c + bit[k]]) + fabs(v[c]));  /* the difference's magnitude */
+      d[k] += wo * (vm[c + bit[k]] + vm[c]);            /* the difference's magnitude */
       ds[k] += wo * fabs(v[c + bit[k]] - v[c]);         /* the value's sensitivity to weight k */
       for (int j = 0; j < 3; ++j) {                      /* the k-gradient's sensitivity to weight j */
         if (j == k || b[j]) continue;
@@ -530,6 +533,138 @@ double oracle_edt_query(const oracle_sdf *S, int nbox, const double *box_p0, con
           double d2 = edt_min_dist_to_boxes(nbox, box_p0, box_vel, box_scale, pt, time);
           values[x][y][z] = d1 < d2 ? d1 : d2; /* :98 */
         }
+      }
+
+  double v00 = (1 - diff[0]) * values[0][0][0] + diff[0] * values[1][0][0]; /* :104-112 */
+  double v01 = (1 - diff[0]) * values[0][0][1] + diff[0] * values[1][0][1];
+  double v10 = (1 - diff[0]) * values[0][1][0] + diff[0] * values[1][1][0];
+  double v11 = (1 - diff[0]) * values[0][1][1] + diff[0] * values[1][1][1];
+  double v0 = (1 - diff[1]) * v00 + diff[1] * v10;
+  double v1 = (1 - diff[1]) * v01 + diff[1] * v11;
+  double dist = (1 - diff[2]) * v0 + diff[2] * v1;
+
+  grad[2] = (v1 - v0) * rinv; /* :114-121 */
+  grad[1] = ((1 - diff[2]) * (v10 - v00) + diff[2] * (v11 - v01)) * rinv;
+  grad[0] = (1 - diff[2]) * (1 - diff[1]) * (values[1][0][0] - values[0][0][0]);
+  grad[0] += (1 - diff[2]) * diff[1] * (values[1][1][0] - values[0][1][0]);
+  grad[0] += diff[2] * (1 - diff[1]) * (values[1][0][1] - values[0][0][1]);
+  grad[0] += diff[2] * diff[1] * (values[1][1][1] - values[0][1][1]);
+  grad[0] *= rinv;
+  return dist;
+}
+
+/* Centre of box b on axis i at `tau` for either list kind (oracle_ext, gtop_oracle.h) and its rounding-error
+ * magnitude.  Constant velocity: p0 + vel*tau (obj_predictor.h:57-66), magnitude |p0| + |vel| |tau|.  Polynomial
+ * (include/gtop.h): tc = fmin(fmax(tau, t1), t2), then Horner in explicit fma; magnitude sum |c_j| |tc|^j.  The
+ * sample time itself differs between implementations (t += dt against 1e-3 + i dt: a few tens of u of t <= tau, and
+ * one rounding of the sum): its effect on the centre is the derivative's magnitude times |tau| — already in
+ * |vel| |tau| for a constant velocity, sum j |c_j| |tc|^(j-1) |tau| for a polynomial (kept when the clamp binds: the
+ * clamp is continuous, and a tau within rounding of t1 / t2 may clamp in one implementation and not in the other). */
+static double ext_box_centre(const oracle_ext *E, int b, int i, double tau, double *cmag) {
+  if (!E->poly) {
+    *cmag = fabs(E->p0[3 * b + i]) + fabs(E->vel[3 * b + i]) * fabs(tau);
+    return E->p0[3 * b + i] + E->vel[3 * b + i] * tau;
+  }
+  double tc = tau;
+  if (E->t_range) tc = fmin(fmax(tau, E->t_range[2 * b]), E->t_range[2 * b + 1]);
+  const double *c = E->coef + 18 * b + 6 * i;
+  double r = c[5];
+  for (int j = 4; j >= 0; --j) r = fma(r, tc, c[j]);
+  double hm = 0, dm = 0, pw = 1, pw1 = 0;
+  const double at = fabs(tc);
+  for (int j = 0; j < 6; ++j) {
+    hm += fabs(c[j]) * pw;
+    dm += j * fabs(c[j]) * pw1;
+    pw1 = pw;
+    pw *= at;
+  }
+  *cmag = hm + dm * fabs(tau);
+  return r;
+}
+
+/* distToBox (src/edt_environment.cpp:26-45) of one box at `pt` with its rounding-error magnitude.  Per axis the
+ * face coordinates c +- scale/2 and the point carry em_i = ptm_i + cmag_i + |scale_i|/2; the slab distance d_i is
+ * continuous in them (the inside test meets the face distance at 0), so it moves by at most em_i u — and not at all
+ * where the point is inside the slab by more than that.  ||d + e|| - ||d|| <= ||e||: the norm's error is
+ * sqrt(sum e_i^2), plus its own rounding, d. */
+static double ext_box_dist(const oracle_ext *E, int b, const double pt[3], const double ptm[3], double tau,
+                           double *mag2) {
+  double d2 = 0.0, e2 = 0.0;
+  for (int i = 0; i < 3; ++i) {
+    double cmag;
+    const double c = ext_box_centre(E, b, i, tau, &cmag);
+    const double h = 0.5 * E->scale[3 * b + i];
+    const double bmax = c + h, bmin = c - h; /* :31-32 */
+    const int inside = pt[i] >= bmin && pt[i] <= bmax;
+    const double di = inside ? 0.0 : fmin(fabs(pt[i] - bmin), fabs(pt[i] - bmax)); /* :36-40 */
+    const double em = ptm[i] + cmag + fabs(h);
+    const double depth = fmin(pt[i] - bmin, bmax - pt[i]);
+    const double ei = (!inside || depth < 0x1p-40 * em) ? em : 0.0;
+    d2 += di * di;
+    e2 += ei * ei;
+  }
+  const double d = sqrt(d2); /* dist.norm(), :42 */
+  *mag2 = d + sqrt(e2);
+  return d;
+}
+
+/* oracle_edt_query's arithmetic with the box list of an oracle_ext; also the 8 corner values v[x*4 + y*2 + z] and
+ * their magnitudes vm[] for sdf_query_mag_v, and *lowered = 1 if a box lowered any corner.  The min over boxes and
+ * with the static value is continuous, so a corner's magnitude is that of the value taken — and the larger of the
+ * two where they lie within 2^-40 of the box distance's magnitude of each other (either may win). */
+static double edt_query_ext(const oracle_sdf *S, const oracle_ext *E, const double pos[3], double time, double grad[3],
+                            double v[8], double vm[8], int *lowered) {
+  *lowered = 0;
+  if (!sdf_in_map(S, pos)) {
+    grad[0] = grad[1] = grad[2] = 0.0;
+    for (int c = 0; c < 8; ++c) v[c] = vm[c] = 0.0;
+    return -1;
+  }
+  double res = S->resolution, rinv = S->resolution_inv;
+  double pos_m[3], idx_pos[3], diff[3];
+  int idx[3];
+  for (int i = 0; i < 3; ++i) pos_m[i] = pos[i] - 0.5 * res * 1.0;
+  sdf_pos_to_index(S, pos_m, idx);
+  for (int i = 0; i < 3; ++i) idx_pos[i] = (idx[i] + 0.5) * res + S->origin[i];
+  for (int i = 0; i < 3; ++i) diff[i] = (pos[i] - idx_pos[i]) * rinv;
+
+  double values[2][2][2];
+  for (int x = 0; x < 2; x++)
+    for (int y = 0; y < 2; y++)
+      for (int z = 0; z < 2; z++) {
+        const int o[3] = {x, y, z};
+        double d1 = sdf_get_distance(S, idx[0] + x, idx[1] + y, idx[2] + z);
+        double val = d1, valm = fabs(d1);
+        if (!(time < 0.0)) { /* :91-94 */
+          double pt[3], ptm[3];
+          for (int i = 0; i < 3; ++i) {
+            pt[i] = (idx[i] + o[i] + 0.5) * res + S->origin[i];
+            ptm[i] = fabs(idx[i] + o[i] + 0.5) * res + fabs(S->origin[i]);
+          }
+          double dmin = 10000000.0, dmag = 10000000.0; /* :64 */
+          for (int b = 0; b < E->nbox; ++b) {
+            double m2;
+            const double di = ext_box_dist(E, b, pt, ptm, time, &m2);
+            if (di < dmin) dmin = di;
+          }
+          int first = 1;
+          for (int b = 0; b < E->nbox; ++b) { /* the magnitude: the largest among the boxes that can be the nearest */
+            double m2;
+            const double di = ext_box_dist(E, b, pt, ptm, time, &m2);
+            if (di <= dmin + 0x1p-40 * m2 && (first || m2 > dmag)) {
+              dmag = m2;
+              first = 0;
+            }
+          }
+          const double d2 = dmin;
+          val = d1 < d2 ? d1 : d2; /* :98 */
+          if (d2 < d1) *lowered = 1;
+          if (d2 < d1 - 0x1p-40 * dmag) valm = dmag;
+          else if (d2 < d1 + 0x1p-40 * dmag) valm = fmax(dmag, fabs(d1));
+        }
+        values[x][y][z] = val;
+        v[x * 4 + y * 2 + z] = val;
+        vm[x * 4 + y * 2 + z] = valm;
       }
 
   double v00 = (1 - diff[0]) * values[0][0][0] + diff[0] * values[1][0][0]; /* :104-112 */
@@ -711,7 +846,11 @@ void oracle_esdf_build_window(const oracle_sdf *S, const double *occupancy,
 static double cost_grad_impl(int m, const double *L, const double *R,
                              const double *Df, const double *T,
                              const oracle_params *prm, const oracle_sdf *S,
-                             const double *x, double *grad_out, double *mag) {
+                             const double *x, double *grad_out, double *mag,
+                             const oracle_ext *ext, double t0, int *nlowered) {
+  const int cons = ext && ext->mode == 1, boxes = ext && ext->nbox > 0;
+  int low_count = 0;
+  double seg_start = t0; /* tests/moving_twin.py sample_times: ((t0 + T[0]) + ...) + T[s-1], then + t */
   const int num_df = 6, num_dp = 3 * m - 3, nd = num_df + num_dp, n6 = 6 * m;
   double cost_smooth = 0, cost_colli = 0, cost_vel = 0, cost_acc = 0;
   double *g_smooth = dalloc((size_t)3 * num_dp);
@@ -813,8 +952,10 @@ static double cost_grad_impl(int m, const double *L, const double *R,
     double t = 1e-3, t_in = 0;
     for (; t < T[s]; t += dt) { /* :353 */
       t_in = t;
+      const double tau = seg_start + t;
       /* :451-468, :471-488 — note the float locals */
       double pos[3], vel[3], acc[3], pmag[3], vmag[3], amag[3], pflip[3] = {0, 0, 0}, vflip[3] = {0, 0, 0};
+      int vsign[3] = {0, 0, 0}, asign[3] = {0, 0, 0}; /* mode 1: sgn() of a value within FLIP_TAU of its magnitude from 0 */
       for (int a = 0; a < 3; ++a) {
         const double *q = c + 6 * a;
         double pd = q[0] + q[1] * t + q[2] * pow(t, 2) + q[3] * pow(t, 3) +
@@ -837,13 +978,21 @@ static double cost_grad_impl(int m, const double *L, const double *R,
           mg_float = fmin(mg_float, fmin(mp_, mv_));
           pflip[a] = mp_ < FLIP_TAU ? (double)nextafterf(p, INFINITY) - (double)p : 0;
           vflip[a] = mv_ < FLIP_TAU ? (double)nextafterf(fabsf(v), INFINITY) - (double)fabsf(v) : 0;
+          vsign[a] = vmag[a] > 0 && fabs(vd) < FLIP_TAU * vmag[a];
         }
       }
       double vel_norm =
           sqrt(vel[0] * vel[0] + vel[1] * vel[1] + vel[2] * vel[2]) + 1e-5;
 
       double dist, gd, cd, grad[3];
-      dist = oracle_sdf_query(S, pos, grad);                       /* :363 */
+      double v8[8], vm8[8];
+      if (boxes) {
+        int low;
+        dist = edt_query_ext(S, ext, pos, tau, grad, v8, vm8, &low);
+        low_count += low;
+      } else {
+        dist = oracle_sdf_query(S, pos, grad);                     /* :363 */
+      }
       cd = prm->alpha * exp(-(dist - prm->d0) / prm->r);           /* :509 */
       gd = -(prm->alpha / prm->r) * exp(-(dist - prm->d0) / prm->r); /* :514 */
 
@@ -860,14 +1009,16 @@ static double cost_grad_impl(int m, const double *L, const double *R,
       double w1m[3] = {0, 0, 0}, w2m[3] = {0, 0, 0};
       if (mag) {
         double dm, gm[3], mgs[2], dgdp[3][3];
-        sdf_query_mag(S, pos, &dm, gm, mgs, dgdp);
+        sdf_query_mag_v(S, pos, boxes ? v8 : NULL, boxes ? vm8 : NULL, &dm, gm, mgs, dgdp);
         mg_cell = fmin(mg_cell, mgs[0]);
         mg_map = fmin(mg_map, mgs[1]);
         /* the exp argument's absolute error, in units of u: (|dist| + |d0|) / r */
         const double ec = 1 + (dm + fabs(prm->d0)) / fabs(prm->r);
         cm_c += fabs(cd) * ec * vel_norm * dt;
         for (int k = 0; k < 3; ++k) {
-          w1m[k] = fabs(gd * cd * vel_norm) * (gm[k] + 2 * fabs(grad[k]) * ec);
+          /* mode 1: one exponential in the weight, not two */
+          w1m[k] = cons ? fabs(gd * vel_norm) * (gm[k] + fabs(grad[k]) * ec)
+                        : fabs(gd * cd * vel_norm) * (gm[k] + 2 * fabs(grad[k]) * ec);
           w2m[k] = fabs(cd) * ec * vmag[k] / vel_norm;   /* the velocity by its magnitude */
         }
         /* a coordinate whose float rounding can go either way (pre-rounding double within FLIP_TAU of its
@@ -878,7 +1029,8 @@ static double cost_grad_impl(int m, const double *L, const double *R,
             const double dd = fabs(grad[j]) * pflip[j], rel = dd / fabs(prm->r);
             fc += fabs(cd) * rel * vel_norm;
             for (int k = 0; k < 3; ++k) {
-              f1[k] += fabs(gd * cd * vel_norm) * (2 * fabs(grad[k]) * rel + dgdp[k][j] * pflip[j]);
+              f1[k] += cons ? fabs(gd * vel_norm) * (fabs(grad[k]) * rel + dgdp[k][j] * pflip[j])
+                            : fabs(gd * cd * vel_norm) * (2 * fabs(grad[k]) * rel + dgdp[k][j] * pflip[j]);
               f2[k] += fabs(cd) * rel * fabs(vel[k]) / vel_norm;
             }
           }
@@ -886,7 +1038,7 @@ static double cost_grad_impl(int m, const double *L, const double *R,
             const double dvn = fabs(vel[j]) * vflip[j] / vel_norm;
             fc += fabs(cd) * dvn;
             for (int k = 0; k < 3; ++k) {
-              f1[k] += fabs(gd * grad[k] * cd) * dvn;
+              f1[k] += (cons ? fabs(gd * grad[k]) : fabs(gd * grad[k] * cd)) * dvn;
               f2[k] += fabs(cd) * (fabs(vel[k]) * dvn / vel_norm + (k == j ? vflip[j] / vel_norm : 0));
             }
           }
@@ -903,7 +1055,7 @@ static double cost_grad_impl(int m, const double *L, const double *R,
       }
 
       for (int k = 0; k < 3; k++) { /* :376-381 */
-        double s1 = gd * grad[k] * cd * vel_norm;
+        double s1 = cons ? gd * grad[k] * vel_norm : gd * grad[k] * cd * vel_norm;
         double s2 = cd * (vel[k] / vel_norm);
         for (int cc = 0; cc < num_dp; ++cc) {
           double a1 = 0, a2 = 0;
@@ -936,6 +1088,7 @@ static double cost_grad_impl(int m, const double *L, const double *R,
             const double ma_ = float_margin(ad, amag[a], 1);
             mg_float = fmin(mg_float, ma_);
             aflip[a] = ma_ < FLIP_TAU ? (double)nextafterf(fabsf(ac), INFINITY) - (double)fabsf(ac) : 0;
+            asign[a] = amag[a] > 0 && fabs(ad) < FLIP_TAU * amag[a];
           }
         }
         double ev[3], ea[3];
@@ -954,12 +1107,17 @@ static double cost_grad_impl(int m, const double *L, const double *R,
             dvr += fabs(vel[k]) * vflip[k] / (vel_norm * vel_norm);
           }
         }
+        double cvs[3], cas[3], Ssum = 0, Smag = 0, Sflip = 0; /* mode 1: every axis's penalty, their sum */
         for (int k = 0; k < 3; k++) {
           cv = prm->alpha_v * exp((fabs(vel[k]) - prm->v0) / prm->r_v); /* :519 */
           cost_vel += cv * vel_norm * dt;
           ca = prm->alpha_a * exp((fabs(acc[k]) - prm->a0) / prm->r_a); /* :529 */
           cost_acc += ca * vel_norm * dt;
+          cvs[k] = cv;
+          cas[k] = ca;
           if (mag) {
+            Smag += fabs(cv) * ev[k] + fabs(ca) * ea[k];
+            Sflip += fabs(cv) * fv[k] + fabs(ca) * fa[k];
             cm_v += fabs(cv) * ev[k] * vel_norm * dt;
             cm_a += fabs(ca) * ea[k] * vel_norm * dt;
             fl_cd += 2 * (fabs(cv) * (fv[k] + dvr) + fabs(ca) * (fa[k] + dvr)) * vel_norm * dt;
@@ -972,6 +1130,14 @@ static double cost_grad_impl(int m, const double *L, const double *R,
                exp((fabs(acc[k]) - prm->a0) / prm->r_a); /* :534 */
           double s1 = gv * vel_norm, s2 = cv * (vel[k] / vel_norm);
           double s3 = ga * vel_norm, s4 = ca * (vel[k] / vel_norm);
+          if (cons) { /* tests/consistent_twin.py: gv sgn(v_k) vn + S v_k / vn on T*V, ga sgn(a_k) vn on T*V*V */
+            const double sv = (double)((vel[k] > 0) - (vel[k] < 0)), sa = (double)((acc[k] > 0) - (acc[k] < 0));
+            Ssum = (cvs[0] + cvs[1] + cvs[2]) + (cas[0] + cas[1] + cas[2]);
+            s1 = gv * sv * vel_norm;
+            s2 = Ssum * (vel[k] / vel_norm);
+            s3 = ga * sa * vel_norm;
+            s4 = 0.0;
+          }
           for (int cc = 0; cc < num_dp; ++cc) {
             double a1 = 0, a2 = 0, a3 = 0, a4 = 0;
             for (int i = 0; i < 6; ++i) {
@@ -987,6 +1153,10 @@ static double cost_grad_impl(int m, const double *L, const double *R,
               /* cv / ca: the last axis's values (the reference's loop variables) */
               double m1 = fabs(s1) * ev[k], m3 = fabs(s3) * ea[k];
               double m2 = fabs(cv) * ev[2] * vmag[k] / vel_norm, m4 = fabs(ca) * ea[2] * vmag[k] / vel_norm;
+              if (cons) { /* S by the magnitudes of its six terms; an axis at exactly 0 (sgn = 0, vmag = 0) gets none */
+                m2 = Smag * vmag[k] / vel_norm;
+                m4 = 0.0;
+              }
               double b1 = 0, b2 = 0;
               for (int i = 0; i < 6; ++i) {
                 double l = fabs(Ldp[i * num_dp + cc]);
@@ -995,10 +1165,20 @@ static double cost_grad_impl(int m, const double *L, const double *R,
               }
               gm_v[k * num_dp + cc] += b1 * dt;
               gm_a[k * num_dp + cc] += b2 * dt;
-              if (dvr > 0 || fv[k] > 0 || fa[k] > 0 || fv[2] > 0 || fa[2] > 0 || vflip[k] > 0) {
-                const double e1 = fabs(s1) * (fv[k] + dvr), e3 = fabs(s3) * (fa[k] + dvr);
-                const double e2 = fabs(cv) * (fabs(vel[k]) * (fv[2] + 2 * dvr) + vflip[k]) / vel_norm;
-                const double e4 = fabs(ca) * (fabs(vel[k]) * (fa[2] + 2 * dvr) + vflip[k]) / vel_norm;
+              if (dvr > 0 || fv[k] > 0 || fa[k] > 0 || fv[2] > 0 || fa[2] > 0 || vflip[k] > 0 ||
+                  (cons && (Sflip > 0 || vsign[k] || asign[k]))) {
+                double e1 = fabs(s1) * (fv[k] + dvr), e3 = fabs(s3) * (fa[k] + dvr);
+                double e2 = fabs(cv) * (fabs(vel[k]) * (fv[2] + 2 * dvr) + vflip[k]) / vel_norm;
+                double e4 = fabs(ca) * (fabs(vel[k]) * (fa[2] + 2 * dvr) + vflip[k]) / vel_norm;
+                if (cons) {
+                  /* S moves with every axis's float step; the sign allowance: a velocity / acceleration whose
+                   * pre-rounding double is within FLIP_TAU of its magnitude from zero may take another sgn in a correct
+                   * implementation — its gv*vn / ga*vn term (doubled below with the rest) */
+                  e2 = (fabs(Ssum) * (fabs(vel[k]) * 2 * dvr + vflip[k]) + fabs(vel[k]) * Sflip) / vel_norm;
+                  e4 = 0.0;
+                  if (vsign[k]) e1 += fabs(gv * vel_norm);
+                  if (asign[k]) e3 += fabs(ga * vel_norm);
+                }
                 double b3 = 0;
                 for (int i = 0; i < 6; ++i)
                   b3 += ((e1 + e2 + e4) * TV[i] + e3 * TVV[i]) * fabs(Ldp[i * num_dp + cc]);
@@ -1014,7 +1194,9 @@ static double cost_grad_impl(int m, const double *L, const double *R,
       if (t_in > 0) mg_count = fmin(mg_count, fabs(T[s] - t_in) / T[s]);
       mg_count = fmin(mg_count, fabs(t - T[s]) / T[s]);
     }
+    seg_start = seg_start + T[s];
   }
+  if (nlowered) *nlowered = low_count;
 
   /* :412-418 */
   double ws = prm->ws, wc = prm->wc, wv = 1.0, wa = 1.0;
@@ -1068,14 +1250,20 @@ double oracle_cost_grad(int m, const double *L, const double *R,
                         const double *Df, const double *T,
                         const oracle_params *prm, const oracle_sdf *S,
                         const double *x, double *grad_out) {
-  return cost_grad_impl(m, L, R, Df, T, prm, S, x, grad_out, NULL);
+  return cost_grad_impl(m, L, R, Df, T, prm, S, x, grad_out, NULL, NULL, 0.0, NULL);
 }
 
 double oracle_cost_grad_mag(int m, const double *L, const double *R,
                             const double *Df, const double *T,
                             const oracle_params *prm, const oracle_sdf *S,
                             const double *x, double *grad_out, double *mag) {
-  return cost_grad_impl(m, L, R, Df, T, prm, S, x, grad_out, mag);
+  return cost_grad_impl(m, L, R, Df, T, prm, S, x, grad_out, mag, NULL, 0.0, NULL);
+}
+
+double oracle_cost_grad_ext(int m, const double *L, const double *R, const double *Df, const double *T,
+                            const oracle_params *prm, const oracle_sdf *S, const double *x, const oracle_ext *ext,
+                            double t0, double *grad_out, double *mag) {
+  return cost_grad_impl(m, L, R, Df, T, prm, S, x, grad_out, mag, ext, t0, NULL);
 }
 
 static double now_s(void) {
@@ -1093,7 +1281,8 @@ static double now_s(void) {
 static double eval_batch_impl(int B, int m, const double *T, int t_stride,
                               const double *Df, const oracle_params *prm,
                               const oracle_sdf *S, const double *x, double *cost,
-                              double *grad, double *mag, int reps, int nthreads) {
+                              double *grad, double *mag, int reps, int nthreads, const oracle_ext *ext,
+                              const double *t0, int t0_stride, int *lowered) {
   int nd = 3 * m + 3, n6 = 6 * m, n = 9 * (m - 1);
   size_t lsz = (size_t)n6 * nd, rsz = (size_t)nd * nd;
   int nprob = t_stride ? B : 1;
@@ -1109,7 +1298,7 @@ static double eval_batch_impl(int B, int m, const double *T, int t_stride,
     return -1.0;
   }
   if (nthreads < 1) nthreads = 1;
-  double t0 = now_s();
+  double clk0 = now_s();
   for (int rep = 0; rep < reps; ++rep) {
 #ifdef _OPENMP
 #pragma omp parallel for num_threads(nthreads) schedule(static)
@@ -1119,27 +1308,34 @@ static double eval_batch_impl(int B, int m, const double *T, int t_stride,
       cost[b] = cost_grad_impl(m, Ls + lsz * p, Rs + rsz * p,
                                Df + (size_t)b * 18, T + (size_t)b * t_stride,
                                prm, S, x + (size_t)b * n, grad + (size_t)b * n,
-                               mag ? mag + (size_t)b * (2 * n + 6) : NULL);
+                               mag ? mag + (size_t)b * (2 * n + 6) : NULL, ext,
+                               t0 ? t0[(size_t)b * t0_stride] : 0.0, lowered ? lowered + b : NULL);
     }
   }
   double t1 = now_s();
   free(Ls);
   free(Rs);
-  return t1 - t0;
+  return t1 - clk0;
 }
 
 double oracle_eval_batch(int B, int m, const double *T, int t_stride,
                          const double *Df, const oracle_params *prm,
                          const oracle_sdf *S, const double *x, double *cost,
                          double *grad, int reps, int nthreads) {
-  return eval_batch_impl(B, m, T, t_stride, Df, prm, S, x, cost, grad, NULL, reps, nthreads);
+  return eval_batch_impl(B, m, T, t_stride, Df, prm, S, x, cost, grad, NULL, reps, nthreads, NULL, NULL, 0, NULL);
 }
 
 double oracle_eval_batch_mag(int B, int m, const double *T, int t_stride,
                              const double *Df, const oracle_params *prm,
                              const oracle_sdf *S, const double *x, double *cost,
                              double *grad, double *mag, int nthreads) {
-  return eval_batch_impl(B, m, T, t_stride, Df, prm, S, x, cost, grad, mag, 1, nthreads);
+  return eval_batch_impl(B, m, T, t_stride, Df, prm, S, x, cost, grad, mag, 1, nthreads, NULL, NULL, 0, NULL);
+}
+
+double oracle_eval_batch_ext(int B, int m, const double *T, int t_stride, const double *Df, const oracle_params *prm,
+                             const oracle_sdf *S, const double *x, const oracle_ext *ext, const double *t0,
+                             int t0_stride, double *cost, double *grad, double *mag, int *lowered, int nthreads) {
+  return eval_batch_impl(B, m, T, t_stride, Df, prm, S, x, cost, grad, mag, 1, nthreads, ext, t0, t0_stride, lowered);
 }
 
 /* ------------------------------------------------------------------ */

@@ -96,6 +96,37 @@ double oracle_eval_batch_mag(int B, int m, const double *T, int t_stride,
                              const oracle_sdf *S, const double *x, double *cost,
                              double *grad, double *mag, int nthreads);
 
+/* The callback with the two later semantics of include/gtop.h, everything else as oracle_cost_grad_mag.
+ *   mode    0: the reference's gradient.  1 (gtop_set_gradient_mode, GTOP_GRADIENT_CONSISTENT, tests/consistent_twin.py):
+ *           the collision weight gd*grad(k)*vn without cd; in the enable_dyn block S = sum_j (cv_j + ca_j) on the
+ *           v/|v| term, sgn(vel_k) / sgn(acc_k) on the penalties' own derivatives, sgn(+-0) = 0.  The cost statements
+ *           are the same in both modes.
+ *   boxes   nbox > 0 (gtop_set_moving_cost): every collision sample's lookup is oracle_edt_query's arithmetic at
+ *           tau = ((t0 + T[0]) + ... + T[s-1]) + t (tests/moving_twin.py).  poly == 0: p0, vel, scale (nbox x 3 each).
+ *           poly != 0 (gtop_set_moving_box_polynomials): coef nbox x 3 x 6 (ascending powers), scale, t_range nbox x 2
+ *           or NULL; the centre is the time clamped into [t1, t2], then Horner in explicit fma.
+ * The magnitudes (same layout as oracle_cost_grad_mag's mag[]) carry, for a corner lowered by a box, the rounding of
+ * the box centre (|p0| + |vel| |tau|, or the Horner magnitude sum |c_j| |tc|^j plus the derivative magnitude
+ * sum j |c_j| |tc|^(j-1) times |tau| for the sample time's own error), of the half extent and of the corner centre;
+ * in mode 1 Gflip also holds, twice, the gv*vn / ga*vn term of every sample whose pre-rounding velocity /
+ * acceleration lies within 2^-44 of its magnitude from zero (its sgn may differ in a correct implementation). */
+typedef struct {
+  int mode;
+  int nbox, poly;
+  const double *p0, *vel, *scale; /* poly == 0: p0, vel; both: scale */
+  const double *coef, *t_range;   /* poly != 0 */
+} oracle_ext;
+
+/* mag may be NULL (no magnitudes); ext may be NULL (mode 0, no boxes). */
+double oracle_cost_grad_ext(int m, const double *L, const double *R, const double *Df, const double *T,
+                            const oracle_params *prm, const oracle_sdf *S, const double *x, const oracle_ext *ext,
+                            double t0, double *grad_out, double *mag);
+/* the batch driver: t0 NULL (all zero), t0_stride 0 (one shared value) or 1; lowered (B, or NULL): the number of
+ * collision samples of each row with at least one corner value lowered by a box. */
+double oracle_eval_batch_ext(int B, int m, const double *T, int t_stride, const double *Df, const oracle_params *prm,
+                             const oracle_sdf *S, const double *x, const oracle_ext *ext, const double *t0,
+                             int t0_stride, double *cost, double *grad, double *mag, int *lowered, int nthreads);
+
 void oracle_traj_stats(int m, const double *coeff, const double *T, double dt_sample, double *out);
 /* PolynomialTraj::getTraj (polynomial_traj.hpp:69-78): returns the number of points, stores the first max_samples */
 int oracle_traj_samples(int m, const double *coeff, const double *T, double dt_sample, int max_samples,

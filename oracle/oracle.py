@@ -35,6 +35,15 @@ class OracleSdf(C.Structure):
     ]
 
 
+class OracleExt(C.Structure):
+    """oracle_ext (gtop_oracle.h): gradient mode and an optional moving-box list."""
+    _fields_ = [
+        ("mode", C.c_int), ("nbox", C.c_int), ("poly", C.c_int),
+        ("p0", C.POINTER(C.c_double)), ("vel", C.POINTER(C.c_double)), ("scale", C.POINTER(C.c_double)),
+        ("coef", C.POINTER(C.c_double)), ("t_range", C.POINTER(C.c_double)),
+    ]
+
+
 def build(force=False):
     """Compile the restatement with gcc (no-op if up to date)."""
     src = os.path.join(_HERE, "gtop_oracle.c")
@@ -94,6 +103,10 @@ def lib():
         L.oracle_eval_batch_mag.argtypes = [C.c_int, C.c_int, dp, C.c_int, dp, C.POINTER(OracleParams),
                                             C.POINTER(OracleSdf), dp, dp, dp, dp, C.c_int]
         L.oracle_eval_batch_mag.restype = C.c_double
+        L.oracle_eval_batch_ext.argtypes = [C.c_int, C.c_int, dp, C.c_int, dp, C.POINTER(OracleParams),
+                                            C.POINTER(OracleSdf), dp, C.POINTER(OracleExt), dp, C.c_int, dp, dp, dp, ip,
+                                            C.c_int]
+        L.oracle_eval_batch_ext.restype = C.c_double
         L.oracle_traj_stats.argtypes = [C.c_int, dp, dp, C.c_double, dp]
         L.oracle_traj_stats.restype = None
         L.oracle_traj_samples.argtypes = [C.c_int, dp, dp, C.c_double, C.c_int, dp]
@@ -302,6 +315,60 @@ def eval_batch_mag(T, Df, x, sdf, params, nthreads=1):
         raise ValueError("oracle_eval_batch_mag failed")
     return (cost, grad, mag[:, 0].copy(), mag[:, 1:n + 1].copy(), mag[:, n + 1:n + 5].copy(), mag[:, n + 5].copy(),
             mag[:, n + 6:].copy())
+
+
+def eval_batch_ext(T, Df, x, sdf, params, mode=0, boxes=None, t0=None, nthreads=1):
+    """eval_batch_mag with a gradient mode and a time-aware lookup (oracle_eval_batch_ext, gtop_oracle.h).
+    mode: 0 the reference's gradient, 1 the consistent one (tests/consistent_twin.py).  boxes: None, a
+    constant-velocity list dict(p0, vel, scale) ((nbox, 3) each, tests/moving_twin.py) or a polynomial list
+    dict(coef (nbox, 3, 6), scale, t_range (nbox, 2) or None) (tests/box_poly_twin.py).  t0: None (0), a scalar shared by
+    the rows, or (B,).  Returns eval_batch_mag's seven arrays and `lowered` (B,): each row's number of collision
+    samples with a corner value lowered by a box."""
+    x = _f64(x)
+    B, n = x.shape
+    m = n // 9 + 1
+    T = _f64(T)
+    stride = m if T.ndim == 2 else 0
+    Df = _f64(Df).reshape(B, 18)
+    ext = OracleExt(mode=int(mode))
+    keep = []
+    if boxes is not None:
+        scale = _f64(boxes["scale"]).reshape(-1, 3)
+        ext.nbox = scale.shape[0]
+        ext.scale = _p(scale)
+        keep.append(scale)
+        if "coef" in boxes:
+            coef = _f64(boxes["coef"]).reshape(-1, 18)
+            assert coef.shape[0] == ext.nbox
+            ext.poly, ext.coef = 1, _p(coef)
+            keep.append(coef)
+            if boxes.get("t_range") is not None:
+                tr = _f64(boxes["t_range"]).reshape(-1, 2)
+                assert tr.shape[0] == ext.nbox
+                ext.t_range = _p(tr)
+                keep.append(tr)
+        else:
+            p0, vel = _f64(boxes["p0"]).reshape(-1, 3), _f64(boxes["vel"]).reshape(-1, 3)
+            assert p0.shape[0] == vel.shape[0] == ext.nbox
+            ext.p0, ext.vel = _p(p0), _p(vel)
+            keep += [p0, vel]
+    t0a, t0_stride = None, 0
+    if t0 is not None:
+        t0a = _f64(t0).reshape(-1)
+        assert t0a.size in (1, B)
+        t0_stride = 1 if t0a.size == B and B > 1 else 0
+    cost = np.zeros(B)
+    grad = np.zeros((B, n))
+    mag = np.zeros((B, 2 * n + 6))
+    lowered = np.zeros(B, dtype=np.int32)
+    sec = lib().oracle_eval_batch_ext(B, m, _p(T), stride, _p(Df), C.byref(params), C.byref(sdf.c), _p(x), C.byref(ext),
+                                      _p(t0a) if t0a is not None else None, t0_stride, _p(cost), _p(grad), _p(mag),
+                                      lowered.ctypes.data_as(C.POINTER(C.c_int)), nthreads)
+    del keep
+    if sec < 0:
+        raise ValueError("oracle_eval_batch_ext failed")
+    return (cost, grad, mag[:, 0].copy(), mag[:, 1:n + 1].copy(), mag[:, n + 1:n + 5].copy(), mag[:, n + 5].copy(),
+            mag[:, n + 6:].copy(), lowered)
 
 
 def cost_grad_mag(T, Df, x, sdf, params):

@@ -51,7 +51,37 @@ Where the oracle's value overflows, the kernel's must too.  Each failure names t
 cost (optimize_batch_ex with max_evals = 1, at clip(x0, lb, ub)); their gradients are covered only through the
 optimizer roads (test_optimizer.py / test_gpu_fuzz.py), not entrywise here.
 
-GTOP_ENTRYWISE_LOG=<file> appends one JSON line per check (body, precision, rows, ties, largest ratios)."""
+The later bodies (second half of the file) against oracle.eval_batch_ext — the oracle with a gradient mode and a
+time-aware lookup, its magnitudes held against 40-digit arithmetic by tests/test_entrywise_bound.py: the consistent
+gradient in every geometry (ordinary, DYN, DYN with steep scale lengths; both precisions; the cost bit-equal to mode
+0's), the moving-obstacle bodies in each of their geometries (ten lanes, five lanes with one or two trajectories per
+wavefront, chunked; with and without DYN; gradient modes 0 and 1; constant-velocity lists of 1 and 32 boxes, polynomial
+lists of 8 — degree five, two validity intervals ending inside the trajectories — and 32; per-row and shared start
+times), the optimizer loop's moving bodies on their first evaluation, the edge batch and the signed field in the new
+modes, and the 64-bit-index forms (DYN, five lanes with one trajectory per wavefront, two wavefronts per trajectory,
+chunked, consistent at both pins, moving, optimizer loop).  The parametrisation ids name the body.  Every check first
+asserts, from the oracle alone, that at most ALLOWANCE_CAP of its (row, entry) pairs rest on a flip or sign allowance
+larger than KAPPA * u * magnitude (largest share on the committed seeds: 2.7 %, the 8-row wide moving case; 2.0 %
+otherwise), and every moving case that at least half of its rows (an eighth with a single box) have a box-lowered
+corner and a cost more than 1e-6 relative off the static one.  In fp32 the steep DYN block overflows past fp32's range
+on most rows of the long-13 / long-40 / long-227 / spl30 batches (36, 5, 1 and 66 rows): those rows are held to
+"overflows where the oracle does", as check() holds every such row.
+Largest |err| / (u * mag), cost / gradient (committed seeds, MI355X; KAPPA 4096 fp64, 1024 fp32): consistent fp64
+0.35 / 1.4, consistent fp32 0.67 / 0.043, moving constant-velocity 0.039 / 0.89, moving polynomial 0.037 / 0.89, moving
+plus consistent 0.039 / 0.89, wide 0.0024 / 0.11.  No tie rows in 26 267.
+Single-line kernel mutations, built apart and run against these tests (long-227 left out): mode 1's weight wds[] taken
+from aw[] fails 57 of the 94 tests — 24 of the 27 fp64 and 4 fp32 checks of test_consistent_every_body (the packed fp32
+bodies do not read it), all 24 of test_moving_every_body, both wide mode-1 cases, the edge batch and the signed field;
+csum_dyn without one axis's ca fails 45 — 21 DYN checks of test_consistent_every_body (3 of them fp32) and all 24 of
+test_moving_every_body (tests/test_gpu_consistent_gradient.py's four steep cases see it too); a box half extent off by
+2^-36 fails NONE of the 94 — the 1e-12 normwise check of
+tests/test_gpu_moving_cost.py sees it on one of three cases tried (m = 2, one box: 1.4e-12 / 1.5e-11; not m = 6 or 13
+with 8 boxes).  tests/test_entrywise_bound.py says why: with Cmag >= 2.6 cost and Gmag_k some 1e4 |g_k| the bound
+resolves about 1e-8 of an entry, far finer than the 1e-5 the mode-1 bodies were held to, coarser than the 1e-12 the
+moving bodies already are; for those it adds the bodies no 1e-12 test launches, not resolution.
+
+GTOP_ENTRYWISE_LOG=<file> appends one JSON line per check (body, precision, rows, ties, largest ratios), and one per
+family of the later bodies at the end of the module."""
 import json
 import math
 import os
@@ -202,28 +232,34 @@ def test_host_entry_points(scene, oracle_mod, geo):
         ctx.set_launch_geometry(0, 0)
 
 
-def test_wide_index_bodies(gtop, oracle_mod):
-    """The 64-bit-index bodies: the 4097 x 4097 x 6 field of test_gpu_parity.test_parity_wide_index_field."""
+@pytest.fixture(scope="module")
+def wide(gtop, oracle_mod):
+    """The 4097 x 4097 x 6 field of test_gpu_parity.test_parity_wide_index_field (past 2^31 bytes: every body on it is
+    a 64-bit-index one), generated and uploaded once: (map extents, context, oracle Sdf)."""
     grid, res = (4097, 4097, 6), 0.2
     origin = np.array([-grid[0] * res / 2, -grid[1] * res / 2, 0.0])
     dist = np.random.default_rng(5).uniform(0.0, 2.0, size=grid[0] * grid[1] * grid[2])
     ms = types.SimpleNamespace(origin=origin, map_size=np.array(grid) * res)
-    b = problem.make_trajectories(96, 6, ms, seed=77, margin=0.15, step_len=(0.5, 1.5))
     ctx = gtop.GtopContext(device=0)
-    try:
-        ctx.set_sdf(dist, grid, origin, res)
-        sdf = oracle_mod.Sdf(origin, res, grid, dist)
-        ref = _ref(oracle_mod, b, sdf, {})
-        for spl in (3, 6, 10, 30):
-            c, g = _device(ctx, b, "f64", 0, spl, {})
-            check(c, g, ref, "f64", ("wide", spl))
-        b32 = _f32_batch(b)
-        ref32 = _ref(oracle_mod, b32, sdf, {})
-        for spl in (3, 6):
-            c, g = _device(ctx, b32, "f32", 0, spl, {})
-            check(c, g, ref32, "f32", ("wide", spl))
-    finally:
-        ctx.close()
+    ctx.set_sdf(dist, grid, origin, res)
+    sdf = oracle_mod.Sdf(origin, res, grid, dist)
+    yield ms, ctx, sdf
+    ctx.close()
+
+
+def test_wide_index_bodies(wide, oracle_mod):
+    """The 64-bit-index bodies at six segments, every samples-per-lane pin, both precisions."""
+    ms, ctx, sdf = wide
+    b = problem.make_trajectories(96, 6, ms, seed=77, margin=0.15, step_len=(0.5, 1.5))
+    ref = _ref(oracle_mod, b, sdf, {})
+    for spl in (3, 6, 10, 30):
+        c, g = _device(ctx, b, "f64", 0, spl, {})
+        check(c, g, ref, "f64", ("wide", spl))
+    b32 = _f32_batch(b)
+    ref32 = _ref(oracle_mod, b32, sdf, {})
+    for spl in (3, 6):
+        c, g = _device(ctx, b32, "f32", 0, spl, {})
+        check(c, g, ref32, "f32", ("wide", spl))
 
 
 @pytest.mark.parametrize("seed", test_gpu_fuzz.seeds(0, 40))
@@ -386,3 +422,344 @@ def test_fused_optimizer_first_evaluation(scene, oracle_mod, m, B):
     ref = oracle_mod.eval_batch_mag(b.T, b.Df, xc, sdf, oracle_mod.make_params(), nthreads=8)
     # (the gradient is not returned: the check is on the cost; the gradient columns are the oracle's own)
     check(cost, ref[1], ref, "f64", ("optimizer loop, first evaluation", m, B))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The bodies added since: the consistent gradient (GtopConsistent<MM>, gtop_set_gradient_mode), the moving-obstacle
+# lookup (GtopMoving<MM> / GtopMovingPoly<MM>, gtop_set_moving_cost) and the 64-bit-index forms of each — against
+# oracle.eval_batch_ext, whose magnitudes tests/test_entrywise_bound.py holds against 40-digit arithmetic.
+# ---------------------------------------------------------------------------------------------------------------------
+ALLOWANCE_CAP = 0.05       # at most this share of a check's (row, entry) pairs may rest on their flip / sign allowance
+STEEP = dict(enable_dyn=1, alpha_v=2.0, r_v=0.5, v0=2.5, alpha_a=1.5, r_a=1.0, a0=3.5)   # test_gpu_consistent_gradient.py's
+FAMILY = {}                # family -> [largest cost ratio, largest gradient ratio] of this run (logged at module teardown)
+
+
+def ref_ext(oracle_mod, b, sdf, kw, mode=0, boxes=None, t0=None):
+    """oracle.eval_batch_ext's seven arrays (what check() takes) and the rows' lowered-sample counts."""
+    *ref, lowered = oracle_mod.eval_batch_ext(b.T, b.Df, b.x, sdf, oracle_mod.make_params(**kw), mode=mode, boxes=boxes,
+                                              t0=t0, nthreads=8)
+    return tuple(ref), lowered
+
+
+def allowance_share(ref, dtype):
+    """Share of the (row, entry) pairs of a reference, cost included, whose flip-plus-sign allowance is larger than
+    KAPPA * u * magnitude: there the check says little.  From the oracle alone."""
+    _, _, cm, gm, _, cf, gf = ref
+    kappa, u = (KAPPA32, U32) if dtype == "f32" else (KAPPA64, U64)
+    fin = np.isfinite(cm) & np.isfinite(gm).all(axis=1)
+    if not fin.any():
+        return 0.0
+    big = np.concatenate([(cf[fin] > kappa * u * cm[fin])[:, None], gf[fin] > kappa * u * gm[fin]], axis=1)
+    return float(big.mean())
+
+
+def check_family(family, c, g, ref, dtype, what):
+    """check() behind the condition that keeps it from passing on allowances; the family's largest ratios kept."""
+    share = allowance_share(ref, dtype)
+    assert share <= ALLOWANCE_CAP, (what, dtype, "share of entries resting on their allowance", share)
+    wc_, wg_, _ = check(c, g, ref, dtype, what)
+    cur = FAMILY.setdefault(family, [0.0, 0.0])
+    cur[0], cur[1] = max(cur[0], wc_), max(cur[1], wg_)
+    return wc_, wg_
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _family_log():
+    yield
+    for family, (rc, rg) in sorted(FAMILY.items()):
+        _log(dict(what=f"family {family}", ratio_cost=rc, ratio_grad=rg))
+        print(f"ENTRYWISE family {family}: largest |err| / (u * mag): cost {rc:.3g}, gradient {rg:.3g}")
+
+
+def _device_mode(ctx, b, dtype, waves, spl, kw, mode):
+    try:
+        ctx.set_gradient_mode(bool(mode))
+        return _device(ctx, b, dtype, waves, spl, kw)
+    finally:
+        ctx.set_gradient_mode(False)
+
+
+def every_body_batch(mp, geo, dtype):
+    """test_every_body's batch of a geometry."""
+    name, waves, spl, m, B = geo
+    b = problem.make_trajectories(B, m, mp, seed=7000 + m + B,
+                                  step_len=(0.2, 0.5) if m > 12 else (0.5, 1.2) if m > 6 else (1.0, 2.0),
+                                  boundary="random")
+    return _f32_batch(b) if dtype == "f32" else b
+
+
+CONS_VARIANTS = {"ordinary": dict(), "dyn": DYN, "dyn-steep": STEEP}
+
+
+@pytest.mark.parametrize("dtype", ["f64", "f32"])
+@pytest.mark.parametrize("variant", list(CONS_VARIANTS))
+@pytest.mark.parametrize("geo", GEOMETRIES, ids=[f"GtopConsistent-{g[0]}" for g in GEOMETRIES])
+def test_consistent_every_body(scene, oracle_mod, geo, variant, dtype):
+    """Mode 1 in every geometry of GEOMETRIES (the bodies of gtop_kernels_consistent.o), with and without the DYN block
+    and with its steep scale lengths; the cost bit-equal to mode 0's."""
+    mp, ctx, sdf = scene
+    name, waves, spl, m, B = geo
+    b = every_body_batch(mp, geo, dtype)
+    kw = CONS_VARIANTS[variant]
+    c0, g0 = _device_mode(ctx, b, dtype, waves, spl, kw, 0)
+    c, g = _device_mode(ctx, b, dtype, waves, spl, kw, 1)
+    assert np.array_equal(c0, c, equal_nan=True), "the cost differs between the gradient modes"
+    assert not np.array_equal(g0, g, equal_nan=True)
+    ref, _ = ref_ext(oracle_mod, b, sdf, kw, mode=1)
+    check_family(f"consistent {dtype}", c, g, ref, dtype, (name, variant, "mode 1"))
+
+
+# ---- moving bodies: the `world` of tests/test_gpu_moving_cost.py ----
+MOVING_PARAMS = dict(ws=1.0, wc=5.0, alpha=10.0, r=0.5, d0=0.8)        # tests/test_moving_cost.py's PARAMS (set fields)
+# (body, samples-per-lane pin, m, B)
+MOVING_GEOMETRIES = [
+    ("ten-lanes-m2", 3, 2, 40), ("ten-lanes-m5", 3, 5, 40), ("five-lanes-two-per-wave-m5", 6, 5, 41),
+    ("five-lanes-one-per-wave-m9", 6, 9, 40), ("chunked-m13", 0, 13, 24), ("chunked-m40", 0, 40, 4),
+]
+BOX_LISTS = ["cv1", "cv32", "poly8-clamped", "poly32"]
+
+
+@pytest.fixture(scope="module")
+def world(gtop, oracle_mod):
+    mp = problem.make_map((64, 56, 40), density=0.05, seed=5)
+    sdf = oracle_mod.Sdf.from_map_size(mp.origin, mp.resolution, mp.map_size)
+    sdf.build_from_occupancy(mp.occupancy)
+    ctx = gtop.GtopContext(device=0)
+    ctx.init_sdf_map(mp.map_size, mp.origin, mp.resolution)
+    ctx.update_sdf_map(mp.obstacle_points())
+    yield mp, sdf, ctx
+    ctx.close()
+
+
+def aimed_boxes(b, t0, rng, kind, rows=None):
+    """tests/test_gpu_moving_cost.py::_aimed_boxes — box k is at a random waypoint of a random trajectory when that
+    trajectory is — as the dict oracle.eval_batch_ext takes.  The polynomial lists (tests/box_poly_twin.coefficients,
+    then cubic .. quintic terms that leave the rendezvous where it is): `poly8-clamped` is of degree five, and its
+    first two boxes carry a validity interval that ends 0.05 s after their rendezvous, inside the trajectory's span.
+    rows: the trajectory each box is aimed at (default: random ones)."""
+    from tests import box_poly_twin
+    nbox = int("".join(ch for ch in kind.split("-")[0] if ch.isdigit()))
+    t0 = np.broadcast_to(np.asarray(t0, dtype=np.float64), (len(b.x),))
+    j = rng.integers(0, len(b.x), nbox) if rows is None else np.asarray(rows)
+    w = rng.integers(0, b.m + 1, nbox)
+    vel = rng.uniform(-2.0, 2.0, (nbox, 3)) * np.array([1.0, 1.0, 0.2])
+    when = np.array([t0[jj] + b.T[jj][:ww].sum() for jj, ww in zip(j, w)])
+    scale = rng.uniform(1.0, 2.0, (nbox, 3))
+    if kind.startswith("cv"):
+        return dict(p0=b.waypoints[j, w] - vel * when[:, None], vel=vel, scale=scale)
+    coef = box_poly_twin.coefficients(b.waypoints[j, w], vel, rng.uniform(-1.0, 1.0, (nbox, 3)), when)
+    coef[:, :, 3:] = rng.normal(0.0, 1.0, (nbox, 3, 3)) * np.array([2e-2, 3e-3, 4e-4])
+    coef[:, :, 0] -= sum(coef[:, :, i] * when[:, None] ** i for i in (3, 4, 5))
+    t_range = None
+    if kind.endswith("clamped"):
+        t_range = np.tile([-np.inf, np.inf], (nbox, 1))
+        t_range[:2] = np.stack([when[:2] - 0.3, when[:2] + 0.05], axis=1)
+    return dict(coef=coef, scale=scale, t_range=t_range)
+
+
+def set_boxes(ctx, boxes, t0):
+    if "coef" in boxes:
+        ctx.set_moving_box_polynomials(boxes["coef"], boxes["scale"], boxes.get("t_range"))
+    else:
+        ctx.set_moving_boxes(boxes["p0"], boxes["vel"], boxes["scale"])
+    ctx.set_moving_cost(True)
+    ctx.set_start_times(t0)
+
+
+def clear_boxes(ctx):
+    ctx.set_moving_cost(False)
+    ctx.set_start_times(None)
+    ctx.set_moving_boxes(np.zeros((0, 3)), np.zeros((0, 3)), np.zeros((0, 3)))
+
+
+def moving_case(oracle_mod, mp, sdf, geo, kind, seed=0):
+    """Batch, start times (per row in every second case, one shared scalar in the others), boxes, and — from the oracle
+    alone — the condition of tests/test_gpu_moving_cost.py::_share_changed: at least half of the rows (an eighth with
+    one box) have a box-lowered corner and a cost more than 1e-6 relative off the static cost."""
+    name, spl, m, B = geo
+    case = MOVING_GEOMETRIES.index(geo) * len(BOX_LISTS) + BOX_LISTS.index(kind)
+    b = problem.make_trajectories(B, m, mp, seed=40 + m + seed, step_len=(0.5, 1.2) if m > 12 else (1.0, 2.0))
+    rng = np.random.default_rng(9000 + 10 * case + seed)
+    t0 = rng.uniform(0.0, 5.0, B) if case % 2 == 0 else float(rng.uniform(0.0, 5.0))
+    boxes = aimed_boxes(b, t0, rng, kind)
+    ref, lowered = ref_ext(oracle_mod, b, sdf, MOVING_PARAMS, boxes=boxes, t0=t0)
+    c_static = oracle_mod.eval_batch(b.T, b.Df, b.x, sdf, oracle_mod.make_params(**MOVING_PARAMS), nthreads=8)[0]
+    share = float(np.mean((lowered > 0) & (np.abs(ref[0] - c_static) > 1e-6 * np.abs(c_static))))
+    assert share >= (1 / 8 if kind == "cv1" else 1 / 2), (name, kind, "share of rows the boxes change", share)
+    if kind.endswith("clamped"):    # the two validity intervals end inside the span of the row they are aimed at
+        span = np.broadcast_to(t0, (B,)) + b.T.sum(axis=1)
+        assert np.all(boxes["t_range"][:2, 1] < span.max()) and np.all(boxes["t_range"][:2, 1] > np.min(t0))
+    return b, t0, boxes, ref, share
+
+
+@pytest.mark.parametrize("kind", BOX_LISTS)
+@pytest.mark.parametrize("geo", MOVING_GEOMETRIES, ids=[f"GtopMoving-{g[0]}-spl{g[1]}" for g in MOVING_GEOMETRIES])
+def test_moving_every_body(world, oracle_mod, geo, kind):
+    """GtopMoving<MM> (cv*) / GtopMovingPoly<MM> (poly*) in each geometry, with and without DYN, gradient modes 0 and 1
+    (the consistent forms of the moving bodies)."""
+    mp, sdf, ctx = world
+    name, spl, m, B = geo
+    b, t0, boxes, ref, share = moving_case(oracle_mod, mp, sdf, geo, kind)
+    fam = "moving polynomial" if "coef" in boxes else "moving constant-velocity"
+    try:
+        set_boxes(ctx, boxes, t0)
+        for dyn in (False, True):
+            kw = dict(MOVING_PARAMS, **(DYN if dyn else {}))
+            c0 = None
+            for mode in (0, 1):
+                r = ref if (not dyn and mode == 0) else ref_ext(oracle_mod, b, sdf, kw, mode=mode, boxes=boxes, t0=t0)[0]
+                c, g = _device_mode(ctx, b, "f64", 0, spl, kw, mode)
+                check_family("moving plus consistent" if mode else fam, c, g, r, "f64",
+                             (name, kind, "dyn" if dyn else "ordinary", f"mode {mode}", f"share {share:.2f}"))
+                assert c0 is None or np.array_equal(c0, c), "the cost differs between the gradient modes"
+                c0 = c
+    finally:
+        clear_boxes(ctx)
+
+
+@pytest.mark.parametrize("kind", ["cv32", "poly8-clamped"])
+@pytest.mark.parametrize("m", [5, 9, 13])
+def test_moving_fused_optimizer_first_evaluation(world, oracle_mod, m, kind):
+    """The optimizer-loop bodies with the moving term (MM = GtopMoving<GtopMmaState> and its polynomial form): the first
+    evaluation's cost, at clip(x0, lb, ub), to Cmag — as test_fused_optimizer_first_evaluation."""
+    mp, sdf, ctx = world
+    B = 3
+    b = problem.make_trajectories(B, m, mp, seed=7300 + m, step_len=(0.5, 1.2))
+    rng = np.random.default_rng(7310 + m)
+    t0 = rng.uniform(0.0, 5.0, B)
+    boxes = aimed_boxes(b, t0, rng, kind)
+    lb, ub = ctx.default_bounds(b.waypoints)
+    x0 = b.x + rng.normal(0.0, 0.5, size=b.x.shape)
+    xc = problem.Batch(b.waypoints, b.T, b.Df, np.clip(x0, lb, ub), m)
+    ref, lowered = ref_ext(oracle_mod, xc, sdf, MOVING_PARAMS, boxes=boxes, t0=t0)
+    assert (lowered > 0).any()
+    try:
+        ctx.set_params(**MOVING_PARAMS)
+        set_boxes(ctx, boxes, t0)
+        ctx.set_problem(b.T, b.Df)
+        _, cost, nev, _ = ctx.optimize_batch_ex(x0, lb, ub, 1)
+    finally:
+        clear_boxes(ctx)
+        ctx.set_params()
+    assert (nev == 1).all()
+    check_family("moving polynomial" if "coef" in boxes else "moving constant-velocity", cost, ref[1], ref, "f64",
+                 ("optimizer loop + moving, first evaluation", m, kind))
+
+
+# ---- edges ----
+@pytest.fixture(scope="module")
+def far_scene(gtop, oracle_mod):
+    """test_edges' map (origin (-500, 300, 0)) and batch (segments of 0.0009 / 0.0299 / 0.03 / 0.0301 s, rows leaving
+    the map), built once."""
+    mp = problem.make_map((50, 40, 24), density=0.03, seed=12)
+    mp = problem.MapSpec(mp.grid, mp.resolution, np.array([-500.0, 300.0, 0.0]), mp.occupancy)
+    sdf = oracle_mod.Sdf.from_map_size(mp.origin, mp.resolution, mp.map_size)
+    sdf.build_from_occupancy(mp.occupancy)
+    ctx = gtop.GtopContext(device=0)
+    ctx.init_sdf_map(mp.map_size, mp.origin, mp.resolution)
+    ctx.update_sdf_map(mp.obstacle_points())
+    yield mp, sdf, ctx, _edge_batches(mp, sdf)
+    ctx.close()
+
+
+@pytest.mark.parametrize("spl", [3, 6, 0], ids=["GtopMoving-ten-lanes", "GtopMoving-five-lanes-two-per-wave", "GtopMoving-auto"])
+def test_edges_moving(far_scene, oracle_mod, spl):
+    """The edge batch through the moving geometries that serve six segments, 8 constant-velocity boxes."""
+    mp, sdf, ctx, b = far_scene
+    rng = np.random.default_rng(93)
+    t0 = rng.uniform(0.0, 5.0, len(b.x))
+    boxes = aimed_boxes(b, t0, rng, "cv8")
+    ref, lowered = ref_ext(oracle_mod, b, sdf, {}, boxes=boxes, t0=t0)
+    assert np.mean(lowered > 0) >= 0.5
+    try:
+        set_boxes(ctx, boxes, t0)
+        c, g = _device(ctx, b, "f64", 0, spl, {})
+    finally:
+        clear_boxes(ctx)
+    check_family("moving constant-velocity", c, g, ref, "f64", ("far origin / short segments, moving", spl))
+
+
+@pytest.mark.parametrize("dtype", ["f64", "f32"])
+def test_edges_consistent(far_scene, oracle_mod, dtype):
+    mp, sdf, ctx, b = far_scene
+    bb = b if dtype == "f64" else _f32_batch(b)
+    c, g = _device_mode(ctx, bb, dtype, 0, 0, {}, 1)
+    check_family(f"consistent {dtype}", c, g, ref_ext(oracle_mod, bb, sdf, {}, mode=1)[0], dtype,
+                 ("far origin / short segments, mode 1",))
+
+
+@pytest.mark.parametrize("dtype", ["f64", "f32"])
+def test_signed_field_consistent(gtop, oracle_mod, dtype):
+    """test_signed_field's field in mode 1."""
+    mp = problem.make_map((48, 40, 24), density=0.05, seed=13)
+    ctx = gtop.GtopContext(device=0)
+    try:
+        ctx.set_field_sign(True, 1.0)
+        ctx.init_sdf_map(mp.map_size, mp.origin, mp.resolution)
+        ctx.update_sdf_map(mp.obstacle_points())
+        dist = ctx.get_sdf().reshape(-1).astype(np.float64)
+        assert (dist < 0).any()
+        sdf = oracle_mod.Sdf.from_map_size(mp.origin, mp.resolution, mp.map_size)
+        sdf.dist[:] = dist
+        b = problem.make_trajectories(64, 6, mp, seed=14, step_len=(0.5, 1.2))
+        bb = b if dtype == "f64" else _f32_batch(b)
+        c, g = _device_mode(ctx, bb, dtype, 0, 0, {}, 1)
+        check_family(f"consistent {dtype}", c, g, ref_ext(oracle_mod, bb, sdf, {}, mode=1)[0], dtype,
+                     ("signed field, mode 1",))
+    finally:
+        ctx.close()
+
+
+# ---- the 64-bit-index forms ----
+# id: the body; (m, B, waves, samples-per-lane pin, parameters, gradient mode, box list or None)
+WIDE_CASES = {
+    "WIDE-DYN-spl3-m6": (6, 96, 0, 3, DYN, 0, None),
+    "WIDE-five-lanes-one-per-wave-spl6-m9": (9, 60, 0, 6, {}, 0, None),
+    "WIDE-two-wavefronts-m10": (10, 40, 1, 0, {}, 0, None),
+    "WIDE-chunked-m13": (13, 40, 0, 0, {}, 0, None),
+    "WIDE-consistent-spl3-m6": (6, 96, 0, 3, {}, 1, None),
+    "WIDE-consistent-spl6-m6": (6, 96, 0, 6, {}, 1, None),
+    "WIDE-moving-cv8-spl6-m6": (6, 8, 0, 6, {}, 0, "cv8"),      # (the map is 819 m wide: one box per row)
+}
+
+
+def wide_batch(ms, m, B):
+    return problem.make_trajectories(B, m, ms, seed=77 + m, margin=0.15, step_len=(0.5, 1.5) if m <= 6 else (0.3, 0.8))
+
+
+@pytest.mark.parametrize("case", list(WIDE_CASES))
+def test_wide_index_more_bodies(wide, oracle_mod, case):
+    ms, ctx, sdf = wide
+    m, B, waves, spl, kw, mode, kind = WIDE_CASES[case]
+    b = wide_batch(ms, m, B)
+    boxes = t0 = None
+    if kind:
+        rng = np.random.default_rng(78)
+        t0 = rng.uniform(0.0, 5.0, B)
+        boxes = aimed_boxes(b, t0, rng, kind, rows=np.arange(B))
+    ref, lowered = ref_ext(oracle_mod, b, sdf, kw, mode=mode, boxes=boxes, t0=t0)
+    try:
+        if kind:
+            assert np.mean(lowered > 0) >= 0.5
+            set_boxes(ctx, boxes, t0)
+        c, g = _device_mode(ctx, b, "f64", waves, spl, kw, mode)
+    finally:
+        if kind:
+            clear_boxes(ctx)
+    check_family("wide", c, g, ref, "f64", (case,))
+
+
+def test_wide_index_fused_optimizer_first_evaluation(wide, oracle_mod):
+    """The fp64 optimizer loop's 64-bit-index body at five segments: its first evaluation's cost to Cmag."""
+    ms, ctx, sdf = wide
+    m, B = 5, 3
+    b = wide_batch(ms, m, B)
+    lb, ub = ctx.default_bounds(b.waypoints)
+    x0 = b.x + np.random.default_rng(79).normal(0.0, 0.5, size=b.x.shape)
+    ctx.set_params()
+    ctx.set_problem(b.T, b.Df)
+    _, cost, nev, _ = ctx.optimize_batch_ex(x0, lb, ub, 1)
+    assert (nev == 1).all()
+    xc = problem.Batch(b.waypoints, b.T, b.Df, np.clip(x0, lb, ub), m)
+    ref, _ = ref_ext(oracle_mod, xc, sdf, {})
+    check_family("wide", cost, ref[1], ref, "f64", ("WIDE optimizer loop, first evaluation", m, B))
