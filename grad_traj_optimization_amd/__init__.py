@@ -20,8 +20,13 @@ from . import insert  # noqa: F401
 from .kinematics import (EXCEEDS, KIN_ABI_VERSION, KIN_ENTRY_POINTS, KIN_REPORT, KIN_SEG, UNDECIDED, WITHIN,  # noqa: F401
                          GtopKinOpts, certify_kinematics_batch, certify_kinematics_device, select_best_kin_certified_device)
 from . import kinematics  # noqa: F401
+from .separation import (SEP_ABI_VERSION, SEP_ENTRY_POINTS, SEP_ROW, GtopSepOpts, select_distinct_device,  # noqa: F401
+                         separation_batch, separation_device, separation_workspace_bytes)
+from . import separation  # noqa: F401
 
-__all__ = ["EXCEEDS", "UNDECIDED", "WITHIN", "KIN_ABI_VERSION", "KIN_ENTRY_POINTS", "KIN_REPORT", "KIN_SEG", "GtopKinOpts", "kinematics",
+__all__ = ["SEP_ABI_VERSION", "SEP_ENTRY_POINTS", "SEP_ROW", "GtopSepOpts", "separation", "select_distinct_device",
+           "separation_batch", "separation_device", "separation_workspace_bytes",
+"EXCEEDS", "UNDECIDED", "WITHIN", "KIN_ABI_VERSION", "KIN_ENTRY_POINTS", "KIN_REPORT", "KIN_SEG", "GtopKinOpts", "kinematics",
            "certify_kinematics_batch", "certify_kinematics_device", "select_best_kin_certified_device",
 "INSERT_INFO", "GtopInsert", "insert", "insert_waypoints", "insert_waypoints_device","GTOP_F32", "GTOP_F64", "GtopError", "GtopLimits", "GtopParams", "GtopRetime", "OPTI_NODE_PARAMS",
            "GtopContext", "GtopGroup", "Rendezvous", "box_polynomial_centres", "library_path", "load_library",

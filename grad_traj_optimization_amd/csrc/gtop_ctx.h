@@ -9,6 +9,7 @@
 //   gtop_capi_report.cpp   the sampled reports (whole and per segment), both selections, both certificates
 //   gtop_capi_remedy.cpp   the remedies for a row that fails: segment-time reallocation, waypoint insertion
 //   gtop_capi_kinematics.cpp  the companion header include/gtop_kinematics.h: the kinematic certificate, its selection
+//   gtop_capi_separation.cpp  the companion header include/gtop_separation.h: pairwise separation, distinct candidates
 // Host-side only: they own device buffers, fill kernel arguments, launch.  There is deliberately no CPU code path:
 // without a gfx950 device every entry point fails (GTOP_ERR_NO_DEVICE).
 #ifndef GTOP_CTX_H_
@@ -123,6 +124,7 @@ struct gtop_ctx {
   GtopDevBuf<double> val_rep;  // gtop_validate_batch staging: report | cost, then pass and best behind them
   GtopDevBuf<double> seg_rep;  // gtop_validate_segments / gtop_reallocate_times staging: segment report | T_out;
                                // gtop_insert_waypoints': when | lb | ub | x_out | T_out | lb_out | ub_out | info
+  GtopDevBuf<double> sep_stage;  // gtop_separation_batch staging: pair_min | pair_max | rows | the launches' workspace
   GtopDevBuf<double> d_q;      // host-API staging of gtop_edt_query: pos | time | dist | grad; gtop_trajectory_samples'
                                // sample scratch too
   GtopPinnedBuf<double> pin;   // device-visible host staging for small host-buffer evaluations: x | cost | grad

@@ -271,6 +271,21 @@ hipError_t gtop_launch_traj_kinematics(int B, int m, const double *coeff, const 
                                        double max_acc, int per_axis, int max_depth, int max_refine, double *kin,
                                        double *seg, hipStream_t stream);
 
+// ---- pairwise separation and distinct-candidate selection (gtop_separation.hip), fp64 ----------------------------
+#define GTOP_SEP_ROW 6   // = include/gtop_separation.h
+// the bytes of the workspace gtop_launch_separation needs for B rows on n_samples samples (its layout is the kernels')
+size_t gtop_separation_work_bytes(int B, int n_samples);
+// pair_min, pair_max [B][B] and rows [B][GTOP_SEP_ROW] of the trajectories (coeff, T) on the grid t_lo + k dt as
+// include/gtop_separation.h lays them out; t0 (NULL: every start 0) with stride 0 or 1; three launches (sample, pairs,
+// rows), work as sized above
+hipError_t gtop_launch_separation(int B, int m, const double *coeff, const double *T, int t_stride, const double *t0,
+                                  int t0_stride, double t_lo, double dt, int n_samples, int hold_ends, double radius,
+                                  double *pair_min, double *pair_max, double *rows, void *work, hipStream_t stream);
+// chosen [K] and count [1] (either may be NULL) by the greedy rule of include/gtop_separation.h; pass may be NULL;
+// one launch of one workgroup, B = 0 included
+hipError_t gtop_launch_select_distinct(int B, const unsigned char *pass, const double *cost, const double *pair_max,
+                                       double min_gap, int K, int *chosen, int *count, hipStream_t stream);
+
 // ---- waypoint insertion (gtop_insert.hip), fp64 ------------------------------------------------------------------
 #define GTOP_INSERT_AT_TIME 0   // = include/gtop.h
 #define GTOP_INSERT_LONGEST 1   // = include/gtop.h
