@@ -23,8 +23,15 @@ from . import kinematics  # noqa: F401
 from .separation import (SEP_ABI_VERSION, SEP_ENTRY_POINTS, SEP_ROW, GtopSepOpts, select_distinct_device,  # noqa: F401
                          separation_batch, separation_device, separation_workspace_bytes)
 from . import separation  # noqa: F401
+from .separation_certificate import (SEPCERT_ABI_VERSION, SEPCERT_ENTRY_POINTS, SEPCERT_PAIR, SEPCERT_ROW,  # noqa: F401
+                                     GtopSepCertOpts, certify_separation_batch, certify_separation_device,
+                                     sepcert_library, sepcert_workspace_bytes)
+from . import separation_certificate  # noqa: F401
 
-__all__ = ["SEP_ABI_VERSION", "SEP_ENTRY_POINTS", "SEP_ROW", "GtopSepOpts", "separation", "select_distinct_device",
+__all__ = ["SEPCERT_ABI_VERSION", "SEPCERT_ENTRY_POINTS", "SEPCERT_PAIR", "SEPCERT_ROW", "GtopSepCertOpts",
+           "separation_certificate", "certify_separation_batch", "certify_separation_device", "sepcert_library",
+           "sepcert_workspace_bytes",
+"SEP_ABI_VERSION", "SEP_ENTRY_POINTS", "SEP_ROW", "GtopSepOpts", "separation", "select_distinct_device",
            "separation_batch", "separation_device", "separation_workspace_bytes",
 "EXCEEDS", "UNDECIDED", "WITHIN", "KIN_ABI_VERSION", "KIN_ENTRY_POINTS", "KIN_REPORT", "KIN_SEG", "GtopKinOpts", "kinematics",
            "certify_kinematics_batch", "certify_kinematics_device", "select_best_kin_certified_device",

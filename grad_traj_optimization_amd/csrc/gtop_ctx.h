@@ -10,6 +10,7 @@
 //   gtop_capi_remedy.cpp   the remedies for a row that fails: segment-time reallocation, waypoint insertion
 //   gtop_capi_kinematics.cpp  the companion header include/gtop_kinematics.h: the kinematic certificate, its selection
 //   gtop_capi_separation.cpp  the companion header include/gtop_separation.h: pairwise separation, distinct candidates
+//   gtop_capi_separation_certificate.cpp  include/gtop_separation_certificate.h: the certificate of pairwise separation
 // Host-side only: they own device buffers, fill kernel arguments, launch.  There is deliberately no CPU code path:
 // without a gfx950 device every entry point fails (GTOP_ERR_NO_DEVICE).
 #ifndef GTOP_CTX_H_
@@ -125,6 +126,7 @@ struct gtop_ctx {
   GtopDevBuf<double> seg_rep;  // gtop_validate_segments / gtop_reallocate_times staging: segment report | T_out;
                                // gtop_insert_waypoints': when | lb | ub | x_out | T_out | lb_out | ub_out | info
   GtopDevBuf<double> sep_stage;  // gtop_separation_batch staging: pair_min | pair_max | rows | the launches' workspace
+  GtopDevBuf<double> sepcert_stage;  // gtop_certify_separation_batch staging: pairs | rows | the launches' workspace
   GtopDevBuf<double> d_q;      // host-API staging of gtop_edt_query: pos | time | dist | grad; gtop_trajectory_samples'
                                // sample scratch too
   GtopPinnedBuf<double> pin;   // device-visible host staging for small host-buffer evaluations: x | cost | grad

@@ -286,6 +286,19 @@ hipError_t gtop_launch_separation(int B, int m, const double *coeff, const doubl
 hipError_t gtop_launch_select_distinct(int B, const unsigned char *pass, const double *cost, const double *pair_max,
                                        double min_gap, int K, int *chosen, int *count, hipStream_t stream);
 
+// ---- continuous-time certificate of pairwise separation (gtop_separation_certificate.hip), fp64 ------------------
+#define GTOP_SEPCERT_PAIR 8   // = include/gtop_separation_certificate.h
+#define GTOP_SEPCERT_ROW 10   // = include/gtop_separation_certificate.h
+// the bytes of the workspace gtop_launch_certify_separation needs for B rows (the rows' boxes)
+size_t gtop_sepcert_work_bytes(int B);
+// pairs [B][B][GTOP_SEPCERT_PAIR] and rows [B][GTOP_SEPCERT_ROW] of the trajectories (coeff, T) as
+// include/gtop_separation_certificate.h lays them out, on the interval tree of gtop_certify.hip with its INFLATE and
+// SLACK; t0 (NULL: every start 0) with stride 0 or 1; one wavefront per pair; two launches (pairs, rows), three with cull
+hipError_t gtop_launch_certify_separation(int B, int m, const double *coeff, const double *T, int t_stride,
+                                          const double *t0, int t0_stride, double min_sep, double t_lo, double t_hi,
+                                          int max_depth, int max_refine, int hold_ends, int cull, double *pairs,
+                                          double *rows, void *work, hipStream_t stream);
+
 // ---- waypoint insertion (gtop_insert.hip), fp64 ------------------------------------------------------------------
 #define GTOP_INSERT_AT_TIME 0   // = include/gtop.h
 #define GTOP_INSERT_LONGEST 1   // = include/gtop.h
