@@ -27,8 +27,13 @@ from .separation_certificate import (SEPCERT_ABI_VERSION, SEPCERT_ENTRY_POINTS, 
                                      GtopSepCertOpts, certify_separation_batch, certify_separation_device,
                                      sepcert_library, sepcert_workspace_bytes)
 from . import separation_certificate  # noqa: F401
+from .prediction import (PRED_ABI_VERSION, PRED_ENTRY_POINTS, PRED_INFO, GtopPredictOpts, fit_predictions,  # noqa: F401
+                         fit_predictions_device, pred_abi_version, pred_library, refresh_box_predictions_device)
+from . import prediction  # noqa: F401
 
-__all__ = ["SEPCERT_ABI_VERSION", "SEPCERT_ENTRY_POINTS", "SEPCERT_PAIR", "SEPCERT_ROW", "GtopSepCertOpts",
+__all__ = ["PRED_ABI_VERSION", "PRED_ENTRY_POINTS", "PRED_INFO", "GtopPredictOpts", "prediction", "fit_predictions",
+           "fit_predictions_device", "pred_abi_version", "pred_library", "refresh_box_predictions_device",
+"SEPCERT_ABI_VERSION", "SEPCERT_ENTRY_POINTS", "SEPCERT_PAIR", "SEPCERT_ROW", "GtopSepCertOpts",
            "separation_certificate", "certify_separation_batch", "certify_separation_device", "sepcert_library",
            "sepcert_workspace_bytes",
 "SEP_ABI_VERSION", "SEP_ENTRY_POINTS", "SEP_ROW", "GtopSepOpts", "separation", "select_distinct_device",

@@ -107,6 +107,52 @@ void GradTrajOptimizer::setMovingObstaclePredictions(const std::vector<Poly3> &c
   if (last_status_ == GTOP_OK) last_status_ = gtop_set_moving_cost(ctx_, nbox > 0);
 }
 
+std::vector<GradTrajOptimizer::PredictInfo> GradTrajOptimizer::fitObstaclePredictions(
+    const std::vector<History> &histories, const std::vector<Vec3> &scales, const PredictOptions &options) {
+  static_assert(GTOP_PRED_INFO == 12, "PredictInfo is one info row");
+  const int N = (int)histories.size();
+  std::vector<PredictInfo> info((size_t)N);
+  if (!ctx_) return info;
+  if (scales.size() != histories.size()) {
+    last_status_ = GTOP_ERR_INVALID;
+    return info;
+  }
+  size_t H = 1;
+  for (const History &h : histories) H = std::max(H, h.size());
+  std::vector<double> hist((size_t)N * H * 4, 0.0);
+  std::vector<int32_t> count((size_t)N);
+  for (int b = 0; b < N; ++b) {
+    count[b] = (int32_t)histories[b].size();
+    for (size_t i = 0; i < histories[b].size(); ++i)
+      std::copy(histories[b][i].begin(), histories[b][i].end(), hist.begin() + ((size_t)b * H + i) * 4);
+  }
+  gtop_predict_opts o{};
+  o.mode = options.mode;
+  o.degree = options.degree;
+  o.lambda = options.lambda;
+  o.horizon = options.horizon;
+  o.inflate = options.inflate;
+  o.regularise_horizon = options.regularise_horizon;
+  std::vector<Poly3> coef((size_t)N);
+  std::vector<std::array<double, 2>> t_range((size_t)N);
+  last_status_ = gtop_fit_predictions(N, (int)H, hist.data(), count.data(), nullptr, &o, N ? coef[0].data() : nullptr,
+                                      N ? t_range[0].data() : nullptr, N ? info[0].data() : nullptr, nullptr);
+  if (last_status_ != GTOP_OK) return info;
+  std::vector<Vec3> scale(scales);
+  for (int b = 0; b < N; ++b) {
+    if (info[b][0] != GTOP_PRED_OK && info[b][0] != GTOP_PRED_LOWERED) {
+      last_status_ = GTOP_ERR_INVALID;
+      return info;
+    }
+    for (int k = 0; k < 3; ++k) {
+      const double grow = options.inflate * info[b][6 + k];   // (its own statement: rounded before it is added)
+      scale[b][k] = 2.0 * (0.5 * scales[b][k] + grow);
+    }
+  }
+  setMovingObstaclePredictions(coef, t_range, scale);
+  return info;
+}
+
 void GradTrajOptimizer::setStartTime(double t0) {
   if (!ctx_) return;
   last_status_ = gtop_set_start_times(ctx_, 1, &t0);

@@ -21,6 +21,7 @@
 
 #include "gtop.h"
 #include "gtop_kinematics.h"
+#include "gtop_prediction.h"
 
 #define OPT_INITIAL_TRY 0
 #define OPT_FIRST_STEP 1
@@ -118,6 +119,23 @@ class GradTrajOptimizer {
   using Poly3 = std::array<double, 18>;
   void setMovingObstaclePredictions(const std::vector<Poly3> &coef, const std::vector<std::array<double, 2>> &t_range,
                                     const std::vector<Vec3> &scale);
+  // The predictions FITTED from observation histories (include/gtop_prediction.h; the reference's ObjPredictor,
+  // src/obj_predictor.cpp): the host fit gtop_fit_predictions of histories[b] — samples {x, y, z, t}, oldest first —
+  // followed by setMovingObstaclePredictions with the fitted rows and the extents scales[b] + 2 inflate resmax (the
+  // half extent gtop_refresh_box_predictions_device writes).  Returns one info row per object (GTOP_PRED_INFO doubles:
+  // status, count, degree used, the interval's start, t_last, the interval's end, resmax per axis, rms, two pads).  An
+  // object that cannot be fitted (no samples, a non-finite one, times that do not advance) refuses the whole list
+  // (ok() is false, the list in force stays); its status in the rows returned tells which.
+  struct PredictOptions {
+    int mode = 0;            // GTOP_PREDICT_POLYFIT; 1: GTOP_PREDICT_CONST_VEL
+    int degree = 5;
+    double lambda = 1.0, horizon = 0.0, inflate = 0.0;
+    bool regularise_horizon = false;
+  };
+  using History = std::vector<std::array<double, 4>>;
+  using PredictInfo = std::array<double, 12>;
+  std::vector<PredictInfo> fitObstaclePredictions(const std::vector<History> &histories, const std::vector<Vec3> &scales,
+                                                  const PredictOptions &options);
   void setStartTime(double t0);
 
   // The safety report of the trajectory at the current Dp (include/gtop.h, gtop_validate_batch; not a method of the

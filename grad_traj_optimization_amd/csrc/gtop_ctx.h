@@ -11,6 +11,7 @@
 //   gtop_capi_kinematics.cpp  the companion header include/gtop_kinematics.h: the kinematic certificate, its selection
 //   gtop_capi_separation.cpp  the companion header include/gtop_separation.h: pairwise separation, distinct candidates
 //   gtop_capi_separation_certificate.cpp  include/gtop_separation_certificate.h: the certificate of pairwise separation
+//   gtop_capi_prediction.cpp  include/gtop_prediction.h: predictions fitted from histories, the box list's refresh
 // Host-side only: they own device buffers, fill kernel arguments, launch.  There is deliberately no CPU code path:
 // without a gfx950 device every entry point fails (GTOP_ERR_NO_DEVICE).
 #ifndef GTOP_CTX_H_

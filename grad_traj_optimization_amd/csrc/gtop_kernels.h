@@ -299,8 +299,22 @@ hipError_t gtop_launch_certify_separation(int B, int m, const double *coeff, con
                                           int max_depth, int max_refine, int hold_ends, int cull, double *pairs,
                                           double *rows, void *work, hipStream_t stream);
 
+// ---- predictions fitted from observation histories (gtop_prediction.hip), fp64 -----------------------------------
+struct GtopPredictArgs;   // gtop_prediction_fit.h: gtop_predict_opts as the kernel takes it
+// coef [N][18], t_range [N][2], info [N][12] and local [N][20] (may be NULL) of the histories hist [N][H][4] (16-byte
+// aligned), count [N], head [N] (may be NULL) as include/gtop_prediction.h lays them out; one wavefront per object, one
+// launch, none for N = 0
+hipError_t gtop_launch_fit_predictions(int mode, int N, int H, const double *hist, const int *count, const int *head,
+                                       const GtopPredictArgs &o, double *coef, double *t_range, double *info,
+                                       double *local, hipStream_t stream);
+// the same fit written into rows [N][kBoxRowPoly] of a polynomial box list and, where given, into cost_rows (the rows
+// the cost bodies read); scale [N][3] (NULL: the extents stay); one launch
+hipError_t gtop_launch_refresh_predictions(int mode, int N, int H, const double *hist, const int *count, const int *head,
+                                           const GtopPredictArgs &o, const double *scale, double *rows, double *cost_rows,
+                                           double *info, hipStream_t stream);
+
 // ---- waypoint insertion (gtop_insert.hip), fp64 ------------------------------------------------------------------
-#define GTOP_INSERT_AT_TIME 0   // = include/gtop.h
+#define GTOP_INSERT_AT_TIME 0  // = include/gtop.h
 #define GTOP_INSERT_LONGEST 1   // = include/gtop.h
 #define GTOP_INSERT_INFO 6      // = include/gtop.h
 // One segment of every row cut in two as include/gtop.h states it: x_out, lb_out, ub_out [B][9m], T_out [B][m + 1],
