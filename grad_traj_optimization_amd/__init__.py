@@ -30,8 +30,15 @@ from . import separation_certificate  # noqa: F401
 from .prediction import (PRED_ABI_VERSION, PRED_ENTRY_POINTS, PRED_INFO, GtopPredictOpts, fit_predictions,  # noqa: F401
                          fit_predictions_device, pred_abi_version, pred_library, refresh_box_predictions_device)
 from . import prediction  # noqa: F401
+from .timeopt import (TIME_ABI_VERSION, TIME_ENTRY_POINTS, TIME_PARTS, TIMEOPT_INFO, GtopTimeOpt,  # noqa: F401
+                      optimize_times, optimize_times_device, time_abi_version, time_gradient_batch,
+                      time_gradient_device, time_library)
+from . import timeopt  # noqa: F401
 
-__all__ = ["PRED_ABI_VERSION", "PRED_ENTRY_POINTS", "PRED_INFO", "GtopPredictOpts", "prediction", "fit_predictions",
+__all__ = ["TIME_ABI_VERSION", "TIME_ENTRY_POINTS", "TIME_PARTS", "TIMEOPT_INFO", "GtopTimeOpt", "timeopt",
+           "optimize_times", "optimize_times_device", "time_abi_version", "time_gradient_batch", "time_gradient_device",
+           "time_library",
+"PRED_ABI_VERSION", "PRED_ENTRY_POINTS", "PRED_INFO", "GtopPredictOpts", "prediction", "fit_predictions",
            "fit_predictions_device", "pred_abi_version", "pred_library", "refresh_box_predictions_device",
 "SEPCERT_ABI_VERSION", "SEPCERT_ENTRY_POINTS", "SEPCERT_PAIR", "SEPCERT_ROW", "GtopSepCertOpts",
            "separation_certificate", "certify_separation_batch", "certify_separation_device", "sepcert_library",

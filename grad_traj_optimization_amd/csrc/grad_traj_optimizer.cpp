@@ -326,6 +326,76 @@ bool GradTrajOptimizer::reallocateSegmentTime(const RetimeOptions &options) {
   return true;
 }
 
+bool GradTrajOptimizer::timeGradient(double *cost, std::vector<double> *gT, std::vector<std::array<double, 4>> *parts) {
+  if (!ctx_ || m_ < 2 || dp_.empty()) {
+    last_status_ = GTOP_ERR_STATE;
+    return false;
+  }
+  double c = 0.0;
+  std::vector<double> g(m_), p(parts ? (size_t)m_ * GTOP_TIME_PARTS : 0);
+  last_status_ = gtop_time_gradient_batch(ctx_, 1, dp_.data(), &c, g.data(), parts ? p.data() : nullptr);
+  if (last_status_ != GTOP_OK) return false;
+  if (cost) *cost = c;
+  if (gT) *gT = g;
+  if (parts) {
+    parts->resize(m_);
+    for (int s = 0; s < m_; ++s)
+      for (int k = 0; k < GTOP_TIME_PARTS; ++k) (*parts)[s][k] = p[(size_t)s * GTOP_TIME_PARTS + k];
+  }
+  return true;
+}
+
+bool GradTrajOptimizer::optimizeSegmentTimes(const TimeOptConfig &config, TimeOptInfo *info) {
+  if (!ctx_ || m_ < 2 || dp_.empty()) {
+    last_status_ = GTOP_ERR_STATE;
+    return false;
+  }
+  gtop_timeopt opt{};
+  opt.rho = config.rho;
+  opt.t_min = config.t_min;
+  opt.t_max = config.t_max;
+  opt.first_move = config.first_move;
+  opt.ftol_rel = config.ftol_rel;
+  opt.xtol_abs = config.xtol_abs;
+  opt.max_evals = config.max_evals;
+  std::vector<double> lo;
+  if (config.keep_limits) {   // the LIMITS reallocation of the trajectory as it stands, Dp untouched
+    gtop_retime rt{};
+    rt.mode = GTOP_RETIME_LIMITS;
+    rt.max_vel = config.limits.max_vel;
+    rt.max_acc = config.limits.max_acc;
+    rt.per_axis = config.limits.per_axis;
+    rt.uniform = config.limits.uniform;
+    rt.max_ratio = config.limits.max_ratio;
+    gtop_limits lim{};
+    lim.margin = config.limits.report.margin;
+    lim.use_boxes = config.limits.report.use_boxes;
+    lo.resize(m_);
+    std::vector<double> x = dp_;
+    last_status_ = gtop_reallocate_times(ctx_, &rt, 1, x.data(), config.limits.report.dt_sample, &lim, lo.data());
+    if (last_status_ != GTOP_OK) return false;
+  }
+  std::vector<double> T(m_);
+  double r[GTOP_TIMEOPT_INFO];
+  last_status_ = gtop_optimize_times(ctx_, &opt, 1, dp_.data(), lo.empty() ? nullptr : lo.data(), T.data(), r);
+  if (last_status_ != GTOP_OK) return false;
+  last_status_ = gtop_set_problem(ctx_, 1, m_, T.data(), m_, df_.data());   // (refuses a time that is not > 0)
+  if (last_status_ != GTOP_OK) return false;
+  segment_time_ = T;
+  coefficientsFromDerivatives(dp_);
+  if (info) {
+    info->code = (int)r[0];
+    info->accepted = (int)r[1];
+    info->evaluations = (int)r[2];
+    info->f_start = r[3];
+    info->f = r[4];
+    info->cost = r[5];
+    info->free_gradient = r[6];
+    info->time_sum = r[7];
+  }
+  return true;
+}
+
 bool GradTrajOptimizer::insertWaypoint(const InsertOptions &options, InsertInfo *info) {
   if (!ctx_ || m_ < 2 || dp_.empty()) {
     last_status_ = GTOP_ERR_STATE;

@@ -22,6 +22,7 @@
 #include "gtop.h"
 #include "gtop_kinematics.h"
 #include "gtop_prediction.h"
+#include "gtop_time.h"
 
 #define OPT_INITIAL_TRY 0
 #define OPT_FIRST_STEP 1
@@ -245,6 +246,30 @@ class GradTrajOptimizer {
     double distance = 0.0;              // the static distance at the new waypoint before the push (0 when push is off)
   };
   bool insertWaypoint(const InsertOptions &options, InsertInfo *info = nullptr);
+  // The derivative of the cost with respect to every segment time at the current Dp and segment_time
+  // (include/gtop_time.h, gtop_time_gradient_batch): the callback's cost at the parameters the last optimizeTrajectory
+  // left in force, gT[s] = d cost / d T_s, and (given) per segment the smoothness and collision + dyn cost and their
+  // two derivatives.  false when the call fails.
+  bool timeGradient(double *cost, std::vector<double> *gT, std::vector<std::array<double, 4>> *parts = nullptr);
+  // New segment times by minimising cost + rho sum(T) over them at the current Dp (include/gtop_time.h,
+  // gtop_optimize_times): a projected gradient descent with backtracking on the device.  keep_limits: the times of
+  // reallocateSegmentTime(limits) at the current trajectory are the lower bounds — never faster than max_vel / max_acc
+  // allow.  The new times become the object's segment_time — what getSegmentTime returns and the next
+  // optimizeTrajectory runs on —, the coefficients are refreshed.  false, and nothing changed, when the call fails.
+  struct TimeOptConfig {
+    double rho = 1.0;
+    double t_min = 0.05, t_max = 60.0;
+    double first_move = 0.05;
+    double ftol_rel = 1e-6, xtol_abs = 1e-9;
+    int max_evals = 40;
+    bool keep_limits = false;
+    RetimeOptions limits;
+  };
+  struct TimeOptInfo {
+    int code = 0, accepted = 0, evaluations = 0;   // 3 FTOL, 4 XTOL, 5 MAXEVAL
+    double f_start = 0.0, f = 0.0, cost = 0.0, free_gradient = 0.0, time_sum = 0.0;
+  };
+  bool optimizeSegmentTimes(const TimeOptConfig &config, TimeOptInfo *info = nullptr);
 
   // extras (not in the reference)
   bool ok() const { return ctx_ != nullptr && last_status_ == GTOP_OK; }

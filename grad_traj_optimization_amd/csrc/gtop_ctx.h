@@ -12,6 +12,7 @@
 //   gtop_capi_separation.cpp  the companion header include/gtop_separation.h: pairwise separation, distinct candidates
 //   gtop_capi_separation_certificate.cpp  include/gtop_separation_certificate.h: the certificate of pairwise separation
 //   gtop_capi_prediction.cpp  include/gtop_prediction.h: predictions fitted from histories, the box list's refresh
+//   gtop_capi_time.cpp        include/gtop_time.h: the segment-time gradient, the optimizer of the time allocation
 // Host-side only: they own device buffers, fill kernel arguments, launch.  There is deliberately no CPU code path:
 // without a gfx950 device every entry point fails (GTOP_ERR_NO_DEVICE).
 #ifndef GTOP_CTX_H_
@@ -125,7 +126,8 @@ struct gtop_ctx {
                                        // gtop_create: the entry point itself must not allocate)
   GtopDevBuf<double> val_rep;  // gtop_validate_batch staging: report | cost, then pass and best behind them
   GtopDevBuf<double> seg_rep;  // gtop_validate_segments / gtop_reallocate_times staging: segment report | T_out;
-                               // gtop_insert_waypoints': when | lb | ub | x_out | T_out | lb_out | ub_out | info
+                               // gtop_insert_waypoints': when | lb | ub | x_out | T_out | lb_out | ub_out | info;
+                               // gtop_time_gradient_batch's: cost | gT | parts; gtop_optimize_times': T_lo | T_out | info
   GtopDevBuf<double> sep_stage;  // gtop_separation_batch staging: pair_min | pair_max | rows | the launches' workspace
   GtopDevBuf<double> sepcert_stage;  // gtop_certify_separation_batch staging: pairs | rows | the launches' workspace
   GtopDevBuf<double> d_q;      // host-API staging of gtop_edt_query: pos | time | dist | grad; gtop_trajectory_samples'

@@ -327,4 +327,23 @@ hipError_t gtop_launch_insert_waypoints(const GtopGrid &g, const double *rec, in
                                         double *x_out, double *T_out, double *lb_out, double *ub_out, double *info,
                                         hipStream_t stream);
 
+// ---- segment-time gradient and segment-time optimizer (gtop_time.hip), fp64 --------------------------------------
+#define GTOP_TIME_PARTS 4     // = include/gtop_time.h
+#define GTOP_TIMEOPT_INFO 8   // = include/gtop_time.h
+// the cost's parameters as gtop_set_params holds them (gtop_params of include/gtop.h, which this header does not see)
+struct GtopTimeCost {
+  double ws, wc, alpha, r, d0, alpha_v, r_v, v0, alpha_a, r_a, a0;
+  int step, enable_dyn;
+};
+// cost [B], gT [B][m] and parts [B][m][GTOP_TIME_PARTS] (may be NULL) as include/gtop_time.h lays them out; rec: the
+// fp64 corner records; one wavefront per trajectory, one launch
+hipError_t gtop_launch_time_gradient(const GtopGrid &g, const double *rec, const GtopTimeCost &p, int B, int m,
+                                     const double *x, const double *Df, const double *T, int t_stride, double *cost,
+                                     double *gT, double *parts, hipStream_t stream);
+// T_out [B][m] and info [B][GTOP_TIMEOPT_INFO] by the rule of include/gtop_time.h; T_lo [B][m] may be NULL; one launch
+hipError_t gtop_launch_time_optimize(const GtopGrid &g, const double *rec, const GtopTimeCost &p, double rho,
+                                     double t_min, double t_max, double first_move, double ftol_rel, double xtol_abs,
+                                     int max_evals, int B, int m, const double *x, const double *Df, const double *T,
+                                     int t_stride, const double *T_lo, double *T_out, double *info, hipStream_t stream);
+
 #endif  // GTOP_KERNELS_H_

@@ -1,0 +1,422 @@
+"""include/gtop_time.h on the GPU: the segment-time gradient against the evaluation's cost and against the numpy twin
+(tests/time_twin.py) on the library's own field, its bit-level laws (one derivative whatever the gradient mode, rows
+independent of the batch, every output written once), and the optimizer of the time allocation against its laws, the
+twin's run and the hand-derived case of tests/golden/TIME_ANALYTIC.md.
+
+Criterion and tolerance of the comparisons: tests/test_gpu_kino.py's — scenes.rel_err at 1e-5, the project's fp64
+parity bound, which covers a sample whose float rounding falls differently."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from grad_traj_optimization_amd import problem
+from tests import scenes
+from tests import time_twin as tt
+from tests.test_time_twin import ANALYTIC_TOL, _rest_case
+
+pytestmark = pytest.mark.gpu
+TOL = 1e-5
+ERR_INVALID, ERR_STATE = 1, 4
+DYN = dict(enable_dyn=1, alpha_v=2.0, r_v=4.0, alpha_a=1.5, r_a=15.0, step=2)
+GUARD = -7.25
+
+
+def _field(gtop, oracle_mod, mp, signed=False):
+    ctx = gtop.GtopContext(device=0)
+    if signed:
+        ctx.set_field_sign(True, 1.5)
+    ctx.init_sdf_map(mp.map_size, mp.origin, mp.resolution)
+    ctx.update_sdf_map(mp.obstacle_points())
+    sdf = oracle_mod.Sdf.from_map_size(mp.origin, mp.resolution, mp.map_size)
+    sdf.dist[:] = ctx.get_sdf().reshape(-1)          # the twin reads the library's own field
+    return ctx, sdf
+
+
+@pytest.fixture(scope="module")
+def scene(gtop, oracle_mod):
+    mp = problem.make_map((60, 50, 30), density=0.03, seed=11)
+    ctx, sdf = _field(gtop, oracle_mod, mp)
+    yield mp, ctx, sdf
+    ctx.close()
+
+
+def _dev(*arrays):
+    import torch
+    return [torch.tensor(np.ascontiguousarray(a), dtype=torch.float64, device="cuda:0") for a in arrays]
+
+
+def _batch(B, m, mp, seed, shared_T=False):
+    b = problem.make_trajectories(B, m, mp, seed=seed, step_len=(0.05, 0.15) if m > 100 else ((0.5, 1.2) if m > 6 else (1.0, 2.0)),
+                                  boundary="random")
+    T = b.T[0].copy() if shared_T else b.T
+    return b, T
+
+
+def _gradient(gtop, ctx, b, T, **kw):
+    import torch
+    x, Df, Tt = _dev(b.x, b.Df.reshape(-1, 18), T)
+    c, g, p = gtop.time_gradient_device(ctx, x, Df, Tt, **kw)
+    torch.cuda.synchronize()
+    return c.cpu().numpy(), g.cpu().numpy(), None if p is None else p.cpu().numpy()
+
+
+def _against_twin(c, g, p, b, T, sdf, params, rows):
+    Tb = np.broadcast_to(T, (b.x.shape[0], b.m))
+    c_ref, g_ref, p_ref = tt.gradient_batch(Tb[rows], b.Df[rows], b.x[rows], sdf, params)
+    rc, rg = scenes.rel_err(c[rows], g[rows], c_ref, g_ref)
+    _, rp = scenes.rel_err(c[rows], p[rows], c_ref, p_ref)
+    return rc, rg, rp
+
+
+@pytest.mark.parametrize("B,m,shared_T,mode", [
+    (3, 2, False, "plain"), (65, 7, False, "plain"), (5, 13, False, "plain"), (2, 227, False, "plain"),
+    (130, 6, True, "plain"), (5, 13, False, "dyn"), (5, 13, False, "step1"), (5, 13, False, "signed"),
+    (65, 7, False, "dyn"), (5, 13, False, "dyn_ws0")])
+def test_gradient_against_the_evaluation_and_the_twin(gtop, oracle_mod, scene, B, m, shared_T, mode):
+    """(step1, signed and dyn_ws0 carry no smoothness term: there the collision and the dyn derivatives stand alone in
+    the max-norm the criterion divides by.)"""
+    import torch
+    mp, ctx, sdf = scene
+    if mode == "signed":
+        ctx, sdf = _field(gtop, oracle_mod, mp, signed=True)
+        assert ctx.field_sign()[0] and sdf.dist.min() < 0.0
+    extra = {"plain": {}, "signed": dict(ws=0.0), "dyn": DYN, "step1": dict(DYN, step=1), "dyn_ws0": dict(DYN, ws=0.0)}[mode]
+    params = dict(gtop.OPTI_NODE_PARAMS, **extra)
+    b, T = _batch(B, m, mp, 3100 + 17 * m + B, shared_T)
+    if mode == "signed":   # waypoint 1 of every row sits deep inside an obstacle, where the signed field is negative
+        deep = np.argwhere(sdf.dist.reshape(mp.grid) < -0.15)
+        assert len(deep) >= B
+        x = b.x.reshape(B, 3, -1).copy()
+        x[:, :, 0] = (deep[:: len(deep) // B][:B] + 0.5) * mp.resolution + mp.origin
+        b = problem.Batch(b.waypoints, b.T, b.Df, x.reshape(B, -1), m)
+        try:
+            scene[1].set_params(**extra)
+            c_unsigned, _, _ = _gradient(gtop, scene[1], b, T)
+        finally:
+            scene[1].set_params()
+    try:
+        ctx.set_params(**extra)
+        c, g, p = _gradient(gtop, ctx, b, T, want_parts=True)
+        ce, _ = ctx.eval_device(*_dev(b.x, b.Df.reshape(-1, 18), T))
+        torch.cuda.synchronize()
+    finally:
+        ctx.set_params()
+    ce = ce.cpu().numpy()
+    r_eval = float(np.max(np.abs(c - ce) / np.abs(ce)))
+    rows = np.arange(B) if B <= 6 else np.r_[0:3, B - 3:B]
+    rc, rg, rp = _against_twin(c, g, p, b, T, sdf, params, rows)
+    print(f"B={B} m={m} {mode}: cost against eval_device {r_eval:.2e}; against the twin cost {rc:.2e} gT {rg:.2e} parts {rp:.2e}")
+    assert r_eval <= TOL and rc <= TOL and rg <= TOL and rp <= TOL
+    assert np.all(np.isfinite(c)) and np.all(np.isfinite(g)) and np.all(np.isfinite(p))
+    assert np.array_equal(g, p[:, :, 2] + p[:, :, 3])
+    assert np.max(np.abs((p[:, :, 0].sum(1) + p[:, :, 1].sum(1) + 1e-3) - c) / c) <= 1e-12
+    if mode == "signed":
+        assert np.all(c > c_unsigned)          # the negative distances are read as they are: a larger penalty
+        ctx.close()
+
+
+def _special_rows(mp):
+    """Row 1 leaves the map (dist = -1, zero field gradient), row 2 has a segment of 0.02 s on the replay path."""
+    b, T = _batch(4, 5, mp, 4200)
+    T = T.copy()
+    x = b.x.reshape(4, 3, -1).copy()
+    x[1, 2, 3] = mp.origin[2] + mp.map_size[2] + 1.5            # waypoint 2 of row 1: z above the map
+    T[2, 2] = 0.02
+    return problem.Batch(b.waypoints, T, b.Df, x.reshape(4, -1), 5), T
+
+
+def test_out_of_map_and_replay_rows(gtop, scene):
+    import torch
+    mp, ctx, sdf = scene
+    b, T = _special_rows(mp)
+    c, g, p = _gradient(gtop, ctx, b, T, want_parts=True)
+    ce, _ = ctx.eval_device(*_dev(b.x, b.Df.reshape(-1, 18), T))
+    torch.cuda.synchronize()
+    assert np.max(np.abs(c - ce.cpu().numpy()) / np.abs(c)) <= TOL
+    rc, rg, rp = _against_twin(c, g, p, b, T, sdf, dict(gtop.OPTI_NODE_PARAMS), np.arange(4))
+    print(f"out-of-map and replay rows against the twin: cost {rc:.2e} gT {rg:.2e} parts {rp:.2e}")
+    assert rc <= TOL and rg <= TOL and rp <= TOL
+    # the replay segment counts 29 samples: the twin's loop does
+    n, t = 0, 1e-3
+    while t < 0.02:
+        n, t = n + 1, t + 0.02 / 30.0
+    assert n == 29
+
+
+def test_bit_level_laws(gtop, scene):
+    """One derivative under both gradient modes; a row's bits do not depend on the batch, its place or the time stride;
+    parts NULL changes nothing; a NaN row and a T = 0 row disturb only themselves; guard words stay."""
+    import torch
+    mp, ctx, sdf = scene
+    b, T = _special_rows(mp)
+    B, m = 4, 5
+    x, Df, Tt = _dev(b.x, b.Df.reshape(-1, 18), T)
+
+    def run(xx, dd, TT, parts=True):
+        Bq = xx.shape[0]
+        bufs = [torch.full((n + 16,), GUARD, dtype=torch.float64, device="cuda:0") for n in (Bq, Bq * m, Bq * m * 4)]
+        views = [bufs[0][8:8 + Bq], bufs[1][8:8 + Bq * m].view(Bq, m), bufs[2][8:8 + Bq * m * 4].view(Bq, m, 4)]
+        gtop.time_gradient_device(ctx, xx, dd, TT, cost=views[0], gT=views[1], parts=views[2] if parts else None)
+        torch.cuda.synchronize()
+        for buf in bufs:
+            assert torch.all(buf[:8] == GUARD) and torch.all(buf[-8:] == GUARD)
+        if not parts:
+            assert torch.all(bufs[2] == GUARD)
+        return [v.clone() for v in views]
+
+    base = run(x, Df, Tt)
+    assert not torch.any(base[0] == GUARD) and not torch.any(base[1] == GUARD) and not torch.any(base[2] == GUARD)
+    try:
+        ctx.set_gradient_mode(True)
+        cons = run(x, Df, Tt)
+    finally:
+        ctx.set_gradient_mode(False)
+    assert all(torch.equal(a, c) for a, c in zip(base, cons))
+    nop = run(x, Df, Tt, parts=False)
+    assert torch.equal(nop[0], base[0]) and torch.equal(nop[1], base[1])
+    # row 2 alone, first, last, in a batch of 130 — and with its times shared through stride 0
+    r = 2
+    alone = run(x[r:r + 1].contiguous(), Df[r:r + 1].contiguous(), Tt[r:r + 1].contiguous())
+    shared = run(x[r:r + 1].contiguous(), Df[r:r + 1].contiguous(), Tt[r].contiguous())
+    big, _ = _batch(130, m, mp, 4300)
+    for place in (0, 129, 77):
+        xb, Dfb, Tb = _dev(big.x, big.Df.reshape(-1, 18), big.T)
+        xb[place], Dfb[place], Tb[place] = x[r], Df[r], Tt[r]
+        got = run(xb, Dfb, Tb)
+        for k in range(3):
+            assert torch.equal(got[k][place], base[k][r]), (place, k)
+    for k in range(3):
+        assert torch.equal(alone[k][0], base[k][r]) and torch.equal(shared[k][0], base[k][r])
+    # a NaN row and a T = 0 row: the launch returns, the other rows keep their bits
+    xn, Tn = x.clone(), Tt.clone()
+    xn[3, 4] = float("nan")
+    Tn[0, 1] = 0.0
+    bad = run(xn, Df, Tn)
+    for k in range(3):
+        assert torch.equal(bad[k][1:3], base[k][1:3])
+
+
+OPT = dict(rho=2.0, t_min=0.1, t_max=4.0, first_move=0.05, ftol_rel=1e-7, xtol_abs=1e-10, max_evals=25)
+
+
+def _optimize(gtop, ctx, b, T, opts, T_lo=None):
+    import torch
+    x, Df, Tt = _dev(b.x, b.Df.reshape(-1, 18), T)
+    B, m = b.x.shape[0], b.m
+    bufs = [torch.full((n + 16,), GUARD, dtype=torch.float64, device="cuda:0") for n in (B * m, B * 8)]
+    T_out, info = bufs[0][8:8 + B * m].view(B, m), bufs[1][8:8 + B * 8].view(B, 8)
+    lo = None if T_lo is None else _dev(T_lo)[0]
+    gtop.optimize_times_device(ctx, gtop.GtopTimeOpt(**opts), x, Df, Tt, T_lo=lo, T_out=T_out, info=info)
+    torch.cuda.synchronize()
+    for buf in bufs:
+        assert torch.all(buf[:8] == GUARD) and torch.all(buf[-8:] == GUARD)
+    return T_out.clone(), info.clone()
+
+
+@pytest.mark.parametrize("B,m,shared_T", [(3, 2, False), (65, 7, False), (5, 13, False), (2, 227, False), (130, 6, True)])
+def test_optimizer_laws_on_collision_rows(gtop, scene, B, m, shared_T):
+    """F never rises, the bounds hold exactly with and without T_lo, info[5] is the gradient entry's cost at T_out bit
+    for bit, the host form gives the device form's bits, and the LIMITS reallocation's output composes as T_lo."""
+    import torch
+    mp, ctx, sdf = scene
+    b, T = _batch(B, m, mp, 5100 + m + B, shared_T)
+    opts = dict(OPT, t_min=0.0301 if m > 100 else 0.1)
+    x, Df, Tt = _dev(b.x, b.Df.reshape(-1, 18), T)
+    # T_lo: the LIMITS reallocation at limits the rows break (never faster than they allow), one column below t_min,
+    # one pinned above t_max
+    coeff = ctx.coefficients_device(x, Df, Tt)
+    seg = ctx.validate_segments_device(coeff, Tt, gtop.GtopLimits())
+    T_lim = ctx.reallocate_times_device(gtop.GtopRetime(mode=gtop.GtopRetime.LIMITS, max_vel=1.5, max_acc=2.0), T=Tt,
+                                        seg_report=seg)
+    torch.cuda.synchronize()
+    T_lo = T_lim.cpu().numpy().copy()
+    assert np.any(T_lo > np.broadcast_to(T, T_lo.shape))
+    T_lo[:, 0] = 0.01
+    T_lo[:, 1] = opts["t_max"] + 1.0
+    for lo in (None, T_lo):
+        T_out, info = _optimize(gtop, ctx, b, T, opts, lo)
+        To, io = T_out.cpu().numpy(), info.cpu().numpy()
+        assert np.all(np.isfinite(To)) and np.all(np.isfinite(io))
+        assert np.all(io[:, 4] <= io[:, 3])                                   # F_out <= F_in
+        assert np.all(np.isin(io[:, 0], (3, 4, 5))) and np.all(io[:, 2] >= 1) and np.all(io[:, 2] <= opts["max_evals"])
+        assert np.all(io[:, 1] <= io[:, 2] - 1) and np.all(io[:, 6] >= 0)
+        lob = np.full_like(To, opts["t_min"]) if lo is None else np.maximum(opts["t_min"], lo)
+        pinned = lob > opts["t_max"]
+        assert np.array_equal(To[pinned], lob[pinned])
+        assert np.all(To[~pinned] >= lob[~pinned]) and np.all(To[~pinned] <= opts["t_max"])
+        c, _, _ = gtop.time_gradient_device(ctx, x, Df, T_out)
+        torch.cuda.synchronize()
+        assert torch.equal(c, info[:, 5])                                      # bit for bit
+        assert np.max(np.abs(io[:, 4] - (io[:, 5] + opts["rho"] * To.sum(1))) / np.abs(io[:, 4])) <= 1e-13
+        assert np.max(np.abs(io[:, 7] - To.sum(1)) / To.sum(1)) <= 1e-14
+        assert np.any(io[:, 1] >= 1)                                           # something moved
+    # the host form: the same bits
+    ctx.set_problem(T, b.Df)
+    Bh = min(B, 9)
+    Th, ih = gtop.optimize_times(ctx, gtop.GtopTimeOpt(**opts), b.x[:Bh], T_lo[:Bh])
+    assert np.array_equal(Th, To[:Bh]) and np.array_equal(ih, io[:Bh])
+    ch, gh, ph = gtop.time_gradient_batch(ctx, b.x[:Bh])
+    cd, gd, pd = _gradient(gtop, ctx, b, T, want_parts=True)
+    assert np.array_equal(ch, cd[:Bh]) and np.array_equal(gh, gd[:Bh]) and np.array_equal(ph, pd[:Bh])
+
+
+def test_optimizer_follows_the_twin_without_a_collision_term(gtop, scene):
+    """wc = 0: no lookup can flip a decision — codes and evaluation counts are the twin's, T_out within 1e-9."""
+    mp, ctx, sdf = scene
+    b, T = _batch(6, 5, mp, 5300)
+    T_lo = np.tile(np.array([0.0, 0.0, 9.0, 0.0, 0.6]), (6, 1))
+    opts = dict(OPT, rho=1.0, t_max=5.0)
+    params = dict(gtop.OPTI_NODE_PARAMS, wc=0.0)
+    try:
+        ctx.set_params(wc=0.0)
+        T_out, info = _optimize(gtop, ctx, b, T, opts, T_lo)
+        T1, info1 = _optimize(gtop, ctx, b, T, dict(opts, max_evals=1), T_lo)
+    finally:
+        ctx.set_params()
+    To, io = T_out.cpu().numpy(), info.cpu().numpy()
+    for i in range(6):
+        T_ref, i_ref = tt.optimize_times(T[i], b.Df[i], b.x[i], None, params, T_lo=T_lo[i], **opts)
+        print(f"row {i}: code {int(io[i, 0])} after {int(io[i, 2])} evaluations, T_out off the twin's by "
+              f"{np.max(np.abs(To[i] - T_ref)):.2e}")
+        assert np.array_equal(io[i, :3], i_ref[:3]), (i, io[i], i_ref)
+        assert np.max(np.abs(To[i] - T_ref)) <= 1e-9
+        assert np.max(np.abs(io[i, 3:] - i_ref[3:]) / np.maximum(np.abs(i_ref[3:]), 1e-12)) <= 1e-6
+    # max_evals = 1: the clamped input, MAXEVAL
+    lo = np.maximum(opts["t_min"], T_lo)
+    clamped = np.where(lo > opts["t_max"], lo, np.clip(T, lo, opts["t_max"]))
+    assert np.array_equal(T1.cpu().numpy(), clamped)
+    i1 = info1.cpu().numpy()
+    assert np.all(i1[:, 0] == 5) and np.all(i1[:, 1] == 0) and np.all(i1[:, 2] == 1) and np.array_equal(i1[:, 3], i1[:, 4])
+
+
+def test_optimizer_stops_where_nothing_pulls(gtop, scene):
+    """Both weights 0 and rho = 0: every g is 0 — XTOL after one evaluation, the clamped input returned."""
+    mp, ctx, sdf = scene
+    b, T = _batch(3, 4, mp, 5400)
+    try:
+        ctx.set_params(ws=0.0, wc=0.0)
+        T_out, info = _optimize(gtop, ctx, b, T, dict(OPT, rho=0.0))
+    finally:
+        ctx.set_params()
+    io = info.cpu().numpy()
+    assert np.all(io[:, 0] == 4) and np.all(io[:, 2] == 1) and np.all(io[:, 1] == 0) and np.all(io[:, 6] == 0.0)
+    assert np.array_equal(T_out.cpu().numpy(), np.clip(T, OPT["t_min"], OPT["t_max"]))
+
+
+def test_optimizer_reaches_the_analytic_optimum(gtop, scene):
+    """tests/golden/TIME_ANALYTIC.md: T* = (3600 ws D^2 / rho)^(1/6), at the bound the document states."""
+    mp, ctx, sdf = scene
+    L, ws, rho = 3.0, 1.0, 2.0
+    Df, x, p = _rest_case(L, ws)
+    Tstar = (3600 * ws * (L / 2) ** 2 / rho) ** (1 / 6)
+    b = problem.Batch(None, None, np.stack([Df, Df]), np.stack([x, x]), 2)
+    T = np.array([[1.0, 3.0], [0.5, 0.5]])
+    try:
+        ctx.set_params(ws=ws, wc=0.0)
+        c, g, _ = _gradient(gtop, ctx, b, T)
+        T_out, info = _optimize(gtop, ctx, b, T, dict(rho=rho, t_min=0.05, t_max=60.0, first_move=0.1, ftol_rel=1e-9,
+                                                      xtol_abs=0.0, max_evals=60))
+    finally:
+        ctx.set_params()
+    g_ref = -3600 * ws * (L / 2) ** 2 / T ** 6
+    assert np.max(np.abs(g - g_ref) / np.abs(g_ref)) <= TOL
+    assert np.max(np.abs(c - ((720 * ws * (L / 2) ** 2 / T ** 5).sum(1) + 1e-3)) / c) <= TOL
+    err = np.max(np.abs(T_out.cpu().numpy() - Tstar), axis=1) / Tstar
+    print(f"T* = {Tstar:.9f}: reached within {err[0]:.2e} and {err[1]:.2e}, evaluations {info[:, 2].tolist()}")
+    assert np.all(err <= ANALYTIC_TOL) and np.all(info[:, 0].cpu().numpy() == 3)
+
+
+def test_one_captured_graph_replays_the_eager_bits(gtop, scene):
+    """time gradient -> optimize times -> gtop_optimize_device_ex on T_out, captured once."""
+    import torch
+    mp, ctx, sdf = scene
+    b, T = _batch(40, 6, mp, 5500)
+    lb, ub = gtop.GtopContext.default_bounds(b.waypoints)
+    x0, Df, Tt, lbt, ubt = _dev(b.x, b.Df.reshape(-1, 18), T, lb, ub)
+    opts = gtop.GtopTimeOpt(**OPT)
+    B, m = 40, 6
+    out = [torch.zeros(s, dtype=torch.float64, device="cuda:0") for s in ((B,), (B, m), (B, m), (B, 8))]
+
+    def cycle(xw):
+        gtop.time_gradient_device(ctx, xw, Df, Tt, cost=out[0], gT=out[1])
+        gtop.optimize_times_device(ctx, opts, xw, Df, Tt, T_out=out[2], info=out[3])
+        return ctx.optimize_device_ex(xw, Df, out[2], lbt, ubt, 12)
+
+    xe = x0.clone()
+    _, ce, ne, code_e = cycle(xe)
+    torch.cuda.synchronize()
+    want = [t.clone() for t in (*out, xe, ce, ne, code_e)]
+    assert not torch.equal(want[2], Tt)
+    for t in out:
+        t.zero_()
+    xg = x0.clone()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        _, cg, ng, code_g = cycle(xg)
+    for _ in range(2):
+        xg.copy_(x0)
+        graph.replay()
+        torch.cuda.synchronize()
+        got = (*out, xg, cg, ng, code_g)
+        for k, (a, w) in enumerate(zip(got, want)):
+            assert torch.equal(a, w), k
+
+
+def test_refusals_launch_nothing(gtop, scene):
+    import torch
+    from grad_traj_optimization_amd import timeopt as gt
+    mp, ctx, sdf = scene
+    L = gt.time_library()
+    b, T = _batch(3, 4, mp, 5600)
+    B, m = 3, 4
+    x, Df, Tt = _dev(b.x, b.Df.reshape(-1, 18), T)
+    outs = [torch.full((n,), GUARD, dtype=torch.float64, device="cuda:0") for n in (B, B * m, B * m * 4, B * m, B * 8)]
+    pc, pg, pp, pT, pi = (t.data_ptr() for t in outs)
+    px, pD, pTt = x.data_ptr(), Df.data_ptr(), Tt.data_ptr()
+    ok = gt.GtopTimeOpt(**OPT)
+
+    def grad(B=B, m=m, px=px, pD=pD, pT_=pTt, stride=m, pc=pc, pg=pg):
+        return L.gtop_time_gradient_device(ctx._h, B, m, px, pD, pT_, stride, pc, pg, pp, None)
+
+    def opt(o=ok, B=B, m=m, px=px, pD=pD, pT_=pTt, stride=m, plo=None, pout=pT, pinfo=pi):
+        return L.gtop_optimize_times_device(ctx._h, None if o is None else C.byref(o), B, m, px, pD, pT_, stride, plo, pout,
+                                            pinfo, None)
+
+    for rc in (grad(m=1), grad(m=228), grad(B=-1), grad(stride=3), grad(stride=1), grad(px=None), grad(pD=None),
+               grad(pT_=None), grad(pc=None), grad(pg=None),
+               opt(m=1), opt(m=228), opt(B=-1), opt(stride=2), opt(px=None), opt(pD=None), opt(pT_=None), opt(pout=None),
+               opt(pinfo=None), opt(o=None), opt(pout=pTt)):
+        assert rc == ERR_INVALID
+    for bad in (dict(reserved=1), dict(rho=-1.0), dict(rho=np.nan), dict(rho=np.inf), dict(t_min=0.03), dict(t_min=np.nan),
+                dict(t_min=5.0, t_max=4.0), dict(t_max=np.inf), dict(t_max=np.nan), dict(first_move=0.0),
+                dict(first_move=-1.0), dict(first_move=np.nan), dict(first_move=np.inf), dict(ftol_rel=-1e-3),
+                dict(ftol_rel=np.nan), dict(xtol_abs=-1.0), dict(xtol_abs=np.nan), dict(max_evals=0), dict(max_evals=-3)):
+        assert opt(o=gt.GtopTimeOpt(**dict(OPT, **bad))) == ERR_INVALID, bad
+        with pytest.raises(gtop.GtopError) as e:
+            gtop.optimize_times_device(ctx, gt.GtopTimeOpt(**dict(OPT, **bad)), x, Df, Tt)
+        assert e.value.code == ERR_INVALID
+    assert opt(o=gt.GtopTimeOpt(**dict(OPT, t_min=0.0301, t_max=0.0301))) == 0     # the limits themselves are legal
+    torch.cuda.synchronize()
+    outs[3].fill_(GUARD)
+    outs[4].fill_(GUARD)
+    assert grad(B=0) == 0 and opt(B=0) == 0
+    # the moving-obstacle cost switched on: GTOP_ERR_STATE from every entry, boxes or not
+    ctx.set_problem(T, b.Df)
+    try:
+        ctx.set_moving_cost(True)
+        assert grad() == ERR_STATE and opt() == ERR_STATE
+        for call in (lambda: gtop.time_gradient_batch(ctx, b.x), lambda: gtop.optimize_times(ctx, ok, b.x)):
+            with pytest.raises(gtop.GtopError) as e:
+                call()
+            assert e.value.code == ERR_STATE
+    finally:
+        ctx.set_moving_cost(False)
+    torch.cuda.synchronize()
+    assert all(bool(torch.all(t == GUARD)) for t in outs)
+    with pytest.raises(ValueError):
+        gtop.time_gradient_device(ctx, x, Df, Tt, gT=outs[0])
+    with pytest.raises(ValueError):
+        gtop.optimize_times_device(ctx, ok, x, Df, Tt, T_lo=outs[0])
+    assert grad() == 0 and opt() == 0                                             # and the context still serves
+    torch.cuda.synchronize()
