@@ -57,7 +57,7 @@ namespace {
 constexpr int kWaveMinw3From = 3072;   // batches that put a third wavefront on a SIMD (1 024 SIMDs)
 
 template <typename R, typename MM>
-using WaveKernelFn = void (*)(const R *, const R *, const R *, const R *, int, int, int, int, int, int,
+using WaveKernelFn = void (*)(const R *, const R *, const R *, int, int, int, int, int, unsigned, unsigned, const R *,
                               const GtopKernelArgs<R>, const GtopWaveConsts<R>, const MM, const GtopSetupConsts<R>);
 
 // one geometry: the collision-free, the ordinary and the DYN instantiation (DYN: one sample at a time, MINW >= 3)
@@ -196,13 +196,19 @@ static hipError_t launch_wave(const GtopKernelArgs<R> &args, const MM &st, const
     s.cost = wa.cost ? wa.cost + b0 : nullptr;
     s.grad = wa.grad ? wa.grad + (size_t)b0 * n : nullptr;
     const int groups = (s.B + plan.nt - 1) / plan.nt;
-    const int grid = 8 * ((groups + 7) / 8);   // the kernel deals its workgroups over 8 XCD-contiguous ranges
+    const int per_xcd = (groups + 7) / 8;
+    const int grid = 8 * per_xcd;   // the kernel deals its workgroups over 8 XCD-contiguous ranges
+    // what every wavefront would otherwise work out in front of its first load: the groups per XCD, the last group
+    // (the padding workgroups shadow it) and the bytes from one group's rows of x / T to the next's (the optimizer loop
+    // reads x from its state and Df, T as fp64 rows by its own indices: it does not use the strides)
+    const unsigned x_grp_bytes = (unsigned)((size_t)plan.nt * (size_t)n * sizeof(R));
+    const unsigned T_grp_bytes = (unsigned)((size_t)plan.nt * (size_t)wa.t_stride * sizeof(R));
     MM sst = st;
     if constexpr (MOV) {   // the slice's rows of the start times
       if (sst.mk.t0) sst.mk.t0 += (size_t)b0 * (size_t)sst.mk.t0_stride;
     }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * plan.nw), smem, stream, s.x, s.Df, s.T, s.sdf, s.B, s.m, s.t_stride, s.nx, s.ny,
-                       s.nz, s, GtopWaveConsts<R>{}, sst, GtopSetupConsts<R>{});
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * plan.nw), smem, stream, s.x, s.Df, s.T, s.B, s.m, s.t_stride, per_xcd,
+                       groups - 1, x_grp_bytes, T_grp_bytes, s.sdf, s, GtopWaveConsts<R>{}, sst, GtopSetupConsts<R>{});
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }

@@ -657,11 +657,13 @@ __device__ __forceinline__ void sample_pair_f32(const GtopKernelArgs<float> &a, 
 // COLLI = false is the |wc| < 1e-4 case (:346, no collision term), decided by the launcher: the kernel body is
 // then one basic block, in which the order the phases are written in can be held (scheduling barriers).
 //
-// Kernel arguments: what the first loads need (three input pointers, B, m, the time stride) and the field
-// descriptor come as leading scalar arguments, which the build preloads into SGPRs at wavefront launch
-// (-amdgpu-kernarg-preload-count, csrc/Makefile): measured with s_memtime stamps, a lone wavefront otherwise
-// waits ~1 100 cycles for its kernel-argument fetch before it can even request its inputs.  The rest of the
-// arguments (`a`; its x/Df/T/sdf/B/m/t_stride/nx/ny/nz fields are not read) arrive while the inputs do.
+// Kernel arguments: what the first loads need — three input pointers, B, m, the time stride, and what launch_wave has
+// worked out of them once per launch instead of every wavefront in front of its first load: the groups per XCD, the
+// last group's index and the byte strides of a group's rows of x and T — come as leading scalar arguments, which the
+// build preloads into SGPRs at wavefront launch (-amdgpu-kernarg-preload-count, csrc/Makefile): measured with
+// s_memtime stamps, a lone wavefront otherwise waits ~1 100 cycles for its kernel-argument fetch before it can even
+// request its inputs.  The rest of the arguments (the field pointer; `a`, whose x/Df/T/sdf/B/m/t_stride fields are
+// not read) arrive while the inputs do.
 // The fp64 constants of the closed forms that are neither inline operands (0.5, 1, 2, 4) nor VOP2 literals: as
 // literals each costs an s_mov pair in front of its use (43 of them, every one a 4-cycle issue slot of a lone
 // wavefront); as kernel arguments they arrive in SGPRs with the rest of the argument block.
@@ -789,10 +791,10 @@ constexpr int gtop_wave_budget() {
 template <typename R, bool WIDE, int SPL, int NT, bool COLLI, int MINW, typename MM = GtopNoMma, bool DYN = false,
           bool LONG = false, int NW = 1>
 __global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(gtop_wave_budget<R, WIDE, MM, SPL, MINW, DYN, LONG>())))
-gtop_eval_wave_kernel(const R *__restrict__ arg_x, const R *__restrict__ arg_Df, const R *__restrict__ arg_T,
-                      const R *__restrict__ arg_sdf, int arg_B, int arg_m, int arg_t_stride, int arg_nx, int arg_ny,
-                      int arg_nz, const GtopKernelArgs<R> arg_rest, const GtopWaveConsts<R> K, const MM st,
-                      const GtopSetupConsts<R> KD) {
+gtop_eval_wave_kernel(const R *__restrict__ arg_x, const R *__restrict__ arg_Df, const R *__restrict__ arg_T, int arg_B,
+                      int arg_m, int arg_t_stride, int arg_per_xcd, int arg_last_grp, unsigned arg_x_grp_bytes,
+                      unsigned arg_T_grp_bytes, const R *__restrict__ arg_sdf, const GtopKernelArgs<R> arg_rest,
+                      const GtopWaveConsts<R> K, const MM st, const GtopSetupConsts<R> KD) {
   constexpr bool MMA = kIsMma<MM>;
   constexpr bool MOV = kIsMov<MM>;
   constexpr bool CONS = kIsCons<MM>;
@@ -803,8 +805,7 @@ gtop_eval_wave_kernel(const R *__restrict__ arg_x, const R *__restrict__ arg_Df,
   using In = typename std::conditional<MMA, double, R>::type;
   GtopKernelArgs<R> a = arg_rest;
   a.x = arg_x; a.Df = arg_Df; a.T = arg_T; a.sdf = arg_sdf;
-  a.B = arg_B; a.m = arg_m; a.t_stride = arg_t_stride;
-  a.nx = arg_nx; a.ny = arg_ny; a.nz = arg_nz;
+  a.B = arg_B; a.m = arg_m; a.t_stride = arg_t_stride;   // (nx, ny, nz: arg_rest's own — not needed before the first corner address)
   constexpr int LPS = kSamples / SPL;   // lanes per segment
   constexpr int SPW = 64 / LPS;         // segment slots per wavefront
   constexpr int kStride = gtop_tile_stride(SPL, NW);   // (two wavefronts: 120 busy lanes)
@@ -829,8 +830,32 @@ gtop_eval_wave_kernel(const R *__restrict__ arg_x, const R *__restrict__ arg_Df,
   R *tile = reinterpret_cast<R *>(smem_raw);   // [19][kStride] (+ [kRounds*64] gradient for the optimizer update)
   GTOP_STAMP(0);
   GTOP_STAMP_HWID();
-  const int lane = NW == 2 ? (int)(threadIdx.x & 63u) : (int)threadIdx.x;
-  const int wave = NW == 2 ? (int)(threadIdx.x >> 6) : 0;   // which half of the trajectory's segments
+  GTOP_MARK(1);   // (region 0, in front of it: the kernel-argument fetch of the no-preload entry)
+  // The lone-wavefront fp64 bodies (one or two wavefronts per trajectory; every wait of theirs is in the open) touch
+  // every 64-byte line of their kernel-argument block with their first instructions: nine one-dword scalar loads
+  // whose values nobody reads.  The arguments beyond the preloaded ones are fetched by the compiler's scalar loads
+  // behind the input requests, in two batches — the second in the middle of the coefficient formation, waited for
+  // three instructions later — and a lone wavefront sat out both fetches; with the lines on their way since the
+  // entry those loads find them in the scalar cache (B = 1 024: 3.69 -> 3.63 us).  The workgroup
+  // and thread ids pass through the statement, so the index arithmetic cannot be scheduled in front of it; the
+  // dwords stay in their registers until the wait below retires them (the compiler does not count these loads).
+  constexpr bool kLone = COLLI && !kIsF32<R> && !WIDE && MINW <= 2 && SPL == 3 && !kIsMma<MM> && !LONG;
+  static_assert(!kLone || (64 + sizeof(GtopKernelArgs<R>) + sizeof(GtopWaveConsts<R>) > 0x200 &&
+                           64 + sizeof(GtopKernelArgs<R>) + sizeof(GtopWaveConsts<R>) <= 0x240),
+                "the entry touches the nine 64-byte lines of the kernel-argument block: leading arguments, a, K");
+  [[maybe_unused]] unsigned kpre[9];
+  unsigned wg_id = blockIdx.x, thr_id = threadIdx.x;
+  if constexpr (kLone) {
+    const auto kp = __builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("s_load_dword %0, %11, 0x0\n\ts_load_dword %1, %11, 0x40\n\ts_load_dword %2, %11, 0x80\n\t"
+                 "s_load_dword %3, %11, 0xc0\n\ts_load_dword %4, %11, 0x100\n\ts_load_dword %5, %11, 0x140\n\t"
+                 "s_load_dword %6, %11, 0x180\n\ts_load_dword %7, %11, 0x1c0\n\ts_load_dword %8, %11, 0x200"
+                 : "=&s"(kpre[0]), "=&s"(kpre[1]), "=&s"(kpre[2]), "=&s"(kpre[3]), "=&s"(kpre[4]), "=&s"(kpre[5]),
+                   "=&s"(kpre[6]), "=&s"(kpre[7]), "=&s"(kpre[8]), "+s"(wg_id), "+v"(thr_id)
+                 : "s"(kp));
+  }
+  const int lane = NW == 2 ? (int)(thr_id & 63u) : (int)thr_id;
+  const int wave = NW == 2 ? (int)(thr_id >> 6) : 0;   // which half of the trajectory's segments
   const int m = a.m, ndp = 3 * m - 3, n = 3 * ndp;
   if constexpr (LONG) __builtin_assume(m > SPW);
   else __builtin_assume(m >= 2 && NT * m <= NW * SPW);
@@ -843,15 +868,20 @@ gtop_eval_wave_kernel(const R *__restrict__ arg_x, const R *__restrict__ arg_Df,
 
   // XCD-aware order (workgroup id mod 8 = XCD): XCD x gets the x-th contiguous eighth of the batch
   const int nt = MANY ? SPW / m : NT;   // trajectories per wavefront
-  const int ngroups = (a.B + nt - 1) / nt;
-  const int per_xcd = (ngroups + 7) >> 3;
+  // (per_xcd = ceil(ngroups / 8) and last_grp = ngroups - 1, ngroups = ceil(B / nt): launch_wave's, the same for
+  // every wavefront of the launch)
+  const int per_xcd = arg_per_xcd, last_grp = arg_last_grp;
   // The grid is 8*per_xcd workgroups; the up to 7 beyond the batch take no early exit (a branch here would
   // split the kernel-argument loads into two dependent round trips): they shadow the last group with every
   // lane idle and every store predicated off.
-  const int grp_raw = ((int)blockIdx.x & 7) * per_xcd + ((int)blockIdx.x >> 3);
-  const bool grp_ok = grp_raw < ngroups;
-  const int grp = grp_ok ? grp_raw : ngroups - 1;
+  const int grp_raw = ((int)wg_id & 7) * per_xcd + ((int)wg_id >> 3);
+  const bool grp_ok = grp_raw <= last_grp;
+  const int grp = grp_ok ? grp_raw : last_grp;
   const int b0 = grp * nt;
+  // byte offsets of the group's first row of x and of T: one unsigned 32 x 32 -> 64-bit
+  // product each, the stride in bytes being launch_wave's (nt rows; below 2^32 by the launch rule's limits)
+  [[maybe_unused]] const uint64_t x_grp_off = (uint64_t)(uint32_t)grp * (uint64_t)arg_x_grp_bytes;
+  [[maybe_unused]] const uint64_t T_grp_off = (uint64_t)(uint32_t)grp * (uint64_t)arg_T_grp_bytes;
 
   const int slot_w = lane / LPS, li = lane - slot_w * LPS;   // segment slot within the wavefront, lane within the segment
   const int slot = wave * SPW + slot_w;
@@ -864,7 +894,9 @@ gtop_eval_wave_kernel(const R *__restrict__ arg_x, const R *__restrict__ arg_Df,
     tl = s >= m;
     s -= tl * m;
   }
-  bool seg_ok = grp_ok & (slot_w < SPW) & (slot < nt * m) & (b0 + tl < a.B);   // (LONG: set per chunk, below)
+  // (one trajectory per group: b0 = grp <= last_grp < B, nothing to test)
+  const bool row_ok = (NT == 1 && !MANY) ? true : (b0 + tl < a.B);
+  bool seg_ok = grp_ok & (slot_w < SPW) & (slot < nt * m) & row_ok;   // (LONG: set per chunk, below)
   if (!seg_ok) { tl = 0; s = 0; }   // idle lanes shadow the first segment: finite data, results never read
 
   unsigned long long t_launch = 0ull;
@@ -958,7 +990,7 @@ gtop_eval_wave_kernel(const R *__restrict__ arg_x, const R *__restrict__ arg_Df,
   }
   [[maybe_unused]] R cost_run = (R)0;   // LONG: this lane's share of the cost over its chunks
   constexpr int kRounds = (LONG || MANY) ? 1 : (NT * 9 * (NW * SPW / NT - 1) + 64 * NW - 1) / (64 * NW);
-  const int tid = NW == 2 ? (int)threadIdx.x : lane;
+  const int tid = NW == 2 ? (int)thr_id : lane;
   int offA[kRounds], offB[kRounds];     // (filled below, while the inputs are on their way)
   bool okq[kRounds];
   bool cost_lane = false;
@@ -981,9 +1013,10 @@ gtop_eval_wave_kernel(const R *__restrict__ arg_x, const R *__restrict__ arg_Df,
     dfb = mvl + kStateVecs * kMV;
     Tb = mvl + kStateVecs * kMV + kDfVals;
   } else {
-    xb = xsrc + (size_t)b0 * n + tl * n;      // this lane's trajectory (b0: wave-uniform)
-    dfb = a.Df + (size_t)b0 * 18 + tl * 18;
-    Tb = a.T + (size_t)b0 * a.t_stride + tl * a.t_stride;
+    // this lane's trajectory (the group's rows: wave-uniform, x_grp_off = b0 n and T_grp_off = b0 t_stride in bytes)
+    xb = reinterpret_cast<const R *>(reinterpret_cast<const char *>(xsrc) + x_grp_off) + tl * n;
+    dfb = a.Df + (size_t)(uint32_t)b0 * 18 + tl * 18;
+    Tb = reinterpret_cast<const R *>(reinterpret_cast<const char *>(a.T) + T_grp_off) + tl * a.t_stride;
   }
   const R T = (R)Tb[s];
   if constexpr (MOV) {
@@ -1001,19 +1034,40 @@ gtop_eval_wave_kernel(const R *__restrict__ arg_x, const R *__restrict__ arg_Df,
   // axis 0: the (p, v, a) triple at the segment's start and at its end; the other axes are one per-lane stride
   // further (6 within Df, 3m-3 within x: :182-187)
   const bool first = s == 0, last = s + 1 == m;
-  const In *p0 = first ? dfb : xb + 3 * (s - 1);
-  const In *p1 = last ? dfb + 3 : xb + 3 * s;
-  const int st0 = first ? 6 : ndp, st1 = last ? 6 : ndp;
   R w0[3][3], w1[3][3];
+  if constexpr (MMA) {   // (from LDS; the optimizer bodies have no register for another form)
+    const In *p0 = first ? dfb : xb + 3 * (s - 1);
+    const In *p1 = last ? dfb + 3 : xb + 3 * s;
+    const int st0 = first ? 6 : ndp, st1 = last ? 6 : ndp;
 #pragma unroll
-  for (int k = 0; k < 3; ++k) {
+    for (int k = 0; k < 3; ++k) {
 #pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      w0[k][i] = (R)p0[k * st0 + i];
-      w1[k][i] = (R)p1[k * st1 + i];
+      for (int i = 0; i < 3; ++i) {
+        w0[k][i] = (R)p0[k * st0 + i];
+        w1[k][i] = (R)p1[k * st1 + i];
+      }
+    }
+  } else {
+    // p0 = first ? dfb : xb + 3 (s - 1) and p1 = last ? dfb + 3 : xb + 3 s, both selected from the same two addresses —
+    // dfb + 3 and xb + 3 s, the start triple read three entries below its one — and walked axis by axis: less
+    // per-lane address arithmetic in front of the first load
+    const In *pm = xb + 3 * s, *dfe = dfb + 3;
+    const In *p0 = first ? dfe : pm;
+    const In *p1 = last ? dfe : pm;
+    const int st0 = first ? 6 : ndp, st1 = last ? 6 : ndp;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        w0[k][i] = (R)p0[i - 3];
+        w1[k][i] = (R)p1[i];
+      }
+      p0 += st0;
+      p1 += st1;
     }
   }
 
+  GTOP_MARK(2);
   // Where this lane's free variable(s) will be summed from at the very end (index arithmetic done here, while
   // the inputs are on their way): free variable = end of segment wpt-1 (entry 2 der + 1) + start of segment
   // wpt (entry 2 der)  (:425-432); tile[v][lane] holds entry v of lane's segment.
@@ -1025,7 +1079,7 @@ gtop_eval_wave_kernel(const R *__restrict__ arg_x, const R *__restrict__ arg_Df,
       tq = i >= n;
       i -= tq * n;
     }
-    okq[r] = grp_ok & (qi < NT * n) & (b0 + tq < a.B);
+    okq[r] = grp_ok & (qi < NT * n) & (NT == 1 || b0 + tq < a.B);
     const int axis = (i >= ndp) + (i >= 2 * ndp), c = i - axis * ndp;
     const int wpt = c / 3 + 1, der = c - 3 * (wpt - 1);   // interior waypoint 1..m-1
     const int rowB = axis * 6 + 2 * der;
@@ -1058,11 +1112,16 @@ gtop_eval_wave_kernel(const R *__restrict__ arg_x, const R *__restrict__ arg_Df,
     // the hand-issued loads hold all 12 corner pairs at once — 4.45 against 4.23 us
     expk.pin();
   }
+  GTOP_MARK(3);
 #if defined(GTOP_STAMPS) && GTOP_STAMPS != 2   // (the first / last stamp build adds no waits)
   GTOP_STAMP(2);   // inputs requested
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   GTOP_STAMP(3);   // inputs landed
 #endif
+  if constexpr (kLone)   // (the entry's nine dwords have landed: their registers are free from here)
+    asm volatile("s_waitcnt lgkmcnt(0) ; entry lines %0 %1 %2 %3 %4 %5 %6 %7 %8"
+                 : "+s"(kpre[0]), "+s"(kpre[1]), "+s"(kpre[2]), "+s"(kpre[3]), "+s"(kpre[4]), "+s"(kpre[5]), "+s"(kpre[6]),
+                   "+s"(kpre[7]), "+s"(kpre[8]));
   // ---- coefficients c = A_s^-1 d (closed form; rows of A_s: src/qp_generator.cpp:185-195) ----
   const R T2 = T * T;   // (for the A_s^-T at the end; the coefficients and the jerk term form their own powers)
   const R iT = fast_rcp(T), iT3 = iT * iT * iT, iT4 = iT3 * iT, iT5 = iT4 * iT;
@@ -1110,6 +1169,7 @@ gtop_eval_wave_kernel(const R *__restrict__ arg_x, const R *__restrict__ arg_Df,
 
   // ---- collision samples (:345-409); sample index = li + j*LPS ----
   if constexpr (COLLI) {
+    GTOP_MARK(4);
     // Sample times (:353): t_i = 1e-3 + i*dt; segments with T < 0.0301 (where the
     // sample COUNT depends on the accumulated value) replay the reference's addition chain.
     // Every term of a sample carries the factor alpha * wc * dt (cd of :509 times the weights of :373/:417);
@@ -1225,6 +1285,7 @@ gtop_eval_wave_kernel(const R *__restrict__ arg_x, const R *__restrict__ arg_Df,
 #pragma unroll kUnrollJ
     for (int j0 = 0; j0 < SPL; j0 += CH) {
       // stage A: positions, index arithmetic, corner loads
+      GTOP_MARK(5);
       R vels[CH][3];
       [[maybe_unused]] R accs[CH][3];
       SdfTap<R> taps[CH];
@@ -1292,6 +1353,7 @@ gtop_eval_wave_kernel(const R *__restrict__ arg_x, const R *__restrict__ arg_Df,
       }
       if (j0 == 0) GTOP_STAMP(4);   // corner loads issued
       if constexpr (CH == SPL || kLoadsFirst) GTOP_PHASE_FENCE();   // every corner load is issued above this line ...
+      GTOP_MARK(6);
       if constexpr (kLoadsFirst) {
         // ... one sample at a time: the velocity (and the speeds below) behind the loads.  Without the fence the
         // compiler, short of registers, loaded one record, waited, and only then loaded the other into the same
@@ -1325,6 +1387,7 @@ gtop_eval_wave_kernel(const R *__restrict__ arg_x, const R *__restrict__ arg_Df,
 #endif
       if constexpr (CH == SPL) GTOP_PHASE_FENCE();
       // stage B: trilinear blend, penalty, accumulation
+      GTOP_MARK(7);
 #pragma unroll
       for (int c = 0; c < CH; ++c) {
         if constexpr (ASMLD) {
@@ -1443,6 +1506,7 @@ gtop_eval_wave_kernel(const R *__restrict__ arg_x, const R *__restrict__ arg_Df,
   GTOP_STAMP(7);   // stage B done
 #endif
   // ---- A_s^-T on the lane's 18 accumulators: coefficient space -> [p0,pT,v0,vT,a0,aT] per axis ----
+  GTOP_MARK(8);
   R jT3 = iT3, jT4 = iT4, jT5 = iT5;
   if constexpr (MINW > 2) {   // (three registers fewer to carry across the samples)
     R iTb = iT;
@@ -1462,6 +1526,7 @@ gtop_eval_wave_kernel(const R *__restrict__ arg_x, const R *__restrict__ arg_Df,
     g[0] = o0; g[1] = ap; g[2] = o2; g[3] = o3; g[4] = o4; g[5] = o5;
   }
   // ---- the one LDS round trip: tile[v][lane], then each free variable (and each segment's cost) sums its entries ----
+  GTOP_MARK(9);
   if constexpr (LONG) {
     if (seg_ok) {   // this chunk's columns of the 5 m-column tile
       const int col = s * LPS + li;
@@ -1484,6 +1549,7 @@ gtop_eval_wave_kernel(const R *__restrict__ arg_x, const R *__restrict__ arg_Df,
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // writers and readers are this wavefront's own lanes,
     __builtin_amdgcn_wave_barrier();                          // whose LDS operations execute in order
   }
+  GTOP_MARK(11);
   R csum_seg = (R)0;
   R *gl = tile + kTileRows * tstride;   // [kRounds*64] (LONG: [kMV]): the gradient for the optimizer update (MMA only)
   if constexpr (LONG) {
@@ -1547,6 +1613,7 @@ gtop_eval_wave_kernel(const R *__restrict__ arg_x, const R *__restrict__ arg_Df,
   }
   // ---- cost (:417-418): every term is already weighted; lanes 48.. hold the segment sums ----
   {
+    GTOP_MARK(10);
     R cpart = cost_lane ? csum_seg : (R)0;
     cpart += gtop_dpp_move<0x111>(cpart);   // row_shr:1
     cpart += gtop_dpp_move<0x112>(cpart);   // row_shr:2
