@@ -34,8 +34,15 @@ from .timeopt import (TIME_ABI_VERSION, TIME_ENTRY_POINTS, TIME_PARTS, TIMEOPT_I
                       optimize_times, optimize_times_device, time_abi_version, time_gradient_batch,
                       time_gradient_device, time_library)
 from . import timeopt  # noqa: F401
+from .swarm import (SWARM_ABI_VERSION, SWARM_ENTRY_POINTS, GtopSwarmOpts, GtopSwarmStop, optimize_swarm,  # noqa: F401
+                    optimize_swarm_device, swarm_abi_version, swarm_gradient_batch, swarm_gradient_device,
+                    swarm_library, swarm_workspace_bytes)
+from . import swarm  # noqa: F401
 
-__all__ = ["TIME_ABI_VERSION", "TIME_ENTRY_POINTS", "TIME_PARTS", "TIMEOPT_INFO", "GtopTimeOpt", "timeopt",
+__all__ = ["SWARM_ABI_VERSION", "SWARM_ENTRY_POINTS", "GtopSwarmOpts", "GtopSwarmStop", "swarm", "optimize_swarm",
+           "optimize_swarm_device", "swarm_abi_version", "swarm_gradient_batch", "swarm_gradient_device",
+           "swarm_library", "swarm_workspace_bytes",
+           "TIME_ABI_VERSION", "TIME_ENTRY_POINTS", "TIME_PARTS", "TIMEOPT_INFO", "GtopTimeOpt", "timeopt",
            "optimize_times", "optimize_times_device", "time_abi_version", "time_gradient_batch", "time_gradient_device",
            "time_library",
 "PRED_ABI_VERSION", "PRED_ENTRY_POINTS", "PRED_INFO", "GtopPredictOpts", "prediction", "fit_predictions",

@@ -396,6 +396,99 @@ bool GradTrajOptimizer::optimizeSegmentTimes(const TimeOptConfig &config, TimeOp
   return true;
 }
 
+bool GradTrajOptimizer::swarmProblem(const std::vector<GradTrajOptimizer *> &robots, const SwarmOptions &options,
+                                     gtop_swarm_opts *opt, std::vector<double> *x) {
+  if (robots.empty() || !robots[0]) return false;
+  GradTrajOptimizer &lead = *robots[0];
+  const int m = lead.m_;
+  for (const GradTrajOptimizer *r : robots)
+    if (!r || !r->ctx_ || r->m_ < 2 || r->m_ != m || r->dp_.empty()) {
+      lead.last_status_ = GTOP_ERR_STATE;
+      return false;
+    }
+  *opt = gtop_swarm_opts{};
+  opt->t_lo = options.t_lo;
+  opt->dt = options.dt;
+  opt->w = options.w;
+  opt->radius = options.radius;
+  opt->n_samples = options.n_samples;
+  opt->hold_ends = options.hold_ends ? 1 : 0;
+  std::vector<double> T, Df;
+  x->clear();
+  for (const GradTrajOptimizer *r : robots) {
+    T.insert(T.end(), r->segment_time_.begin(), r->segment_time_.end());
+    Df.insert(Df.end(), r->df_.begin(), r->df_.end());
+    x->insert(x->end(), r->dp_.begin(), r->dp_.end());
+  }
+  lead.last_status_ = gtop_set_problem(lead.ctx_, (int)robots.size(), m, T.data(), m, Df.data());
+  return lead.last_status_ == GTOP_OK;
+}
+
+void GradTrajOptimizer::ownProblem() {
+  const int rc = gtop_set_problem(ctx_, 1, m_, segment_time_.data(), m_, df_.data());
+  if (last_status_ == GTOP_OK) last_status_ = rc;
+}
+
+bool GradTrajOptimizer::swarmGradient(const std::vector<GradTrajOptimizer *> &robots, const SwarmOptions &options,
+                                      std::vector<double> *S, std::vector<std::vector<double>> *grad,
+                                      std::vector<double> *active) {
+  gtop_swarm_opts opt;
+  std::vector<double> x;
+  if (!swarmProblem(robots, options, &opt, &x)) return false;
+  GradTrajOptimizer &lead = *robots[0];
+  const size_t B = robots.size(), n = lead.dp_.size();
+  std::vector<double> s(B), g(B * n), a(B);
+  lead.last_status_ = gtop_swarm_gradient_batch(lead.ctx_, &opt, (int)B, x.data(), nullptr, s.data(), g.data(), a.data());
+  lead.ownProblem();
+  if (lead.last_status_ != GTOP_OK) return false;
+  if (S) *S = s;
+  if (active) *active = a;
+  if (grad) {
+    grad->resize(B);
+    for (size_t b = 0; b < B; ++b) (*grad)[b].assign(g.begin() + b * n, g.begin() + (b + 1) * n);
+  }
+  return true;
+}
+
+bool GradTrajOptimizer::optimizeSwarm(const std::vector<GradTrajOptimizer *> &robots, const SwarmOptions &options,
+                                      std::vector<double> *min_cost, std::vector<std::array<double, 2>> *joint) {
+  gtop_swarm_opts opt;
+  std::vector<double> x;
+  if (!swarmProblem(robots, options, &opt, &x)) return false;
+  GradTrajOptimizer &lead = *robots[0];
+  const size_t B = robots.size(), n = lead.dp_.size();
+  gtop_swarm_stop stop{};
+  stop.sweeps = options.sweeps;
+  stop.evals_per_sweep = options.evals_per_sweep;
+  std::vector<double> lb(B * n), ub(B * n), mc(B), jt(2 * B);   // the bounds of optimizeTrajectory, :151-179
+  for (size_t b = 0; b < B; ++b) {
+    const GradTrajOptimizer &r = *robots[b];
+    for (int i = 0; i < r.num_dp_; ++i)
+      for (int a = 0; a < 3; ++a) {
+        const size_t j = b * n + (size_t)i + (size_t)a * r.num_dp_;
+        const double centre = i % 3 == 0 ? r.path_[(i / 3 + 1) * 3 + a] : 0.0;
+        const double half = i % 3 == 0 ? r.cfg_.bos : (i % 3 == 1 ? r.cfg_.vos : r.cfg_.aos);
+        lb[j] = centre - half;
+        ub[j] = centre + half;
+      }
+  }
+  gtop_set_optimizer_precision(lead.ctx_, GTOP_F64);
+  lead.last_status_ = gtop_optimize_swarm(lead.ctx_, &opt, &stop, (int)B, x.data(), lb.data(), ub.data(), mc.data(), jt.data());
+  lead.ownProblem();
+  if (lead.last_status_ != GTOP_OK) return false;
+  for (size_t b = 0; b < B; ++b) {
+    GradTrajOptimizer &r = *robots[b];
+    r.dp_.assign(x.begin() + b * n, x.begin() + (b + 1) * n);
+    r.coefficientsFromDerivatives(r.dp_);
+  }
+  if (min_cost) *min_cost = mc;
+  if (joint) {
+    joint->resize(B);
+    for (size_t b = 0; b < B; ++b) (*joint)[b] = {jt[2 * b], jt[2 * b + 1]};
+  }
+  return true;
+}
+
 bool GradTrajOptimizer::insertWaypoint(const InsertOptions &options, InsertInfo *info) {
   if (!ctx_ || m_ < 2 || dp_.empty()) {
     last_status_ = GTOP_ERR_STATE;

@@ -22,6 +22,7 @@
 #include "gtop.h"
 #include "gtop_kinematics.h"
 #include "gtop_prediction.h"
+#include "gtop_swarm.h"
 #include "gtop_time.h"
 
 #define OPT_INITIAL_TRY 0
@@ -270,6 +271,30 @@ class GradTrajOptimizer {
     double f_start = 0.0, f = 0.0, cost = 0.0, free_gradient = 0.0, time_sum = 0.0;
   };
   bool optimizeSegmentTimes(const TimeOptConfig &config, TimeOptInfo *info = nullptr);
+  // The robots of a swarm, one object each, planned against each other (include/gtop_swarm.h).  Their paths must have
+  // the same number of segments.  Both calls run on the FIRST object's context: its map, and the parameters its last
+  // optimizeTrajectory left in force; that context's problem is the swarm for the length of the call and the object's
+  // own again afterwards.  The start times are that context's.
+  struct SwarmOptions {
+    double t_lo = 0.0, dt = 0.05;   // the common grid tau_k = t_lo + k dt
+    int n_samples = 256;
+    double w = 1.0, radius = 1.0;   // the weight of the term and the radius of interaction
+    bool hold_ends = true;          // a robot stands at its start before and at its end after its flight
+    int sweeps = 4, evals_per_sweep = 25;   // optimizeSwarm's stop rules
+  };
+  // gtop_swarm_gradient_batch at every robot's current Dp: S[b], the penalty of robot b against the others, grad[b], its
+  // derivative with respect to robot b's Dp (axis-major), and (given) active[b], the number of active terms.  The swarm's
+  // total is sum(S) / 2.  false when the call fails.
+  static bool swarmGradient(const std::vector<GradTrajOptimizer *> &robots, const SwarmOptions &options,
+                            std::vector<double> *S, std::vector<std::vector<double>> *grad,
+                            std::vector<double> *active = nullptr);
+  // gtop_optimize_swarm from every robot's current Dp inside the bounds optimizeTrajectory uses: in every sweep each
+  // robot minimises its own cost plus its penalty against the plans the others had at the sweep's start.  The results
+  // become the objects' Dp and coefficients.  min_cost[b] (given): the last sweep's least cost + penalty; joint[b]
+  // (given): {the robot's own cost, its penalty with the others unfrozen} at the result.  false, and nothing changed,
+  // when the call fails.
+  static bool optimizeSwarm(const std::vector<GradTrajOptimizer *> &robots, const SwarmOptions &options,
+                            std::vector<double> *min_cost = nullptr, std::vector<std::array<double, 2>> *joint = nullptr);
 
   // extras (not in the reference)
   bool ok() const { return ctx_ != nullptr && last_status_ == GTOP_OK; }
@@ -283,6 +308,10 @@ class GradTrajOptimizer {
                     const std::vector<double> &Dx, const std::vector<double> &Dy, const std::vector<double> &Dz);
   void pushParams();
   void coefficientsFromDerivatives(const std::vector<double> &dp);        // :253-279
+  // the swarm as the first object's problem: the call's status (the first object's last_status_)
+  static bool swarmProblem(const std::vector<GradTrajOptimizer *> &robots, const SwarmOptions &options,
+                           gtop_swarm_opts *opt, std::vector<double> *x);
+  void ownProblem();   // this object's problem back on its context
 
   Config cfg_;
   gtop_ctx *ctx_ = nullptr;

@@ -238,9 +238,11 @@ int gtop_eval_device(gtop_ctx *c, int dtype, int B, int m, const void *d_x, cons
 // `stream` — one launch for the whole loop (fusion mode 2), one per round (1), or two
 // per round (0); no host synchronisation inside.
 // (problem_B: see moving_args — gtop_optimize_batch_ex runs the first B rows of the problem set)
+// (hook: gtop_ctx.h, GtopRoundHook — the two-launch form whatever the fusion knob says, the hook between its launches)
 static int optimize_device_impl(gtop_ctx *c, int B, int m, void *d_x, const void *d_Df, const void *d_T,
                                 int time_stride, const void *d_lb, const void *d_ub, const gtop_stop *stop, void *d_minf,
-                                int32_t *d_nevals, int32_t *d_code, void *hip_stream, int problem_B) try {
+                                int32_t *d_nevals, int32_t *d_code, void *hip_stream, int problem_B,
+                                const GtopRoundHook *hook = nullptr) try {
   if (!c) return GTOP_ERR_INVALID;
   int rc = check_eval_state(c);
   if (rc) return rc;
@@ -295,8 +297,8 @@ static int optimize_device_impl(gtop_ctx *c, int B, int m, void *d_x, const void
     return fail(c, GTOP_ERR_INVALID, "optimize: this many segments cannot be served (ten lanes per segment: up to 6; "
                                      "one wavefront's LDS with the optimizer's state: 118)");
   plan.consistent = c->grad_mode == GTOP_GRADIENT_CONSISTENT;   // (the separate-update form's evaluations take the plan too)
-  const bool fused = c->fuse_mma != 0;
-  const bool resident = c->fuse_mma == 2;   // one launch runs all max_evals evaluations of every trajectory
+  const bool fused = !hook && c->fuse_mma != 0;
+  const bool resident = !hook && c->fuse_mma == 2;   // one launch runs all max_evals evaluations of every trajectory
   st.iters = resident ? max_evals : 1;
   st.max_evals = max_evals;
   GtopKernelArgs<double> a =
@@ -338,6 +340,7 @@ static int optimize_device_impl(gtop_ctx *c, int B, int m, void *d_x, const void
       if ((rc = launch_eval<double>(c, a.sdf, B, m, st.xcur, d_Df, d_T, time_stride, a.cost, a.grad, s, &plan,
                                     problem_B)))   // the geometry the fused modes run: same bits
         return rc;
+      if (hook && (rc = hook->round(hook->user, c, st.xcur, c->mma_f.data(), c->mma_g.data(), s))) return rc;
       HIPCHK(c, gtop_launch_mma_update(st, B, (int)n, c->mma_f.data(), c->mma_g.data(), s));
     }
   }
@@ -352,6 +355,19 @@ int gtop_optimize_device_ex(gtop_ctx *c, int B, int m, void *d_x, const void *d_
                             int32_t *d_nevals, int32_t *d_code, void *hip_stream) {
   return optimize_device_impl(c, B, m, d_x, d_Df, d_T, time_stride, d_lb, d_ub, stop, d_minf, d_nevals, d_code, hip_stream, 0);
 }
+
+}  // extern "C"
+
+// (gtop_ctx.h)
+int gtop_optimize_rounds(gtop_ctx *c, int B, int m, void *d_x, const void *d_Df, const void *d_T, int time_stride,
+                         const void *d_lb, const void *d_ub, int evals, void *d_minf, void *hip_stream, int problem_B,
+                         const GtopRoundHook *hook) {
+  const gtop_stop stop = {evals, 0.0, 0.0, 0.0};
+  return optimize_device_impl(c, B, m, d_x, d_Df, d_T, time_stride, d_lb, d_ub, &stop, d_minf, nullptr, nullptr,
+                              hip_stream, problem_B, hook);
+}
+
+extern "C" {
 
 int gtop_optimize_device(gtop_ctx *c, int B, int m, void *d_x, const void *d_Df, const void *d_T,
                          int time_stride, const void *d_lb, const void *d_ub, int max_evals, void *d_minf,

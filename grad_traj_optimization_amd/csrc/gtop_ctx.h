@@ -13,6 +13,7 @@
 //   gtop_capi_separation_certificate.cpp  include/gtop_separation_certificate.h: the certificate of pairwise separation
 //   gtop_capi_prediction.cpp  include/gtop_prediction.h: predictions fitted from histories, the box list's refresh
 //   gtop_capi_time.cpp        include/gtop_time.h: the segment-time gradient, the optimizer of the time allocation
+//   gtop_capi_swarm.cpp       include/gtop_swarm.h: the swarm separation cost, its gradient, the swarm optimizer
 // Host-side only: they own device buffers, fill kernel arguments, launch.  There is deliberately no CPU code path:
 // without a gfx950 device every entry point fails (GTOP_ERR_NO_DEVICE).
 #ifndef GTOP_CTX_H_
@@ -129,6 +130,8 @@ struct gtop_ctx {
                                // gtop_insert_waypoints': when | lb | ub | x_out | T_out | lb_out | ub_out | info;
                                // gtop_time_gradient_batch's: cost | gT | parts; gtop_optimize_times': T_lo | T_out | info
   GtopDevBuf<double> sep_stage;  // gtop_separation_batch staging: pair_min | pair_max | rows | the launches' workspace
+  GtopDevBuf<double> swarm_stage;  // gtop_swarm_gradient_batch staging: the frozen rows' coefficients | S | grad | active |
+                                   // the launches' workspace; gtop_optimize_swarm's: joint | the workspace
   GtopDevBuf<double> sepcert_stage;  // gtop_certify_separation_batch staging: pairs | rows | the launches' workspace
   GtopDevBuf<double> d_q;      // host-API staging of gtop_edt_query: pos | time | dist | grad; gtop_trajectory_samples'
                                // sample scratch too
@@ -254,5 +257,21 @@ typedef int (*gtop_certificate_launch_fn)(gtop_ctx *c, int B, const void *job, d
 int gtop_certificate_host(gtop_ctx *c, const char *rows_text, int B, const double *x, bool given, const void *job,
                           gtop_certificate_ready_fn ready, gtop_certificate_launch_fn launch, int row_cols, double *rows,
                           int seg_cols, double *segs);
+
+
+// ---- the batched optimizer with a term of the caller's between its two launches (gtop_capi_eval.cpp) ----
+// Called once per round of the two-launch form, after the context's evaluation has written f [B] and grad [B][n] at the
+// trial points xcur [B][n] and before the MMA update reads them: it may enqueue launches on `stream` that ADD to f and
+// grad.  A status other than GTOP_OK ends the call with it.
+struct GtopRoundHook {
+  int (*round)(void *user, gtop_ctx *c, const double *d_xcur, double *d_f, double *d_grad, hipStream_t stream);
+  void *user;
+};
+// gtop_optimize_device_ex with {evals, 0, 0, 0} as its stop rules; with a hook it takes the two-launch form whatever
+// gtop_set_optimizer_fusion says (the context's state, mma_f and mma_g included, grows as for that call).  Without a
+// hook it enqueues exactly what gtop_optimize_device_ex enqueues.
+int gtop_optimize_rounds(gtop_ctx *c, int B, int m, void *d_x, const void *d_Df, const void *d_T, int time_stride,
+                         const void *d_lb, const void *d_ub, int evals, void *d_minf, void *hip_stream, int problem_B,
+                         const GtopRoundHook *hook);
 
 #endif  // GTOP_CTX_H_

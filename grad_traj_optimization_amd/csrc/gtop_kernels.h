@@ -346,4 +346,30 @@ hipError_t gtop_launch_time_optimize(const GtopGrid &g, const double *rec, const
                                      int max_evals, int B, int m, const double *x, const double *Df, const double *T,
                                      int t_stride, const double *T_lo, double *T_out, double *info, hipStream_t stream);
 
+// ---- swarm separation cost (gtop_swarm.hip), fp64 ----------------------------------------------------------------
+// the common grid of include/gtop_swarm.h's options
+struct GtopSwarmGrid {
+  double t_lo, dt;
+  int n_samples, hold_ends;
+};
+// the bytes of the workspace the launches below need for B rows of m segments on n_samples samples (its layout is the
+// kernels'), and the two regions of it the optimizer's entry uses itself: the coefficient scratch [B][m][18] of a round
+// and S [B] of the closing joint evaluation
+size_t gtop_swarm_work_bytes(int B, int m, int n_samples);
+double *gtop_swarm_coeff_scratch(void *work, int B, int m, int n_samples);
+double *gtop_swarm_joint_scratch(void *work, int B, int m, int n_samples);
+// the rows (coeff, T) sampled on the grid into side 0 (the trial rows) or 1 (the frozen rows) of the workspace; t0
+// (NULL: every start 0) with stride 0 or 1; one launch
+hipError_t gtop_launch_swarm_sample(const GtopSwarmGrid &g, int B, int m, const double *coeff, const double *T,
+                                    int t_stride, const double *t0, int t0_stride, int side, void *work,
+                                    hipStream_t stream);
+// S [B], grad [B][9 (m - 1)] and active [B] (may be NULL) of the trial rows sampled in side 0 against the rows of
+// partner_side (0: the batch itself) as include/gtop_swarm.h lays them out; add != 0: S and grad are ADDED to f and grad;
+// two launches (pairs, rows)
+hipError_t gtop_launch_swarm_terms(const GtopSwarmGrid &g, double w, double radius, int B, int m, const double *T,
+                                   int t_stride, const double *t0, int t0_stride, int partner_side, int add, double *f,
+                                   double *grad, double *active, void *work, hipStream_t stream);
+// joint [B][2] = cost [B] | S [B] (NULL: +0); one launch
+hipError_t gtop_launch_swarm_joint(int B, const double *cost, const double *S, double *joint, hipStream_t stream);
+
 #endif  // GTOP_KERNELS_H_

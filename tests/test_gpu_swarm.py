@@ -1,0 +1,459 @@
+"""The swarm separation cost on the device (include/gtop_swarm.h, csrc/gtop_swarm.hip) against its twin
+(tests/swarm_twin.py): S, the gradient and the active count bit for bit at the tile, chunk and padding edges of the
+kernels, joint and frozen; the invariances a row's figures must have; every refusal; the swarm optimizer against
+gtop_optimize_device_ex (w = 0), against the serial restatement (oracle/mma_twin.py on the oracle's cost plus the twin's
+frozen term), on three robots whose plans cross, and captured into a graph."""
+import numpy as np
+import pytest
+
+from grad_traj_optimization_amd import problem
+from oracle import mma_twin
+from tests import swarm_twin as sw
+
+pytestmark = pytest.mark.gpu
+
+ERR_INVALID, ERR_STATE = 1, 4
+
+
+def bits(a):
+    return np.ascontiguousarray(np.asarray(a, dtype=np.float64)).view(np.uint64)
+
+
+def same(a, b):
+    a, b = bits(a), bits(b)
+    return a.shape == b.shape and np.array_equal(a, b)
+
+
+@pytest.fixture(scope="module")
+def scene(gtop, oracle_mod):
+    mp = problem.make_map((60, 50, 30), density=0.03, seed=11)
+    ctx = gtop.GtopContext(device=0)
+    ctx.init_sdf_map(mp.map_size, mp.origin, mp.resolution)
+    ctx.update_sdf_map(mp.obstacle_points())
+    ctx.set_params()
+    sdf = oracle_mod.Sdf.from_map_size(mp.origin, mp.resolution, mp.map_size)
+    sdf.build_from_occupancy(mp.occupancy)
+    yield mp, ctx, sdf
+    ctx.close()
+
+
+@pytest.fixture(scope="module")
+def bare(gtop):
+    """A context without parameters and without a field: the gradient reads neither."""
+    ctx = gtop.GtopContext(device=0)
+    yield ctx
+    ctx.close()
+
+
+def dev(a, dtype=None):
+    import torch
+    return torch.tensor(np.ascontiguousarray(a), device="cuda:0", dtype=dtype)
+
+
+def device_rows(ctx, x, Df, T):
+    """The device's own coefficients of the rows: what the kernels and the twin both start from."""
+    import torch
+    coeff = ctx.coefficients_device(dev(x), dev(Df), dev(T))
+    torch.cuda.synchronize()
+    return coeff, coeff.cpu().numpy()
+
+
+def start_list(kind, B, seed):
+    if kind == 0:
+        return None
+    rng = np.random.default_rng(seed)
+    return rng.uniform(0.0, 0.5, 1 if kind == 1 else B)
+
+
+def grid_for(T, t0, n):
+    span = float(np.atleast_2d(T).sum(axis=1).max()) + (float(np.max(t0)) if t0 is not None else 0.0)
+    return 0.01, span / max(n - 1, 1) * 1.05
+
+
+# every B, m, n_samples, T form, start-time count and hold_ends of the issue; the three edges (a tile and a row more,
+# a chunk and a sample more, a padded last tile) meet in the cases with B = 65, n = 257
+CASES = [(1, 2, 1, False, 0, 0, False), (2, 3, 7, True, 1, 1, True), (3, 6, 8, False, "B", 0, False),
+         (63, 7, 9, False, 0, 1, True), (64, 2, 64, True, "B", 0, False), (65, 3, 257, False, 1, 0, True),
+         (65, 6, 257, True, "B", 1, False), (130, 6, 9, False, "B", 1, True), (130, 7, 64, True, 0, 0, False)]
+
+
+@pytest.mark.parametrize("B,m,n,shared,t0_kind,hold,frozen", CASES)
+def test_device_equals_twin_bit_for_bit(gtop, bare, B, m, n, shared, t0_kind, hold, frozen):
+    import torch
+    ctx = bare
+    x, Df, T = sw.crossing_rows(B, m, 1000 + B + m, shared_T=shared)
+    t0 = start_list(t0_kind, B, B + n)
+    t_lo, dt = grid_for(T, t0, n)
+    coeff, ch = device_rows(ctx, x, Df, T)
+    fz = fh = None
+    if frozen:
+        xf, _, _ = sw.crossing_rows(B, m, 2000 + B + m, shared_T=shared)
+        fz, fh = device_rows(ctx, xf, Df, T)
+    opts = gtop.GtopSwarmOpts(t_lo=t_lo, dt=dt, n_samples=n, w=3.0, radius=1.0, hold_ends=bool(hold))
+    ctx.set_start_times(t0)
+    try:
+        S, g, act = gtop.swarm_gradient_device(ctx, opts, coeff, dev(T), coeff_frozen=fz, want_active=True)
+        torch.cuda.synchronize()
+    finally:
+        ctx.set_start_times(None)
+    St, gt, at, _ = sw.swarm_terms(ch, T, t0, t_lo, dt, n, hold, 3.0, 1.0, frozen=fh)
+    if B > 2 and n > 1:
+        assert at.sum() > 0 and (at == 0).sum() < B      # the case has active terms
+    assert np.array_equal(act.cpu().numpy(), at.astype(np.float64))
+    assert same(S.cpu().numpy(), St), np.max(np.abs(S.cpu().numpy() - St))
+    assert same(g.cpu().numpy(), gt), np.max(np.abs(g.cpu().numpy() - gt))
+
+
+def test_the_analytic_case(gtop, bare):
+    import torch
+    from tests.test_swarm_twin import analytic_rows
+    c, T, o = analytic_rows()
+    opts = gtop.GtopSwarmOpts(t_lo=o["t_lo"], dt=o["dt"], n_samples=o["n"], w=o["w"], radius=o["radius"], hold_ends=False)
+    S, g, act = gtop.swarm_gradient_device(bare, opts, dev(c), dev(T), want_active=True)
+    torch.cuda.synchronize()
+    want = np.zeros((2, 9))
+    want[0, 3:6] = (6.75, 0.0, 0.4482421875)
+    want[1] = -want[0]
+    assert S.tolist() == [3.796875, 3.796875] and act.tolist() == [9.0, 9.0] and np.array_equal(g.cpu().numpy(), want)
+    # a pair at d2 == R2 exactly is not active
+    c = np.zeros((2, 2, 18))
+    c[1, :, 0], c[1, :, 6] = 3.0, 4.0
+    opts = gtop.GtopSwarmOpts(t_lo=0.0, dt=0.25, n_samples=9, w=1.0, radius=5.0)
+    S, g, act = gtop.swarm_gradient_device(bare, opts, dev(c), dev(np.array([1.0, 1.0])), want_active=True)
+    torch.cuda.synchronize()
+    assert S.tolist() == [0.0, 0.0] and act.tolist() == [0.0, 0.0] and not g.cpu().numpy().any()
+
+
+def test_invariances(gtop, scene):
+    import torch
+    mp, ctx, _ = scene
+    B, m, n = 40, 6, 64
+    x, Df, T = sw.crossing_rows(B, m, 31)
+    xf, _, _ = sw.crossing_rows(B, m, 32)
+    t_lo, dt = grid_for(T, None, n)
+    opts = gtop.GtopSwarmOpts(t_lo=t_lo, dt=dt, n_samples=n, w=2.0, radius=1.0, hold_ends=True)
+    coeff, ch = device_rows(ctx, x, Df, T)
+    fz, fh = device_rows(ctx, xf, Df, T)
+    Tt = dev(T)
+    base = {}
+    for name, f in (("joint", None), ("frozen", fz)):
+        out = gtop.swarm_gradient_device(ctx, opts, coeff, Tt, coeff_frozen=f, want_active=True)
+        again = gtop.swarm_gradient_device(ctx, opts, coeff, Tt, coeff_frozen=f, want_active=True)
+        torch.cuda.synchronize()
+        assert all(torch.equal(a, b) for a, b in zip(out, again))           # two runs are equal
+        assert out[2].sum().item() > 0
+        base[name] = [o.cpu().numpy() for o in out]
+    # rows further than R from everything appended (B crosses 64): the first rows keep their bits
+    far = np.zeros((30, m, 18))
+    far[:, :, 0] = 100.0 + 10.0 * np.arange(30)[:, None]
+    Tb = np.concatenate([T, np.full((30, m), 0.75)])
+    for name, f in (("joint", None), ("frozen", fh)):
+        ff = None if f is None else dev(np.concatenate([f, far + 5.0]))
+        out = gtop.swarm_gradient_device(ctx, opts, dev(np.concatenate([ch, far])), dev(Tb), coeff_frozen=ff, want_active=True)
+        torch.cuda.synchronize()
+        for o, b in zip(out, base[name]):
+            assert same(o.cpu().numpy()[:B], b), name
+        assert not out[0].cpu().numpy()[B:].any() and not out[2].cpu().numpy()[B:].any()
+    # the host form equals the device form
+    ctx.set_problem(T, Df.reshape(B, 3, 6))
+    for name, f in (("joint", None), ("frozen", xf)):
+        S, g, act = gtop.swarm_gradient_batch(ctx, opts, x, x_frozen=f)
+        assert same(S, base[name][0]) and same(g, base[name][1]) and same(act, base[name][2]), name
+    # guard words around every output and the workspace
+    need = gtop.swarm_workspace_bytes(B, m, n)
+    nvar = 9 * (m - 1)
+    G = 64
+    bufs = {k: torch.full((size + 2 * G,), -7.25, device="cuda:0", dtype=torch.float64)
+            for k, size in (("S", B), ("g", B * nvar), ("a", B))}
+    work = torch.full((need + 2 * G,), 0x5A, device="cuda:0", dtype=torch.uint8)
+    gtop.swarm_gradient_device(ctx, opts, coeff, Tt, coeff_frozen=fz, S=bufs["S"][G:G + B],
+                               grad=bufs["g"][G:G + B * nvar].view(B, nvar), active=bufs["a"][G:G + B],
+                               work=work[G:G + need])
+    torch.cuda.synchronize()
+    for k, size in (("S", B), ("g", B * nvar), ("a", B)):
+        assert (bufs[k][:G] == -7.25).all() and (bufs[k][G + size:] == -7.25).all(), k
+    assert (work[:G] == 0x5A).all() and (work[G + need:] == 0x5A).all()
+    assert same(bufs["S"][G:G + B].cpu().numpy(), base["frozen"][0])
+    assert same(bufs["g"][G:G + B * nvar].cpu().numpy().reshape(B, nvar), base["frozen"][1])
+    # a row of NaN coefficients is an absent row for every other row
+    r = 7
+    gone, nan = ch.copy(), ch.copy()
+    gone[r] = 0.0
+    gone[r, :, 0] = 1e3
+    nan[r] = np.nan
+    out = gtop.swarm_gradient_device(ctx, opts, dev(nan), Tt, want_active=True)
+    ref = gtop.swarm_gradient_device(ctx, opts, dev(gone), Tt, want_active=True)
+    torch.cuda.synchronize()
+    keep = np.arange(B) != r
+    changed = 0
+    for o, e, b in zip(out, ref, base["joint"]):
+        assert same(o.cpu().numpy()[keep], e.cpu().numpy()[keep])
+        changed += not same(e.cpu().numpy()[keep], b[keep])
+    assert changed and base["joint"][2][r] > 0       # the row did interact: the others' figures moved when it left
+
+
+def test_refusals_launch_nothing(gtop, scene, bare):
+    import torch
+    mp, ctx, _ = scene
+    B, m, n = 3, 3, 16
+    x, Df, T = sw.crossing_rows(B, m, 5)
+    coeff, _ = device_rows(ctx, x, Df, T)
+    Tt, Dft = dev(T), dev(Df)
+    lb, ub = dev(x - 1.0), dev(x + 1.0)
+    good = dict(t_lo=0.0, dt=0.1, n_samples=n, w=1.0, radius=1.0)
+    need = gtop.swarm_workspace_bytes(B, m, n)
+    work = torch.zeros(need, device="cuda:0", dtype=torch.uint8)
+    S = torch.full((B,), -3.5, device="cuda:0", dtype=torch.float64)
+    g = torch.full((B, 9 * (m - 1)), -3.5, device="cuda:0", dtype=torch.float64)
+    xs = dev(x)
+    mc = torch.full((B,), -3.5, device="cuda:0", dtype=torch.float64)
+
+    def untouched():
+        torch.cuda.synchronize()
+        return (S == -3.5).all() and (g == -3.5).all() and (mc == -3.5).all() and torch.equal(xs, dev(x)) \
+            and not work.any()
+
+    def grad_call(c=ctx, opts=None, coeff_=coeff, T_=Tt, work_=work, **kw):
+        o = opts if opts is not None else gtop.GtopSwarmOpts(**{**good, **kw})
+        gtop.swarm_gradient_device(c, o, coeff_, T_, S=S, grad=g, work=work_)
+
+    def opt_call(c=ctx, stop=None, opts=None, **kw):
+        o = opts if opts is not None else gtop.GtopSwarmOpts(**{**good, **kw})
+        gtop.optimize_swarm_device(c, o, stop or gtop.GtopSwarmStop(1, 2), xs, Dft, Tt, lb, ub, min_cost=mc, work=work)
+
+    bad_opts = [dict(t_lo=np.inf), dict(dt=0.0), dict(dt=-0.1), dict(dt=np.nan), dict(n_samples=0), dict(n_samples=65537),
+                dict(hold_ends=2), dict(reserved=(0, 1)), dict(reserved=(1, 0)), dict(w=-1.0), dict(w=np.inf),
+                dict(w=np.nan), dict(radius=0.0), dict(radius=-1.0), dict(radius=np.inf), dict(radius=np.nan)]
+    for call in (grad_call, opt_call):
+        for kw in bad_opts:
+            with pytest.raises(gtop.GtopError) as e:
+                call(**kw)
+            assert e.value.code == ERR_INVALID and untouched(), kw
+    L = gtop.swarm_library()
+    import ctypes as C
+    o = gtop.GtopSwarmOpts(**good)
+    p = coeff.data_ptr()
+    args = lambda **k: {**dict(B=B, m=m, coeff=p, T=Tt.data_ptr(), stride=m, S=S.data_ptr(), g=g.data_ptr(),  # noqa: E731
+                               work=work.data_ptr(), nwork=need), **k}
+
+    def raw_grad(opt=C.byref(o), **k):
+        a = args(**k)
+        return L.gtop_swarm_gradient_device(ctx._h, opt, a["B"], a["m"], a["coeff"], None, a["T"], a["stride"], a["S"],
+                                            a["g"], None, a["work"], a["nwork"], None)
+    for k in (dict(B=-1), dict(B=4097), dict(m=1), dict(m=228), dict(stride=1), dict(coeff=None), dict(T=None),
+              dict(S=None), dict(g=None), dict(work=None), dict(nwork=need - 1)):
+        assert raw_grad(**k) == ERR_INVALID and untouched(), k
+    assert raw_grad(opt=None) == ERR_INVALID and untouched()
+    assert raw_grad(B=0, coeff=None, S=None) == 0 and untouched()            # B = 0 launches nothing
+
+    s = gtop.GtopSwarmStop(1, 2)
+
+    def raw_opt(opt=C.byref(o), stop=C.byref(s), **k):
+        a = {**dict(B=B, m=m, x=xs.data_ptr(), Df=Dft.data_ptr(), T=Tt.data_ptr(), stride=m, lb=lb.data_ptr(),
+                    ub=ub.data_ptr(), mc=mc.data_ptr(), work=work.data_ptr(), nwork=need), **k}
+        return L.gtop_optimize_swarm_device(ctx._h, opt, stop, a["B"], a["m"], a["x"], a["Df"], a["T"], a["stride"],
+                                            a["lb"], a["ub"], a["mc"], None, a["work"], a["nwork"], None)
+    for k in (dict(B=-1), dict(B=4097), dict(m=1), dict(m=119), dict(m=228), dict(stride=2), dict(x=None), dict(Df=None),
+              dict(T=None), dict(lb=None), dict(ub=None), dict(mc=None), dict(work=None), dict(nwork=need - 1)):
+        assert raw_opt(**k) == ERR_INVALID and untouched(), k
+    assert raw_opt(opt=None) == ERR_INVALID and raw_opt(stop=None) == ERR_INVALID and untouched()
+    for st in (gtop.GtopSwarmStop(0, 2), gtop.GtopSwarmStop(1, 0), gtop.GtopSwarmStop(1, 2, (0, 1))):
+        assert raw_opt(stop=C.byref(st)) == ERR_INVALID and untouched()
+    assert raw_opt(B=0, x=None) == 0 and untouched()
+    # a start-time count that is neither 0, 1 nor B
+    ctx.set_start_times([0.0, 0.1])
+    try:
+        for call in (grad_call, opt_call):
+            with pytest.raises(gtop.GtopError) as e:
+                call()
+            assert e.value.code == ERR_INVALID and untouched()
+    finally:
+        ctx.set_start_times(None)
+    # the optimizer's states: no parameters / no field, fp32 evaluations, the moving-obstacle cost
+    with pytest.raises(gtop.GtopError) as e:
+        opt_call(c=bare)
+    assert e.value.code == ERR_STATE and untouched()
+    half = gtop.GtopContext(device=0)
+    try:
+        half.set_params()
+        with pytest.raises(gtop.GtopError) as e:
+            opt_call(c=half)
+        assert e.value.code == ERR_STATE and untouched()
+    finally:
+        half.close()
+    ctx.set_optimizer_precision("f32")
+    try:
+        with pytest.raises(gtop.GtopError) as e:
+            opt_call()
+        assert e.value.code == ERR_STATE and untouched()
+    finally:
+        ctx.set_optimizer_precision("f64")
+    ctx.set_moving_cost(True)
+    try:
+        with pytest.raises(gtop.GtopError) as e:
+            opt_call()
+        assert e.value.code == ERR_STATE and untouched()
+    finally:
+        ctx.set_moving_cost(False)
+    # and the good call goes through
+    grad_call()
+    opt_call()
+    torch.cuda.synchronize()
+    assert not (S == -3.5).any() and not (mc == -3.5).any()
+
+
+def test_w_zero_is_the_batched_optimizer(gtop, scene):
+    import torch
+    mp, ctx, _ = scene
+    B, m, evals = 70, 6, 15
+    b = problem.make_trajectories(B, m, mp, seed=41)
+    lb, ub = gtop.GtopContext.default_bounds(b.waypoints)
+    Df, T, lbt, ubt = dev(b.Df.reshape(-1, 18)), dev(b.T), dev(lb), dev(ub)
+    opts = gtop.GtopSwarmOpts(t_lo=0.0, dt=0.1, n_samples=32, w=0.0, radius=1.0)
+    try:
+        for mode in (0, 1, 2):
+            ctx.set_optimizer_fusion(mode)
+            xr, cr, _, _ = ctx.optimize_device_ex(dev(b.x), Df, T, lbt, ubt, evals)
+            xs, cs, joint = gtop.optimize_swarm_device(ctx, opts, gtop.GtopSwarmStop(1, evals), dev(b.x), Df, T, lbt, ubt,
+                                                       want_joint=True)
+            torch.cuda.synchronize()
+            assert torch.equal(xs, xr) and torch.equal(cs, cr), mode
+            assert not joint[:, 1].any() and (joint[:, 0] > 0).all()
+    finally:
+        ctx.set_optimizer_fusion(2)
+
+
+@pytest.mark.parametrize("m", [3, 6])
+def test_optimizer_follows_the_serial_restatement(gtop, scene, oracle_mod, m):
+    mp, ctx, sdf = scene
+    B, sweeps, evals, n = 4, 2, 12, 48
+    w, radius = 40.0, 1.5
+    b = problem.make_trajectories(B, m, mp, seed=50 + m)
+    # the four robots brought together: every path shifted so that its middle lies near the map's centre
+    centre = np.array(mp.origin) + 0.5 * np.array(mp.map_size)
+    rng = np.random.default_rng(m)
+    wp = b.waypoints - b.waypoints.mean(axis=1, keepdims=True) + centre + rng.uniform(-0.3, 0.3, (B, 1, 3))
+    T = problem.segment_times(wp)
+    Df, Dp = problem.initial_derivatives(wp)
+    x0 = Dp.reshape(B, -1) + rng.normal(0.0, 0.05, (B, 9 * (m - 1)))
+    Df2 = Df.reshape(B, 18)
+    lb, ub = gtop.GtopContext.default_bounds(wp)
+    t_lo, dt = 0.0, float(np.max(T.sum(axis=1))) / (n - 1)
+    opts = gtop.GtopSwarmOpts(t_lo=t_lo, dt=dt, n_samples=n, w=w, radius=radius, hold_ends=True)
+    ctx.set_problem(T, Df)
+    xs, costs, joint = gtop.optimize_swarm(ctx, opts, gtop.GtopSwarmStop(sweeps, evals), x0, lb, ub)
+    prm = oracle_mod.make_params()
+    x = x0.copy()
+    seen_active = 0
+    for sweep in range(sweeps):
+        frozen = sw.coefficients(x, Df2, T)
+        nxt, minf, f_start = x.copy(), np.zeros(B), np.zeros(B)
+        for i in range(B):
+            gen = oracle_mod.generator(T[i])
+
+            def f(xi, i=i, gen=gen):
+                c, g = oracle_mod.cost_grad(T[i], Df[i], xi, sdf, prm, L=gen["L"], R=gen["R"])
+                trial = frozen.copy()
+                trial[i] = sw.coefficients(xi[None], Df2[i:i + 1], T[i:i + 1])[0]
+                S, gs, act, _ = sw.swarm_terms(trial, T, None, t_lo, dt, n, 1, w, radius, frozen=frozen)
+                f.active += int(act[i])
+                return c + S[i], g + gs[i]
+            f.active = 0
+            res = mma_twin.minimize(f, x[i], lb[i], ub[i], evals)
+            nxt[i], minf[i], f_start[i] = res["x"], res["minf"], res["fs"][0]
+            seen_active += f.active
+        x = nxt
+    assert seen_active > 0                                                   # the term took part
+    for i in range(B):
+        assert abs(costs[i] - minf[i]) <= 1e-6 * abs(minf[i]), (i, costs[i], minf[i])
+        assert np.max(np.abs(xs[i] - x[i])) <= 1e-6 * max(1.0, np.max(np.abs(x[i]))), i
+        assert np.all(xs[i] >= lb[i] - 1e-12) and np.all(xs[i] <= ub[i] + 1e-12)
+        assert costs[i] <= f_start[i] * (1 + 1e-6)                           # never worse than the last sweep's start
+
+
+def crossing_robots(mp):
+    """Three robots whose straight-line plans pass the map's centre at the same time, with lateral offsets so that no
+    pair is collinear: (waypoints (3, 4, 3))."""
+    c = np.array(mp.origin) + 0.5 * np.array(mp.map_size)
+    wp = np.zeros((3, 4, 3))
+    for r, (ang, off) in enumerate(((0.0, (0.0, 0.15, 0.0)), (2.1, (0.1, -0.1, 0.2)), (4.2, (-0.15, 0.0, -0.2)))):
+        d = np.array([np.cos(ang), np.sin(ang), 0.0])
+        for k, s in enumerate((-3.0, -1.0, 1.0, 3.0)):
+            wp[r, k] = c + s * d + np.array(off)
+    return wp
+
+
+def test_crossing_robots_are_moved_apart(gtop, scene):
+    import torch
+    mp, ctx, _ = scene
+    wp = crossing_robots(mp)
+    B, m, n = 3, 3, 96
+    T = np.tile(problem.segment_times(wp[:1]), (B, 1))                      # the same clock: they meet at the centre
+    Df, Dp = problem.initial_derivatives(wp)
+    x0 = Dp.reshape(B, -1)
+    lb, ub = gtop.GtopContext.default_bounds(wp)
+    dt = float(T[0].sum()) / (n - 1)
+    radius = 1.2
+    opts = gtop.GtopSwarmOpts(t_lo=0.0, dt=dt, n_samples=n, w=200.0, radius=radius, hold_ends=True)
+    S0, _, act0, _ = sw.swarm_terms(sw.coefficients(x0, Df.reshape(B, 18), T), T, None, 0.0, dt, n, 1, 200.0, radius)
+    assert act0.min() > 0                                                    # they do come within R at the start
+    Dft, Tt, lbt, ubt = dev(Df.reshape(B, 18)), dev(T), dev(lb), dev(ub)
+    sep = gtop.GtopSepOpts(t_lo=0.0, dt=dt, n_samples=n, radius=radius, hold_ends=True)
+    stop = gtop.GtopSwarmStop(4, 20)
+    res = {}
+    for name, w in (("swarm", 200.0), ("alone", 0.0)):
+        o = gtop.GtopSwarmOpts(t_lo=0.0, dt=dt, n_samples=n, w=w, radius=radius, hold_ends=True)
+        xs, mc, joint = gtop.optimize_swarm_device(ctx, o, stop, dev(x0), Dft, Tt, lbt, ubt, want_joint=True)
+        coeff = ctx.coefficients_device(xs, Dft, Tt)
+        _, _, rows = gtop.separation_device(ctx, coeff, Tt, sep)
+        S, _, _ = gtop.swarm_gradient_device(ctx, opts, coeff, Tt)
+        torch.cuda.synchronize()
+        res[name] = (xs, joint, coeff, rows[:, 0].min().item(), S.cpu().numpy())
+    xs, joint, coeff, least, S = res["swarm"]
+    assert 0.5 * S.sum() < 0.5 * float(S0.sum())
+    assert least > res["alone"][3]
+    assert (xs.cpu().numpy() >= lb).all() and (xs.cpu().numpy() <= ub).all()
+    # the closing joint evaluation is the two calls made separately at the returned x
+    cost, _ = ctx.eval_device(xs, Dft, Tt)
+    torch.cuda.synchronize()
+    assert same(joint[:, 0].cpu().numpy(), cost.cpu().numpy()) and same(joint[:, 1].cpu().numpy(), S)
+
+
+def test_the_optimizer_call_is_capturable(gtop, scene):
+    import torch
+    mp, ctx, _ = scene
+    wp = crossing_robots(mp)
+    B, m, n = 3, 3, 64
+    T = np.tile(problem.segment_times(wp[:1]), (B, 1))
+    Df, Dp = problem.initial_derivatives(wp)
+    x0 = dev(Dp.reshape(B, -1))
+    lb, ub = gtop.GtopContext.default_bounds(wp)
+    Dft, Tt, lbt, ubt = dev(Df.reshape(B, 18)), dev(T), dev(lb), dev(ub)
+    opts = gtop.GtopSwarmOpts(t_lo=0.0, dt=float(T[0].sum()) / (n - 1), n_samples=n, w=150.0, radius=1.2, hold_ends=True)
+    stop = gtop.GtopSwarmStop(2, 6)
+    work = torch.zeros(gtop.swarm_workspace_bytes(B, m, n), device="cuda:0", dtype=torch.uint8)
+    xg, mc, joint = x0.clone(), torch.zeros(B, device="cuda:0", dtype=torch.float64), \
+        torch.zeros((B, 2), device="cuda:0", dtype=torch.float64)
+
+    def run():
+        gtop.optimize_swarm_device(ctx, opts, stop, xg, Dft, Tt, lbt, ubt, min_cost=mc, joint=joint, work=work)
+
+    run()                                                                   # warm up: the context's state grows here
+    torch.cuda.synchronize()
+    want = (xg.clone(), mc.clone(), joint.clone())
+    assert not torch.equal(want[0], x0)
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    graph = torch.cuda.CUDAGraph()
+    xg.copy_(x0)
+    torch.cuda.synchronize()
+    with torch.cuda.graph(graph, stream=side):
+        run()
+    for _ in range(2):
+        xg.copy_(x0)
+        mc.zero_()
+        joint.zero_()
+        graph.replay()
+        torch.cuda.synchronize()
+        for k, (a, e) in enumerate(zip((xg, mc, joint), want)):
+            assert torch.equal(a, e), k
