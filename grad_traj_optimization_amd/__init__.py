@@ -34,6 +34,10 @@ from .timeopt import (TIME_ABI_VERSION, TIME_ENTRY_POINTS, TIME_PARTS, TIMEOPT_I
                       optimize_times, optimize_times_device, time_abi_version, time_gradient_batch,
                       time_gradient_device, time_library)
 from . import timeopt  # noqa: F401
+from .timeopt_moving import (TIME_MOVING_ABI_VERSION, TIME_MOVING_ENTRY_POINTS, TIME_MOVING_PARTS,  # noqa: F401
+                             optimize_times_moving, optimize_times_moving_device, time_gradient_moving_batch,
+                             time_gradient_moving_device, time_moving_abi_version, time_moving_library)
+from . import timeopt_moving  # noqa: F401
 from .swarm import (SWARM_ABI_VERSION, SWARM_ENTRY_POINTS, GtopSwarmOpts, GtopSwarmStop, optimize_swarm,  # noqa: F401
                     optimize_swarm_device, swarm_abi_version, swarm_gradient_batch, swarm_gradient_device,
                     swarm_library, swarm_workspace_bytes)
@@ -45,6 +49,9 @@ __all__ = ["SWARM_ABI_VERSION", "SWARM_ENTRY_POINTS", "GtopSwarmOpts", "GtopSwar
            "TIME_ABI_VERSION", "TIME_ENTRY_POINTS", "TIME_PARTS", "TIMEOPT_INFO", "GtopTimeOpt", "timeopt",
            "optimize_times", "optimize_times_device", "time_abi_version", "time_gradient_batch", "time_gradient_device",
            "time_library",
+           "TIME_MOVING_ABI_VERSION", "TIME_MOVING_ENTRY_POINTS", "TIME_MOVING_PARTS", "timeopt_moving",
+           "optimize_times_moving", "optimize_times_moving_device", "time_gradient_moving_batch",
+           "time_gradient_moving_device", "time_moving_abi_version", "time_moving_library",
 "PRED_ABI_VERSION", "PRED_ENTRY_POINTS", "PRED_INFO", "GtopPredictOpts", "prediction", "fit_predictions",
            "fit_predictions_device", "pred_abi_version", "pred_library", "refresh_box_predictions_device",
 "SEPCERT_ABI_VERSION", "SEPCERT_ENTRY_POINTS", "SEPCERT_PAIR", "SEPCERT_ROW", "GtopSepCertOpts",

@@ -345,7 +345,36 @@ bool GradTrajOptimizer::timeGradient(double *cost, std::vector<double> *gT, std:
   return true;
 }
 
+bool GradTrajOptimizer::timeGradientMoving(double *cost, std::vector<double> *gT, double *gt0,
+                                           std::vector<std::array<double, 6>> *parts) {
+  if (!ctx_ || m_ < 2 || dp_.empty()) {
+    last_status_ = GTOP_ERR_STATE;
+    return false;
+  }
+  double c = 0.0, g0 = 0.0;
+  std::vector<double> g(m_), p(parts ? (size_t)m_ * GTOP_TIME_MOVING_PARTS : 0);
+  last_status_ = gtop_time_gradient_moving_batch(ctx_, 1, dp_.data(), &c, g.data(), &g0, parts ? p.data() : nullptr);
+  if (last_status_ != GTOP_OK) return false;
+  if (cost) *cost = c;
+  if (gT) *gT = g;
+  if (gt0) *gt0 = g0;
+  if (parts) {
+    parts->resize(m_);
+    for (int s = 0; s < m_; ++s)
+      for (int k = 0; k < GTOP_TIME_MOVING_PARTS; ++k) (*parts)[s][k] = p[(size_t)s * GTOP_TIME_MOVING_PARTS + k];
+  }
+  return true;
+}
+
 bool GradTrajOptimizer::optimizeSegmentTimes(const TimeOptConfig &config, TimeOptInfo *info) {
+  return optimizeSegmentTimesWith(config, info, false);
+}
+
+bool GradTrajOptimizer::optimizeSegmentTimesMoving(const TimeOptConfig &config, TimeOptInfo *info) {
+  return optimizeSegmentTimesWith(config, info, true);
+}
+
+bool GradTrajOptimizer::optimizeSegmentTimesWith(const TimeOptConfig &config, TimeOptInfo *info, bool moving) {
   if (!ctx_ || m_ < 2 || dp_.empty()) {
     last_status_ = GTOP_ERR_STATE;
     return false;
@@ -377,7 +406,8 @@ bool GradTrajOptimizer::optimizeSegmentTimes(const TimeOptConfig &config, TimeOp
   }
   std::vector<double> T(m_);
   double r[GTOP_TIMEOPT_INFO];
-  last_status_ = gtop_optimize_times(ctx_, &opt, 1, dp_.data(), lo.empty() ? nullptr : lo.data(), T.data(), r);
+  last_status_ = (moving ? gtop_optimize_times_moving : gtop_optimize_times)(ctx_, &opt, 1, dp_.data(),
+                                                                             lo.empty() ? nullptr : lo.data(), T.data(), r);
   if (last_status_ != GTOP_OK) return false;
   last_status_ = gtop_set_problem(ctx_, 1, m_, T.data(), m_, df_.data());   // (refuses a time that is not > 0)
   if (last_status_ != GTOP_OK) return false;

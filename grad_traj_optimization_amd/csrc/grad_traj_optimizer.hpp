@@ -24,6 +24,7 @@
 #include "gtop_prediction.h"
 #include "gtop_swarm.h"
 #include "gtop_time.h"
+#include "gtop_time_moving.h"
 
 #define OPT_INITIAL_TRY 0
 #define OPT_FIRST_STEP 1
@@ -271,6 +272,15 @@ class GradTrajOptimizer {
     double f_start = 0.0, f = 0.0, cost = 0.0, free_gradient = 0.0, time_sum = 0.0;
   };
   bool optimizeSegmentTimes(const TimeOptConfig &config, TimeOptInfo *info = nullptr);
+  // The two calls above under the moving-obstacle cost (include/gtop_time_moving.h, gtop_time_gradient_moving_batch
+  // and gtop_optimize_times_moving), which the two above refuse while setMovingObstacles / setMovingObstaclePredictions
+  // have the mode on: the cost and its derivative see the boxes at setStartTime's clock, where a segment time moves
+  // the lookups of every later segment.  gt0 (given): d cost / d start time.  parts: the four columns of timeGradient,
+  // then q_s (what the segment's cost gains per second of delay of its start) and the sum of q over the later
+  // segments.  Without boxes they give what the two above give.
+  bool timeGradientMoving(double *cost, std::vector<double> *gT, double *gt0 = nullptr,
+                          std::vector<std::array<double, 6>> *parts = nullptr);
+  bool optimizeSegmentTimesMoving(const TimeOptConfig &config, TimeOptInfo *info = nullptr);
   // The robots of a swarm, one object each, planned against each other (include/gtop_swarm.h).  Their paths must have
   // the same number of segments.  Both calls run on the FIRST object's context: its map, and the parameters its last
   // optimizeTrajectory left in force; that context's problem is the swarm for the length of the call and the object's
@@ -312,6 +322,8 @@ class GradTrajOptimizer {
   static bool swarmProblem(const std::vector<GradTrajOptimizer *> &robots, const SwarmOptions &options,
                            gtop_swarm_opts *opt, std::vector<double> *x);
   void ownProblem();   // this object's problem back on its context
+  // optimizeSegmentTimes (gtop_optimize_times) or, moving, optimizeSegmentTimesMoving (gtop_optimize_times_moving)
+  bool optimizeSegmentTimesWith(const TimeOptConfig &config, TimeOptInfo *info, bool moving);
 
   Config cfg_;
   gtop_ctx *ctx_ = nullptr;

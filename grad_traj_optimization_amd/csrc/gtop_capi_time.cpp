@@ -3,16 +3,12 @@
 // allocation, no synchronisation: capturable) and a host form over the problem set.
 #include <cmath>
 
-#include "gtop_ctx.h"
-#include "gtop_time.h"
+#include "gtop_capi_time.h"
 
-namespace {
-
-// what both device forms ask of the context and of a call of B rows of m segments, before anything is launched
-int time_ready(gtop_ctx *c, const char *who, int B, int m, int time_stride) {
+int gtop_time_ready(gtop_ctx *c, const char *who, int B, int m, int time_stride, bool refuse_moving) {
   if (!c->have_params) return fail(c, GTOP_ERR_STATE, "gtop_set_params has not been called");
   if (!c->field.have_grid) return fail(c, GTOP_ERR_STATE, "no distance field set");
-  if (c->moving_cost != 0)
+  if (refuse_moving && c->moving_cost != 0)
     return fail(c, GTOP_ERR_STATE, std::string(who) + ": the moving-obstacle cost is switched on; under absolute sample "
                                                       "times a segment time moves every later segment's lookups, "
                                                       "which this derivative does not form");
@@ -21,7 +17,7 @@ int time_ready(gtop_ctx *c, const char *who, int B, int m, int time_stride) {
   return GTOP_OK;
 }
 
-int check_timeopt(gtop_ctx *c, const gtop_timeopt *o) {
+int gtop_check_timeopt(gtop_ctx *c, const gtop_timeopt *o) {
   if (!o) return fail(c, GTOP_ERR_INVALID, "optimize_times: options is NULL");
   if (o->reserved != 0) return fail(c, GTOP_ERR_INVALID, "optimize_times: reserved must be 0");
   if (!(o->rho >= 0.0) || !std::isfinite(o->rho))
@@ -36,19 +32,21 @@ int check_timeopt(gtop_ctx *c, const gtop_timeopt *o) {
   return GTOP_OK;
 }
 
-GtopTimeCost time_cost(const gtop_ctx *c) {
+GtopTimeCost gtop_time_cost(const gtop_ctx *c) {
   const gtop_params &p = c->prm;
   return {p.ws, p.wc, p.alpha, p.r, p.d0, p.alpha_v, p.r_v, p.v0, p.alpha_a, p.r_a, p.a0, p.step, p.enable_dyn};
 }
 
+namespace {
+
 int gradient_on_stream(gtop_ctx *c, int B, int m, const void *d_x, const void *d_Df, const void *d_T, int time_stride,
                        void *d_cost, void *d_gT, void *d_parts, void *hip_stream) {
-  if (int rc = time_ready(c, "time_gradient", B, m, time_stride)) return rc;
+  if (int rc = gtop_time_ready(c, "time_gradient", B, m, time_stride, true)) return rc;
   if (B == 0) return GTOP_OK;
   if (!d_x || !d_Df || !d_T || !d_cost || !d_gT) return fail(c, GTOP_ERR_INVALID, "time_gradient: NULL buffer");
   if (int rc = c->field.need_records64(c)) return rc;
   HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, gtop_launch_time_gradient(c->field.grid, c->field.rec64.data(), time_cost(c), B, m,
+  HIPCHK(c, gtop_launch_time_gradient(c->field.grid, c->field.rec64.data(), gtop_time_cost(c), B, m,
                                       static_cast<const double *>(d_x), static_cast<const double *>(d_Df),
                                       static_cast<const double *>(d_T), time_stride, static_cast<double *>(d_cost),
                                       static_cast<double *>(d_gT), static_cast<double *>(d_parts),
@@ -59,14 +57,14 @@ int gradient_on_stream(gtop_ctx *c, int B, int m, const void *d_x, const void *d
 int optimize_on_stream(gtop_ctx *c, const gtop_timeopt *o, int B, int m, const void *d_x, const void *d_Df,
                        const void *d_T, int time_stride, const void *d_T_lo, void *d_T_out, void *d_info,
                        void *hip_stream) {
-  if (int rc = check_timeopt(c, o)) return rc;
-  if (int rc = time_ready(c, "optimize_times", B, m, time_stride)) return rc;
+  if (int rc = gtop_check_timeopt(c, o)) return rc;
+  if (int rc = gtop_time_ready(c, "optimize_times", B, m, time_stride, true)) return rc;
   if (B == 0) return GTOP_OK;
   if (!d_x || !d_Df || !d_T || !d_T_out || !d_info) return fail(c, GTOP_ERR_INVALID, "optimize_times: NULL buffer");
   if (d_T_out == d_T) return fail(c, GTOP_ERR_INVALID, "optimize_times: T_out may not alias T");
   if (int rc = c->field.need_records64(c)) return rc;
   HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, gtop_launch_time_optimize(c->field.grid, c->field.rec64.data(), time_cost(c), o->rho, o->t_min, o->t_max,
+  HIPCHK(c, gtop_launch_time_optimize(c->field.grid, c->field.rec64.data(), gtop_time_cost(c), o->rho, o->t_min, o->t_max,
                                       o->first_move, o->ftol_rel, o->xtol_abs, o->max_evals, B, m,
                                       static_cast<const double *>(d_x), static_cast<const double *>(d_Df),
                                       static_cast<const double *>(d_T), time_stride, static_cast<const double *>(d_T_lo),
@@ -93,7 +91,7 @@ int gtop_time_gradient_batch(gtop_ctx *c, int B, const double *x, double *cost, 
   if ((rc = gtop_problem_rows(c, B, x && cost && gT, "time_gradient_batch: 1 <= B <= problem batch; x, cost and gT required")))
     return rc;
   const int m = c->m;
-  if ((rc = time_ready(c, "time_gradient_batch", B, m, c->t_stride))) return rc;   // (before anything is staged)
+  if ((rc = gtop_time_ready(c, "time_gradient_batch", B, m, c->t_stride, true))) return rc;   // (before anything is staged)
   HIPCHK(c, hipSetDevice(c->device));
   const size_t n = 9 * (size_t)(m - 1), nT = (size_t)B * m;
   // the segment staging: cost | gT | parts
@@ -122,11 +120,11 @@ int gtop_optimize_times(gtop_ctx *c, const gtop_timeopt *opt, int B, const doubl
                         double *info) try {
   if (!c) return GTOP_ERR_INVALID;
   int rc;
-  if ((rc = check_timeopt(c, opt))) return rc;
+  if ((rc = gtop_check_timeopt(c, opt))) return rc;
   if ((rc = gtop_problem_rows(c, B, x && T_out && info, "optimize_times: 1 <= B <= problem batch; x, T_out and info required")))
     return rc;
   const int m = c->m;
-  if ((rc = time_ready(c, "optimize_times", B, m, c->t_stride))) return rc;   // (before anything is staged)
+  if ((rc = gtop_time_ready(c, "optimize_times", B, m, c->t_stride, true))) return rc;   // (before anything is staged)
   HIPCHK(c, hipSetDevice(c->device));
   const size_t n = 9 * (size_t)(m - 1), nT = (size_t)B * m, nI = (size_t)B * GTOP_TIMEOPT_INFO;
   // the segment staging: T_lo | T_out | info

@@ -10,6 +10,9 @@
 // (gtop_insert.hip).
 // The centre of a POLYNOMIAL box (gtop_set_moving_box_polynomials) is stated here once for those two kernels and for
 // the cost bodies (mov_min_boxes, gtop_wave_kernel.h).
+// The derivative of the box-lowered corner values with respect to the boxes' time (gtop_edt_box_velocity_of,
+// gtop_edt_box_min_dtau; include/gtop_time_moving.h) is stated here once too, for the segment-time pass of
+// gtop_time_pass.h.
 // The STATIC lookup (base index, diff, trilinear value; the gradient in gtop_edt.hip) is unfused, as poly_eval is:
 // it is sdf_map.cpp's arithmetic operation for operation, so a static query returns the bits of the reference's
 // getDistWithGradTrilinear.  Fused, a gradient component that cancels between corners of very different size (free
@@ -164,6 +167,60 @@ __device__ __forceinline__ void gtop_edt_box_min(const GtopGrid &g, const double
         for (int z = 0; z < 2; ++z) {
           const double d2 = sqrt(d1[0][x] * d1[0][x] + d1[1][y] * d1[1][y] + d1[2][z] * d1[2][z]);   // dist.norm()
           values[x][y][z] = d2 < values[x][y][z] ? d2 : values[x][y][z];
+          vmax = fmax(vmax, values[x][y][z]);
+        }
+  }
+}
+
+// ---- the TIME derivative of the box-lowered lookup (include/gtop_time_moving.h), stated here once ----
+// The velocity c'_k of a box's centre at time t.  Constant velocity: vel_k.  Polynomial: the derivative of the quintic
+// at the clamped time inside the open interval (t1, t2); outside it and at its ends the box stands: 0.
+template <bool POLY>
+__device__ __forceinline__ void gtop_edt_box_velocity_of(const double *row, double t, double cv[3]) {
+  if constexpr (POLY) {
+    const double tc = gtop_box_poly_time(row, t);
+    const bool moves = t > row[21] && t < row[22];
+    for (int k = 0; k < 3; ++k) {
+      const double *c = row + 6 * k;
+      const double v = fma(fma(fma(fma(5.0 * c[5], tc, 4.0 * c[4]), tc, 3.0 * c[3]), tc, 2.0 * c[2]), tc, c[1]);
+      cv[k] = moves ? v : 0.0;
+    }
+  } else {
+    for (int k = 0; k < 3; ++k) cv[k] = row[3 + k];
+  }
+}
+
+// gtop_edt_box_min with the derivative of every corner value with respect to the box's time beside it: the VALUES are
+// gtop_edt_box_min's expressions, skip included, so they come out bit for bit the same.  Per axis and corner offset
+// d d1 / d t is 0 inside the slab, +c'_k below it (pt < bmin: d1 = bmin - pt) and -c'_k above it (pt > bmax).  A corner
+// the box lowers (strictly: the static value wins a tie, and the earlier box among boxes) carries
+// (sum_k d1_k d1'_k) / d2, 0 where d2 = 0; a corner it does not lower keeps what it carried (0 for a static value).
+__device__ __forceinline__ void gtop_edt_box_min_dtau(const GtopGrid &g, const double bmin[3], const double bmax[3],
+                                                      const double cv[3], const int idx[3], double values[2][2][2],
+                                                      double dvals[2][2][2], double &vmax) {
+  double d1[3][2], e1[3][2];
+  for (int k = 0; k < 3; ++k)
+    for (int o = 0; o < 2; ++o) {
+      const double pt = (idx[k] + o + 0.5) * g.res + g.origin[k];
+      d1[k][o] = (pt >= bmin[k] && pt <= bmax[k]) ? 0.0 : fmin(fabs(pt - bmin[k]), fabs(pt - bmax[k]));
+      e1[k][o] = pt < bmin[k] ? cv[k] : (pt > bmax[k] ? -cv[k] : 0.0);
+    }
+  const double near2 = fmin(d1[0][0], d1[0][1]) * fmin(d1[0][0], d1[0][1]) +
+                       fmin(d1[1][0], d1[1][1]) * fmin(d1[1][0], d1[1][1]) +
+                       fmin(d1[2][0], d1[2][1]) * fmin(d1[2][0], d1[2][1]);
+  if (sqrt(near2) < vmax) {
+    vmax = 0.0;
+#pragma unroll
+    for (int x = 0; x < 2; ++x)
+#pragma unroll
+      for (int y = 0; y < 2; ++y)
+#pragma unroll
+        for (int z = 0; z < 2; ++z) {
+          const double d2 = sqrt(d1[0][x] * d1[0][x] + d1[1][y] * d1[1][y] + d1[2][z] * d1[2][z]);   // dist.norm()
+          const double num = d1[0][x] * e1[0][x] + d1[1][y] * e1[1][y] + d1[2][z] * e1[2][z];
+          const bool lower = d2 < values[x][y][z];
+          dvals[x][y][z] = lower ? (d2 > 0.0 ? num / d2 : 0.0) : dvals[x][y][z];
+          values[x][y][z] = lower ? d2 : values[x][y][z];
           vmax = fmax(vmax, values[x][y][z]);
         }
   }

@@ -346,6 +346,24 @@ hipError_t gtop_launch_time_optimize(const GtopGrid &g, const double *rec, const
                                      int max_evals, int B, int m, const double *x, const double *Df, const double *T,
                                      int t_stride, const double *T_lo, double *T_out, double *info, hipStream_t stream);
 
+// ---- the same under the moving-obstacle cost (gtop_time_moving.hip), fp64 -----------------------------------------
+#define GTOP_TIME_MOVING_PARTS 6   // = include/gtop_time_moving.h
+// cost [B], gT [B][m], gt0 [B] (may be NULL) and parts [B][m][GTOP_TIME_MOVING_PARTS] (may be NULL) as
+// include/gtop_time_moving.h lays them out.  boxes: at most GTOP_MOVING_MAX_BOXES of either kind (more:
+// hipErrorInvalidValue); count 0: the static lookup, the moving columns 0.  t0 (NULL: every start 0) with stride 0 or 1.
+// One wavefront per trajectory, one launch
+hipError_t gtop_launch_time_gradient_moving(const GtopGrid &g, const double *rec, const GtopTimeCost &p,
+                                            const GtopBoxList &boxes, const double *t0, int t0_stride, int B, int m,
+                                            const double *x, const double *Df, const double *T, int t_stride,
+                                            double *cost, double *gT, double *gt0, double *parts, hipStream_t stream);
+// gtop_launch_time_optimize with that pass as its evaluation; 1 .. GTOP_MOVING_MAX_BOXES boxes; one launch
+hipError_t gtop_launch_time_optimize_moving(const GtopGrid &g, const double *rec, const GtopTimeCost &p,
+                                            const GtopBoxList &boxes, const double *t0, int t0_stride, double rho,
+                                            double t_min, double t_max, double first_move, double ftol_rel,
+                                            double xtol_abs, int max_evals, int B, int m, const double *x,
+                                            const double *Df, const double *T, int t_stride, const double *T_lo,
+                                            double *T_out, double *info, hipStream_t stream);
+
 // ---- swarm separation cost (gtop_swarm.hip), fp64 ----------------------------------------------------------------
 // the common grid of include/gtop_swarm.h's options
 struct GtopSwarmGrid {

@@ -1,187 +1,14 @@
 // gtop_time.hip — the derivative of the cost with respect to every segment time, and the optimizer of the time
 // allocation built on it, on gfx950, fp64 (include/gtop_time.h).
 //
-// With the waypoint values held in x and Df, segment s depends on T_s alone: d cost / d T_s is a sum over the segment's
-// own 30 samples plus the closed-form derivative of its jerk integral.  One WAVEFRONT per trajectory, several per
-// workgroup, no workgroup barrier.  The lanes run over (segment of a pair, sample): lanes 0 .. 29 the samples of segment
-// 2p, lanes 32 .. 61 those of segment 2p + 1, so that a segment's sums stay inside one 32-lane half and are taken by a
-// fixed xor butterfly — a row's bits do not depend on B or on its place.  Pairs are walked in order; an odd m leaves
-// the upper half idle in the last pass.  The lookups read the corner records (gtop_edt_lookup.h).  The coefficients are
-// recomputed from x, Df and T in every pass: nothing per sample or per iteration is written to HBM.
-//
-// The optimizer is the same pass inside the row's loop, with T, g, the trial T' and its g' in LDS (4 m doubles per
+// The pass over a trajectory and the optimizer's row loop are gtop_time_pass.h's, shared with the kernels under the
+// moving-obstacle cost (gtop_time_moving.hip); here they are instantiated without it: one wavefront per trajectory,
+// several per workgroup, no workgroup barrier, T, g, the trial T' and its g' of the optimizer in LDS (4 m doubles per
 // wavefront).
 
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "gtop_device_common.h"
-#include "gtop_edt_lookup.h"
-#include "gtop_kernels.h"
+#include "gtop_time_pass.h"
 
 namespace {
-
-constexpr int kTimeWaves = 4;   // wavefronts (trajectories) per workgroup
-
-struct TimeParams {
-  GtopGrid g;
-  const double *rec;   // the fp64 corner records
-  double ws, wc;       // ws: 0 at step 1 already
-  double alpha, d0, inv_r, alpha_over_r;
-  double alpha_v, v0, inv_r_v, alpha_a, a0, inv_r_a;
-  int colli, dyn;      // |wc| >= 1e-4; enable_dyn at step 2
-};
-
-// this wavefront's own LDS writes, before its own LDS reads (one wavefront's LDS operations execute in order)
-__device__ __forceinline__ void time_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// the sum over the 32 lanes of a half, in every lane of it; the order is the butterfly's, whatever the row
-__device__ __forceinline__ double time_half_sum(double v) {
-  for (int off = 16; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-__device__ __forceinline__ double time_wave_max(double v) {
-  for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off));
-  return v;
-}
-
-// One pass over the trajectory at segment times Ts (global memory or LDS): g_out[s] = d cost / d T_s + g_add, parts
-// (may be NULL) [m][GTOP_TIME_PARTS]; returns the cost (its 1e-3 included), the same value in every lane.
-__device__ __forceinline__ double time_pass(const TimeParams &P, int m, int lane, const double *__restrict__ xb,
-                                            const double *__restrict__ dfb, const double *Ts, double g_add,
-                                            double *g_out, double *parts) {
-  const int half = lane >> 5, i = lane & 31;
-  const int ndp = 3 * m - 3;
-  const double fr = (double)i / 30.0;   // d t_i / d T
-  double cost = 0.0;
-  for (int s0 = 0; s0 < m; s0 += 2) {
-    const int sq = s0 + half;
-    const bool seg_ok = sq < m;
-    const int s = seg_ok ? sq : m - 1;   // (an idle half repeats the last segment: its loads stay in bounds, nothing is written)
-    const double T = Ts[s];
-    // derivative vector layout (src/qp_generator.cpp:363-387): start | end | waypoint 1 | ... | waypoint m-1
-    const bool first = s == 0, last = s + 1 == m;
-    const double *p0 = first ? dfb : xb + 3 * (s - 1);
-    const double *p1 = last ? dfb + 3 : xb + 3 * s;
-    const int st0 = first ? 6 : ndp, st1 = last ? 6 : ndp;
-    // ---- coefficients c = A_s^-1 d and c' = d c / d T (rows of A_s: src/qp_generator.cpp:185-195) ----
-    const double T2 = T * T, T3 = T2 * T, T4 = T2 * T2, T5 = T4 * T;
-    const double iT = 1.0 / T, iT3 = iT * iT * iT, iT4 = iT3 * iT, iT5 = iT4 * iT;
-    double c[3][6], d[3][3];   // d[k][j - 3] = c_j'
-    double jc = 0.0, jd = 0.0;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const double a0 = p0[k * st0 + 2], v0 = p0[k * st0 + 1], q0 = p0[k * st0];
-      const double aT = p1[k * st1 + 2], vT = p1[k * st1 + 1], qT = p1[k * st1];
-      const double Pp = qT - q0 - v0 * T - 0.5 * a0 * T2, dP = -v0 - a0 * T;
-      const double Vv = (vT - v0 - a0 * T) * T, dV = vT - v0 - 2.0 * a0 * T;
-      const double Aa = (aT - a0) * T2, dA = 2.0 * (aT - a0) * T;
-      c[k][0] = q0; c[k][1] = v0; c[k][2] = 0.5 * a0;
-      c[k][3] = (10.0 * Pp - 4.0 * Vv + 0.5 * Aa) * iT3;
-      c[k][4] = (7.0 * Vv - 15.0 * Pp - Aa) * iT4;
-      c[k][5] = (6.0 * Pp - 3.0 * Vv + 0.5 * Aa) * iT5;
-      d[k][0] = (10.0 * dP - 4.0 * dV + 0.5 * dA) * iT3 - 3.0 * c[k][3] * iT;
-      d[k][1] = (7.0 * dV - 15.0 * dP - dA) * iT4 - 4.0 * c[k][4] * iT;
-      d[k][2] = (6.0 * dP - 3.0 * dV + 0.5 * dA) * iT5 - 5.0 * c[k][5] * iT;
-      // the jerk term (Jerk Hessian Q_s: src/qp_generator.cpp:226-234): c'Qc, its explicit d/dT and 2 (Qc) . c'
-      const double c3 = c[k][3], c4 = c[k][4], c5 = c[k][5];
-      const double q3 = 36.0 * T * c3 + 72.0 * T2 * c4 + 120.0 * T3 * c5;
-      const double q4 = 72.0 * T2 * c3 + 192.0 * T3 * c4 + 360.0 * T4 * c5;
-      const double q5 = 120.0 * T3 * c3 + 360.0 * T4 * c4 + 720.0 * T5 * c5;
-      jc += c3 * q3 + c4 * q4 + c5 * q5;
-      jd += 36.0 * c3 * c3 + 288.0 * T * c3 * c4 + 720.0 * T2 * c3 * c5 + 576.0 * T2 * c4 * c4 +
-            2880.0 * T3 * c4 * c5 + 3600.0 * T4 * c5 * c5;
-      jd += 2.0 * (q3 * d[k][0] + q4 * d[k][1] + q5 * d[k][2]);
-    }
-    const double smooth = P.ws * jc, dsmooth = P.ws * jd;   // (every lane of the half holds the same two values)
-
-    // ---- the segment's samples (src/grad_traj_optimizer.cpp:345-409): lane i is sample i ----
-    double cs = 0.0, ds = 0.0;
-    if (P.colli) {
-      // t_i = 1e-3 + i dt (:353); a segment with T < 0.0301, where the sample COUNT hangs on the accumulated value,
-      // replays the reference's addition chain
-      double dt = T * (1.0 / 30.0);
-      double t = (double)i * dt + 1e-3;
-      bool live = i < 30;
-      if (T < 0.0301) {
-        dt = T / 30.0;
-        t = 1e-3;
-        for (int j = 0; j < i && j < 30; ++j) t += dt;
-        live = live && t < T;
-      }
-      // (a sample past the loop bound is evaluated at the first sample's time, with weight 0: no extrapolated polynomial)
-      if (!live) t = 1e-3;
-      const double fri = live ? fr : 0.0;
-      const double t2 = t * t, t3 = t2 * t, t4 = t2 * t2, t5 = t4 * t;
-      double pos[3], vel[3], acc[3], pd[3], vd[3], ad[3];
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        const double *q = c[k], *e = d[k];
-        // the reference's float locals (:457-465, :477-485, :491-505)
-        pos[k] = (double)(float)(q[0] + q[1] * t + q[2] * t2 + q[3] * t3 + q[4] * t4 + q[5] * t5);
-        vel[k] = (double)(float)(q[1] + 2.0 * q[2] * t + 3.0 * q[3] * t2 + 4.0 * q[4] * t3 + 5.0 * q[5] * t4);
-        acc[k] = (double)(float)(2.0 * q[2] + 6.0 * q[3] * t + 12.0 * q[4] * t2 + 20.0 * q[5] * t3);
-        const double jerk = 6.0 * q[3] + 24.0 * q[4] * t + 60.0 * q[5] * t2;
-        pd[k] = e[0] * t3 + e[1] * t4 + e[2] * t5 + vel[k] * fri;
-        vd[k] = 3.0 * e[0] * t2 + 4.0 * e[1] * t3 + 5.0 * e[2] * t4 + acc[k] * fri;
-        ad[k] = 6.0 * e[0] * t + 12.0 * e[1] * t2 + 20.0 * e[2] * t3 + jerk * fri;
-      }
-      const double vn = sqrt(vel[0] * vel[0] + vel[1] * vel[1] + vel[2] * vel[2]) + 1e-5;   // :358
-      const double vdot = (vel[0] * vd[0] + vel[1] * vd[1] + vel[2] * vd[2]) / vn;          // d vn / d T
-      // SDFMap::getDistWithGradTrilinear (:363): the cell from the float position, in double; out of the map dist = -1
-      // and the gradient 0 (sdf_map.cpp:187)
-      int idx[3];
-      double diff[3], values[2][2][2], grad[3];
-      gtop_edt_corners(P.g, P.rec, pos, idx, diff, values);
-      const GtopTrilinear tl = gtop_edt_trilinear(diff, values);
-      gtop_edt_gradient(P.g, diff, values, tl, grad);
-      double dist = tl.d;
-      if (gtop_edt_out_of_map(P.g, pos)) {
-        dist = -1.0;
-        grad[0] = grad[1] = grad[2] = 0.0;
-      }
-      const double e = exp((P.d0 - dist) * P.inv_r);
-      const double cd = P.alpha * e, gd = -P.alpha_over_r * e;   // :509, :514
-      const double gp = grad[0] * pd[0] + grad[1] * pd[1] + grad[2] * pd[2];
-      cs = P.wc * (cd * vn * dt);                                                            // :373, weighted as :417
-      ds = P.wc * (gd * gp * vn * dt + cd * vdot * dt + cd * vn * (1.0 / 30.0));
-      if (P.dyn) {   // the block of :383-407 with the formulas of :517-535
-        double S = 0.0, dS = 0.0;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-          const double cv = P.alpha_v * exp((fabs(vel[k]) - P.v0) * P.inv_r_v);
-          const double ca = P.alpha_a * exp((fabs(acc[k]) - P.a0) * P.inv_r_a);
-          const double sv = (double)((vel[k] > 0.0) - (vel[k] < 0.0)), sa = (double)((acc[k] > 0.0) - (acc[k] < 0.0));
-          S += cv + ca;
-          dS += cv * P.inv_r_v * sv * vd[k] + ca * P.inv_r_a * sa * ad[k];
-        }
-        cs += S * vn * dt;
-        ds += dS * vn * dt + S * vdot * dt + S * vn * (1.0 / 30.0);
-      }
-      cs = live ? cs : 0.0;   // (past the loop bound, and the two idle lanes of a half: nothing reaches the sums)
-      ds = live ? ds : 0.0;
-      cs = time_half_sum(cs);
-      ds = time_half_sum(ds);
-    }
-    if (seg_ok && i == 0) {
-      g_out[s] = (dsmooth + ds) + g_add;
-      if (parts) {
-        double *o = parts + (size_t)s * 4;
-        o[0] = smooth; o[1] = cs; o[2] = dsmooth; o[3] = ds;
-      }
-    }
-    // the cost: the segments' two parts in segment order, by every lane alike
-    const double seg_cost = smooth + cs;
-    const double c_lo = __shfl(seg_cost, 0), c_hi = __shfl(seg_cost, 32);
-    cost += c_lo;
-    if (s0 + 1 < m) cost += c_hi;
-  }
-  return cost + 1e-3;   // :417-418
-}
 
 __global__ void __launch_bounds__(64 * kTimeWaves)
 time_gradient_kernel(const TimeParams P, int B, int m, const double *__restrict__ x, const double *__restrict__ Df,
@@ -191,20 +18,11 @@ time_gradient_kernel(const TimeParams P, int B, int m, const double *__restrict_
   const int b = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * kTimeWaves + (threadIdx.x >> 6)));
   if (b >= B) return;
   const size_t n = 9 * (size_t)(m - 1);
-  const double c = time_pass(P, m, lane, x + (size_t)b * n, Df + (size_t)b * 18, T + (size_t)b * t_stride, 0.0,
-                             gT + (size_t)b * m, parts ? parts + (size_t)b * m * 4 : nullptr);
+  TimeMoving none{};
+  const double c = time_pass<false, false, GTOP_TIME_PARTS>(P, none, m, lane, x + (size_t)b * n, Df + (size_t)b * 18,
+                                                            T + (size_t)b * t_stride, 0.0, gT + (size_t)b * m,
+                                                            parts ? parts + (size_t)b * m * 4 : nullptr);
   if (lane == 0) cost[b] = c;
-}
-
-struct TimeOpt {
-  double rho, t_min, t_max, first_move, ftol_rel, xtol_abs;
-  int max_evals;
-};
-
-// lo_s = max(t_min, T_lo[s]); lo_s > t_max pins the segment at lo_s
-__device__ __forceinline__ double time_clamp(const TimeOpt &O, const double *lo_row, int s, double v) {
-  const double lo = lo_row ? fmax(O.t_min, lo_row[s]) : O.t_min;
-  return lo > O.t_max ? lo : fmin(fmax(v, lo), O.t_max);
 }
 
 // LDS: per wavefront T | g | T' | g', m doubles each
@@ -220,95 +38,9 @@ time_optimize_kernel(const TimeParams P, const TimeOpt O, int B, int m, const do
   const size_t n = 9 * (size_t)(m - 1);
   const double *xb = x + (size_t)b * n, *dfb = Df + (size_t)b * 18, *Tin = T + (size_t)b * t_stride;
   const double *lo_row = T_lo ? T_lo + (size_t)b * m : nullptr;
-  double *Tc = time_lds + (size_t)wave * 4 * m, *gc = Tc + m, *Tp = gc + m, *gp = Tp + m;
-
-  double tsum = 0.0;
-  for (int s = lane; s < m; s += 64) {
-    const double v = time_clamp(O, lo_row, s, Tin[s]);
-    Tc[s] = v;
-    tsum += v;
-  }
-  tsum = gtop_wave_sum(tsum);
-  time_wave_sync();
-  double cost = time_pass(P, m, lane, xb, dfb, Tc, O.rho, gc, nullptr);
-  time_wave_sync();
-  double F = cost + O.rho * tsum;
-  const double F0 = F;
-  int evals = 1, accepted = 0, code = GTOP_MMA_XTOL_REACHED;
-  double gmax = 0.0;
-  for (int s = lane; s < m; s += 64) gmax = fmax(gmax, fabs(gc[s]));
-  gmax = time_wave_max(gmax);
-  if (gmax > 0.0) {
-    double a = O.first_move / gmax;
-    for (;;) {
-      int backtracks = 0;
-      double Fp = 0.0, costp = 0.0, tsump = 0.0;
-      bool stop = false;
-      for (;;) {
-        double dmax = 0.0, slope = 0.0;
-        tsump = 0.0;
-        for (int s = lane; s < m; s += 64) {
-          const double told = Tc[s], g = gc[s];
-          const double tn = time_clamp(O, lo_row, s, told - a * g);
-          const double dd = tn - told;
-          Tp[s] = tn;
-          tsump += tn;
-          dmax = fmax(dmax, fabs(dd));
-          slope += g * dd;
-        }
-        dmax = time_wave_max(dmax);
-        slope = gtop_wave_sum(slope);
-        tsump = gtop_wave_sum(tsump);
-        if (dmax <= O.xtol_abs) { code = GTOP_MMA_XTOL_REACHED; stop = true; break; }
-        if (evals >= O.max_evals) { code = GTOP_MMA_MAXEVAL_REACHED; stop = true; break; }
-        time_wave_sync();
-        costp = time_pass(P, m, lane, xb, dfb, Tp, O.rho, gp, nullptr);
-        time_wave_sync();
-        Fp = costp + O.rho * tsump;
-        ++evals;
-        if (Fp <= F + 1e-4 * slope) break;   // (a NaN F' is a rejection)
-        a *= 0.5;
-        ++backtracks;
-      }
-      if (stop) break;
-      const double decrease = F - Fp;
-      double *t0 = Tc; Tc = Tp; Tp = t0;
-      double *t1 = gc; gc = gp; gp = t1;
-      F = Fp; cost = costp; tsum = tsump;
-      ++accepted;
-      if (decrease <= O.ftol_rel * fabs(F)) { code = GTOP_MMA_FTOL_REACHED; break; }
-      if (backtracks == 0) a *= 2.0;
-    }
-  }
-  // the row's results: T_out, and the largest |g| among the segments their gradient does not hold at a bound
-  double gfree = 0.0;
-  for (int s = lane; s < m; s += 64) {
-    const double v = Tc[s], g = gc[s];
-    const double lo = lo_row ? fmax(O.t_min, lo_row[s]) : O.t_min;
-    const bool held = lo > O.t_max || (v <= lo && g > 0.0) || (v >= O.t_max && g < 0.0);
-    if (!held) gfree = fmax(gfree, fabs(g));
-    T_out[(size_t)b * m + s] = v;
-  }
-  gfree = time_wave_max(gfree);
-  if (lane == 0) {
-    double *o = info + (size_t)b * 8;
-    o[0] = (double)code; o[1] = (double)accepted; o[2] = (double)evals; o[3] = F0;
-    o[4] = F; o[5] = cost; o[6] = gfree; o[7] = tsum;
-  }
-}
-
-TimeParams time_params(const GtopGrid &g, const double *rec, const GtopTimeCost &p) {
-  TimeParams P;
-  P.g = g;
-  P.rec = rec;
-  P.ws = p.step == 1 ? 0.0 : p.ws;   // :412-415
-  P.wc = p.wc;
-  P.alpha = p.alpha; P.d0 = p.d0; P.inv_r = 1.0 / p.r; P.alpha_over_r = p.alpha / p.r;
-  P.alpha_v = p.alpha_v; P.v0 = p.v0; P.inv_r_v = p.r_v != 0.0 ? 1.0 / p.r_v : 0.0;
-  P.alpha_a = p.alpha_a; P.a0 = p.a0; P.inv_r_a = p.r_a != 0.0 ? 1.0 / p.r_a : 0.0;
-  P.colli = !(fabs(p.wc) < 1e-4);   // :346
-  P.dyn = p.enable_dyn && p.step == 2;   // :383
-  return P;
+  TimeMoving none{};
+  time_optimize_row<false, false>(P, none, O, b, m, lane, xb, dfb, Tin, lo_row, time_lds + (size_t)wave * 4 * m, T_out,
+                                  info);
 }
 
 }  // namespace
