@@ -42,8 +42,15 @@ from .swarm import (SWARM_ABI_VERSION, SWARM_ENTRY_POINTS, GtopSwarmOpts, GtopSw
                     optimize_swarm_device, swarm_abi_version, swarm_gradient_batch, swarm_gradient_device,
                     swarm_library, swarm_workspace_bytes)
 from . import swarm  # noqa: F401
+from .joint import (JOINT_ABI_VERSION, JOINT_ENTRY_POINTS, JOINT_INFO, GtopJointOpt, joint_abi_version,  # noqa: F401
+                    joint_gradient_batch, joint_gradient_device, joint_library, joint_workspace_bytes, optimize_joint,
+                    optimize_joint_device)
+from . import joint  # noqa: F401
 
-__all__ = ["SWARM_ABI_VERSION", "SWARM_ENTRY_POINTS", "GtopSwarmOpts", "GtopSwarmStop", "swarm", "optimize_swarm",
+__all__ = ["JOINT_ABI_VERSION", "JOINT_ENTRY_POINTS", "JOINT_INFO", "GtopJointOpt", "joint", "joint_abi_version",
+           "joint_gradient_batch", "joint_gradient_device", "joint_library", "joint_workspace_bytes", "optimize_joint",
+           "optimize_joint_device",
+           "SWARM_ABI_VERSION", "SWARM_ENTRY_POINTS", "GtopSwarmOpts", "GtopSwarmStop", "swarm", "optimize_swarm",
            "optimize_swarm_device", "swarm_abi_version", "swarm_gradient_batch", "swarm_gradient_device",
            "swarm_library", "swarm_workspace_bytes",
            "TIME_ABI_VERSION", "TIME_ENTRY_POINTS", "TIME_PARTS", "TIMEOPT_INFO", "GtopTimeOpt", "timeopt",

@@ -426,6 +426,89 @@ bool GradTrajOptimizer::optimizeSegmentTimesWith(const TimeOptConfig &config, Ti
   return true;
 }
 
+bool GradTrajOptimizer::jointGradient(double *cost, std::vector<double> *gx, std::vector<double> *gT,
+                                      std::vector<std::array<double, 4>> *parts) {
+  if (!ctx_ || m_ < 2 || dp_.empty()) {
+    last_status_ = GTOP_ERR_STATE;
+    return false;
+  }
+  double c = 0.0;
+  std::vector<double> g(dp_.size()), t(m_), p(parts ? (size_t)m_ * GTOP_TIME_PARTS : 0);
+  last_status_ = gtop_joint_gradient_batch(ctx_, 1, dp_.data(), &c, g.data(), t.data(), parts ? p.data() : nullptr);
+  if (last_status_ != GTOP_OK) return false;
+  if (cost) *cost = c;
+  if (gx) *gx = g;
+  if (gT) *gT = t;
+  if (parts) {
+    parts->resize(m_);
+    for (int s = 0; s < m_; ++s)
+      for (int k = 0; k < GTOP_TIME_PARTS; ++k) (*parts)[s][k] = p[(size_t)s * GTOP_TIME_PARTS + k];
+  }
+  return true;
+}
+
+bool GradTrajOptimizer::optimizeJoint(const JointOptConfig &config, JointOptInfo *info) {
+  if (!ctx_ || m_ < 2 || dp_.empty()) {
+    last_status_ = GTOP_ERR_STATE;
+    return false;
+  }
+  gtop_jointopt opt{};
+  opt.rho = config.rho;
+  opt.t_min = config.t_min;
+  opt.t_max = config.t_max;
+  opt.ftol_rel = config.ftol_rel;
+  opt.xtol_rel = config.xtol_rel;
+  opt.max_evals = config.max_evals;
+  std::vector<double> lo;
+  if (config.keep_limits) {   // the LIMITS reallocation of the trajectory as it stands, Dp untouched
+    gtop_retime rt{};
+    rt.mode = GTOP_RETIME_LIMITS;
+    rt.max_vel = config.limits.max_vel;
+    rt.max_acc = config.limits.max_acc;
+    rt.per_axis = config.limits.per_axis;
+    rt.uniform = config.limits.uniform;
+    rt.max_ratio = config.limits.max_ratio;
+    gtop_limits lim{};
+    lim.margin = config.limits.report.margin;
+    lim.use_boxes = config.limits.report.use_boxes;
+    lo.resize(m_);
+    std::vector<double> x = dp_;
+    last_status_ = gtop_reallocate_times(ctx_, &rt, 1, x.data(), config.limits.report.dt_sample, &lim, lo.data());
+    if (last_status_ != GTOP_OK) return false;
+  }
+  const size_t n = dp_.size();
+  std::vector<double> x = dp_, lb(n), ub(n), T(m_);   // the bounds of optimizeTrajectory, :151-179
+  for (int i = 0; i < num_dp_; ++i)
+    for (int a = 0; a < 3; ++a) {
+      const size_t j = (size_t)i + (size_t)a * num_dp_;
+      const double centre = i % 3 == 0 ? path_[(i / 3 + 1) * 3 + a] : 0.0;
+      const double half = i % 3 == 0 ? cfg_.bos : (i % 3 == 1 ? cfg_.vos : cfg_.aos);
+      lb[j] = centre - half;
+      ub[j] = centre + half;
+    }
+  double r[GTOP_JOINT_INFO];
+  gtop_set_optimizer_precision(ctx_, GTOP_F64);
+  last_status_ = gtop_optimize_joint(ctx_, &opt, 1, x.data(), lb.data(), ub.data(), lo.empty() ? nullptr : lo.data(),
+                                     T.data(), r);
+  if (last_status_ != GTOP_OK) return false;
+  last_status_ = gtop_set_problem(ctx_, 1, m_, T.data(), m_, df_.data());   // (refuses a time that is not > 0)
+  if (last_status_ != GTOP_OK) return false;
+  segment_time_ = T;
+  dp_ = x;
+  coefficientsFromDerivatives(dp_);
+  if (info) {
+    info->code = (int)r[0];
+    info->evaluations = (int)r[1];
+    info->f_start = r[2];
+    info->f = r[3];
+    info->cost = r[4];
+    info->time_sum = r[5];
+    info->free_gradient_x = r[6];
+    info->free_gradient_t = r[7];
+  }
+  return true;
+}
+
 bool GradTrajOptimizer::swarmProblem(const std::vector<GradTrajOptimizer *> &robots, const SwarmOptions &options,
                                      gtop_swarm_opts *opt, std::vector<double> *x) {
   if (robots.empty() || !robots[0]) return false;

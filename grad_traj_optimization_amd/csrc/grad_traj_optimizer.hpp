@@ -23,6 +23,7 @@
 #include "gtop_kinematics.h"
 #include "gtop_prediction.h"
 #include "gtop_swarm.h"
+#include "gtop_joint.h"
 #include "gtop_time.h"
 #include "gtop_time_moving.h"
 
@@ -281,6 +282,28 @@ class GradTrajOptimizer {
   bool timeGradientMoving(double *cost, std::vector<double> *gT, double *gt0 = nullptr,
                           std::vector<std::array<double, 6>> *parts = nullptr);
   bool optimizeSegmentTimesMoving(const TimeOptConfig &config, TimeOptInfo *info = nullptr);
+  // The cost with its derivative with respect to every free waypoint value (gx, laid out as Dp, axis-major) and every
+  // segment time (gT) from one pass (include/gtop_joint.h, gtop_joint_gradient_batch), at the current Dp and
+  // segment_time and the parameters the last optimizeTrajectory left in force.  false when the call fails.
+  bool jointGradient(double *cost, std::vector<double> *gx, std::vector<double> *gT,
+                     std::vector<std::array<double, 4>> *parts = nullptr);
+  // Dp and the segment times optimised TOGETHER: cost + rho sum(T) minimised over both by the batched MMA loop
+  // (include/gtop_joint.h, gtop_optimize_joint) inside optimizeTrajectory's bounds on Dp and t_min .. t_max on the times;
+  // keep_limits as in TimeOptConfig.  Dp, segment_time and the coefficients are replaced.  false, and nothing changed,
+  // when the call fails.
+  struct JointOptConfig {
+    double rho = 1.0;
+    double t_min = 0.05, t_max = 60.0;
+    double ftol_rel = 0.0, xtol_rel = 0.0;
+    int max_evals = 40;
+    bool keep_limits = false;
+    RetimeOptions limits;
+  };
+  struct JointOptInfo {
+    int code = 0, evaluations = 0;   // 3 FTOL, 4 XTOL, 5 MAXEVAL
+    double f_start = 0.0, f = 0.0, cost = 0.0, time_sum = 0.0, free_gradient_x = 0.0, free_gradient_t = 0.0;
+  };
+  bool optimizeJoint(const JointOptConfig &config, JointOptInfo *info = nullptr);
   // The robots of a swarm, one object each, planned against each other (include/gtop_swarm.h).  Their paths must have
   // the same number of segments.  Both calls run on the FIRST object's context: its map, and the parameters its last
   // optimizeTrajectory left in force; that context's problem is the swarm for the length of the call and the object's

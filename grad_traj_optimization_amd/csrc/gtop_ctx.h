@@ -14,6 +14,7 @@
 //   gtop_capi_prediction.cpp  include/gtop_prediction.h: predictions fitted from histories, the box list's refresh
 //   gtop_capi_time.cpp        include/gtop_time.h: the segment-time gradient, the optimizer of the time allocation
 //   gtop_capi_swarm.cpp       include/gtop_swarm.h: the swarm separation cost, its gradient, the swarm optimizer
+//   gtop_capi_joint.cpp       include/gtop_joint.h: the joint gradient over x and T, the joint optimizer
 // Host-side only: they own device buffers, fill kernel arguments, launch.  There is deliberately no CPU code path:
 // without a gfx950 device every entry point fails (GTOP_ERR_NO_DEVICE).
 #ifndef GTOP_CTX_H_

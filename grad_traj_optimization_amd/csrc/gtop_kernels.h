@@ -390,4 +390,35 @@ hipError_t gtop_launch_swarm_terms(const GtopSwarmGrid &g, double w, double radi
 // joint [B][2] = cost [B] | S [B] (NULL: +0); one launch
 hipError_t gtop_launch_swarm_joint(int B, const double *cost, const double *S, double *joint, hipStream_t stream);
 
+// ---- the joint pass over waypoint derivatives and segment times, and its optimizer's own launches (gtop_joint.hip),
+// fp64 ----
+#define GTOP_JOINT_INFO 8   // = include/gtop_joint.h
+// One pass per row: f, d f / d x (9 (m - 1) entries at gx) and d f / d T (m entries at gT; parts as
+// gtop_launch_time_gradient, may be NULL).  Every row pointer comes with its stride in doubles, so that the pass runs on
+// separate buffers (the public gradient) and on a packed state z = [x | T] with f | g beside it (the optimizer).
+// with_rho: f = cost + rho sum_s T_s and rho is added to every gT entry; else f = cost and gT is bare.
+// aux (may be NULL): aux[b * aux_stride] = the cost without the rho term (aux_plain) or f.
+struct GtopJointRows {
+  const double *x; size_t x_stride;
+  const double *T; size_t t_stride;   // 0: one row of times for all
+  double *f; size_t f_stride;
+  double *gx; size_t gx_stride;
+  double *gT; size_t gt_stride;
+  double *aux; size_t aux_stride;
+  int aux_plain;
+};
+hipError_t gtop_launch_joint_pass(const GtopGrid &g, const double *rec, const GtopTimeCost &p, int B, int m,
+                                  const GtopJointRows &rows, const double *Df, int with_rho, double rho, double *parts,
+                                  hipStream_t stream);
+// the packed start point z0 [B][10m - 9] = [x | T] and the packed bounds zlb, zub = [lb | lo] , [ub | hi]: lo_s =
+// max(t_min, T_lo[b][s]) (T_lo NULL: t_min), hi_s = t_max, and lo_s > t_max pins the segment: lo_s = hi_s; one launch
+hipError_t gtop_launch_joint_pack(int B, int m, const double *x, const double *T, int t_stride, const double *lb,
+                                  const double *ub, const double *T_lo, double t_min, double t_max, double *z0,
+                                  double *zlb, double *zub, hipStream_t stream);
+// the results of a finished loop: x_out, T_out from the best point z [B][10m - 9], and info [B][GTOP_JOINT_INFO] but
+// its entries [2] and [4] (written by the passes) from the gradient g at that point, the bounds, minf, code and nevals
+hipError_t gtop_launch_joint_report(int B, int m, const double *z, const double *g, const double *zlb, const double *zub,
+                                    const double *minf, const int *code, const int *nevals, double *x_out, double *T_out,
+                                    double *info, hipStream_t stream);
+
 #endif  // GTOP_KERNELS_H_

@@ -16,6 +16,15 @@
 // evaluation's own order, against the boxes staged in LDS; beside the 8 corner values the box loop tracks their 8
 // derivatives with respect to tau (gtop_edt_box_min_dtau).  T_s then also moves every LATER segment: q_s, what the
 // segment's cost gains per second of delay of its start, goes to LDS and is summed from the last segment to the first.
+//
+// GX (a template argument, as MOV: without it every line it adds is compiled out): the pass also leaves the derivative
+// with respect to every free waypoint value (gtop_joint.hip, include/gtop_joint.h).  The coefficients
+// are linear in a segment's six end values per axis, so a sample adds Wp h_j + Wv h_j' + Wa h_j'' to entry j of axis k:
+// 18 values per sample, summed over the half by time_half_sum's butterfly taken for all 18 at once (time_half_spread18:
+// a lane keeps only its share of the values at every level, 20 shuffles for 90, and ends with ONE complete sum).  The
+// lane adds the jerk term of its entry; an interior waypoint gets the end part of the segment before it plus the start
+// part of the segment behind it: across the halves of a pair by one shuffle, across pairs by one carried value per lane —
+// no LDS, no global traffic but the one store per entry.
 #ifndef GTOP_TIME_PASS_H_
 #define GTOP_TIME_PASS_H_
 
@@ -63,19 +72,72 @@ __device__ __forceinline__ double time_wave_max(double v) {
   return v;
 }
 
+// time_half_sum of 18 values at once.  The same butterfly level by level (xor 16, 8, 4, 2, 1: the same pairs in the same
+// order, so the same bits), but at every level a lane keeps the lower or the upper share of its values by its bit of that
+// level and trades the other share for its partner's: 9 + 5 + 3 + 2 + 1 shuffles.  Lane i of the half ends with the
+// complete sum of ONE value — or of a pad: 18 of the 32 lanes hold a value.  SUM = false: no shuffle and no addition, the
+// lane's pick of v (of a table, or of the values' own indices: which value the lane ends with; pad for none).
+template <bool SUM, typename V>
+__device__ __forceinline__ V time_half_spread18(const V (&v)[18], int i, V pad) {
+  V a[9], b[5], c[3], d[2];
+  bool up = (i & 16) != 0;
+#pragma unroll
+  for (int k = 0; k < 9; ++k) {
+    const V keep = up ? v[k + 9] : v[k], send = up ? v[k] : v[k + 9];
+    if constexpr (SUM) a[k] = keep + __shfl_xor(send, 16); else a[k] = keep;
+  }
+  up = (i & 8) != 0;
+#pragma unroll
+  for (int k = 0; k < 5; ++k) {
+    const V hi = k + 5 < 9 ? a[k + 5 < 9 ? k + 5 : 0] : pad;
+    const V keep = up ? hi : a[k], send = up ? a[k] : hi;
+    if constexpr (SUM) b[k] = keep + __shfl_xor(send, 8); else b[k] = keep;
+  }
+  up = (i & 4) != 0;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const V hi = k + 3 < 5 ? b[k + 3 < 5 ? k + 3 : 0] : pad;
+    const V keep = up ? hi : b[k], send = up ? b[k] : hi;
+    if constexpr (SUM) c[k] = keep + __shfl_xor(send, 4); else c[k] = keep;
+  }
+  up = (i & 2) != 0;
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    const V hi = k + 2 < 3 ? c[k + 2 < 3 ? k + 2 : 0] : pad;
+    const V keep = up ? hi : c[k], send = up ? c[k] : hi;
+    if constexpr (SUM) d[k] = keep + __shfl_xor(send, 2); else d[k] = keep;
+  }
+  up = (i & 1) != 0;
+  const V keep = up ? d[1] : d[0], send = up ? d[0] : d[1];
+  if constexpr (SUM) return keep + __shfl_xor(send, 1); else return keep;
+}
+
 // One pass over the trajectory at segment times Ts (global memory or LDS): g_out[s] = d cost / d T_s + g_add, parts
 // (may be NULL) [m][NP]; returns the cost (its 1e-3 included), the same value in every lane.  NP = GTOP_TIME_PARTS, or
 // GTOP_TIME_MOVING_PARTS with [4] = q_s and [5] = R_s behind the four (both 0 without MOV).
-template <bool MOV, bool POLY, int NP>
+// GX: gx (3 (3m - 3) doubles, laid out as xb) gets d cost / d xb, every entry written once, by the lane that holds it.
+template <bool MOV, bool POLY, int NP, bool GX = false>
 __device__ __forceinline__ double time_pass(const TimeParams &P, TimeMoving &M, int m, int lane,
                                             const double *__restrict__ xb, const double *__restrict__ dfb,
-                                            const double *Ts, double g_add, double *g_out, double *parts) {
+                                            const double *Ts, double g_add, double *g_out, double *parts,
+                                            [[maybe_unused]] double *gx = nullptr) {
   const int half = lane >> 5, i = lane & 31;
   const int ndp = 3 * m - 3;
   const double fr = (double)i / 30.0;   // d t_i / d T
   double cost = 0.0;
   [[maybe_unused]] double carry = 0.0;   // MOV: the start of segment s0 on the boxes' clock
   if constexpr (MOV) carry = M.tau0;
+  // GX: the 18 entries of a segment are numbered part * 9 + axis * 3 + (0 position, 1 velocity, 2 acceleration); part 0
+  // is the END part in the lower half and the START part in the upper half, part 1 the other: the two lanes of a pair that
+  // hold the two parts of one waypoint's entry then sit 32 apart.  slot: the entry this lane ends with (-1: none).
+  [[maybe_unused]] int slot = -1;
+  [[maybe_unused]] double end_carry = 0.0;   // the upper half's end part of this lane's entry, for the next pair
+  if constexpr (GX) {
+    int ids[18];
+#pragma unroll
+    for (int q = 0; q < 18; ++q) ids[q] = q;
+    slot = time_half_spread18<false>(ids, i, -1);
+  }
   for (int s0 = 0; s0 < m; s0 += 2) {
     const int sq = s0 + half;
     const bool seg_ok = sq < m;
@@ -98,6 +160,7 @@ __device__ __forceinline__ double time_pass(const TimeParams &P, TimeMoving &M, 
     const double iT = 1.0 / T, iT3 = iT * iT * iT, iT4 = iT3 * iT, iT5 = iT4 * iT;
     double c[3][6], d[3][3];   // d[k][j - 3] = c_j'
     double jc = 0.0, jd = 0.0;
+    [[maybe_unused]] double jq[3][3] = {};   // GX: per axis 2 ws (q3, q4, q5), the jerk term's chain
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
       const double a0 = p0[k * st0 + 2], v0 = p0[k * st0 + 1], q0 = p0[k * st0];
@@ -121,8 +184,31 @@ __device__ __forceinline__ double time_pass(const TimeParams &P, TimeMoving &M, 
       jd += 36.0 * c3 * c3 + 288.0 * T * c3 * c4 + 720.0 * T2 * c3 * c5 + 576.0 * T2 * c4 * c4 +
             2880.0 * T3 * c4 * c5 + 3600.0 * T4 * c5 * c5;
       jd += 2.0 * (q3 * d[k][0] + q4 * d[k][1] + q5 * d[k][2]);
+      if constexpr (GX) {
+        jq[k][0] = P.ws * (2.0 * q3);
+        jq[k][1] = P.ws * (2.0 * q4);
+        jq[k][2] = P.ws * (2.0 * q5);
+      }
     }
     const double smooth = P.ws * jc, dsmooth = P.ws * jd;   // (every lane of the half holds the same two values)
+    // GX: the table d c_n / d (end value), n = 3, 4, 5, in this half's entry order e = part * 3 + (0, 1, 2): the lower
+    // half has (pT, vT, aT | p0, v0, a0), the upper (p0, v0, a0 | pT, vT, aT); is_start[part]: 1.0 where c0, c1, c2 move
+    [[maybe_unused]] double A3[6], A4[6], A5[6], is_start[2] = {};
+    [[maybe_unused]] double gsum = 0.0;   // the half's sum of this lane's entry over the samples
+    if constexpr (GX) {
+      const double iT2 = iT * iT;
+      const double s3[3] = {-10.0 * iT3, -6.0 * iT2, -1.5 * iT}, e3[3] = {10.0 * iT3, -4.0 * iT2, 0.5 * iT};
+      const double s4[3] = {15.0 * iT4, 8.0 * iT3, 1.5 * iT2}, e4[3] = {-15.0 * iT4, 7.0 * iT3, -iT2};
+      const double s5[3] = {-6.0 * iT5, -3.0 * iT4, -0.5 * iT3}, e5[3] = {6.0 * iT5, -3.0 * iT4, 0.5 * iT3};
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        A3[j] = half ? s3[j] : e3[j]; A3[j + 3] = half ? e3[j] : s3[j];
+        A4[j] = half ? s4[j] : e4[j]; A4[j + 3] = half ? e4[j] : s4[j];
+        A5[j] = half ? s5[j] : e5[j]; A5[j + 3] = half ? e5[j] : s5[j];
+      }
+      is_start[0] = half ? 1.0 : 0.0;
+      is_start[1] = half ? 0.0 : 1.0;
+    }
 
     // ---- the segment's samples (src/grad_traj_optimizer.cpp:345-409): lane i is sample i ----
     double cs = 0.0, ds = 0.0;
@@ -216,6 +302,48 @@ __device__ __forceinline__ double time_pass(const TimeParams &P, TimeMoving &M, 
         qs = live ? w : 0.0;
         qs = time_half_sum(qs);
       }
+      if constexpr (GX) {
+        // h_e = d pos / d (entry e), h_e' = d vel / d e, h_e'' = d acc / d e at t: the table's polynomials, plus
+        // 1, t, t^2 / 2 (and their derivatives) where the entry is a start value
+        double h[6], h1[6], h2[6];
+#pragma unroll
+        for (int e = 0; e < 6; ++e) {
+          const int j = e % 3;
+          const double st = is_start[e / 3];
+          const double b0 = j == 0 ? 1.0 : (j == 1 ? t : 0.5 * t2), b1 = j == 0 ? 0.0 : (j == 1 ? 1.0 : t);
+          const double b2 = j == 2 ? 1.0 : 0.0;
+          h[e] = (A3[e] * t3 + A4[e] * t4 + A5[e] * t5) + st * b0;
+          h1[e] = (3.0 * A3[e] * t2 + 4.0 * A4[e] * t3 + 5.0 * A5[e] * t4) + st * b1;
+          h2[e] = (6.0 * A3[e] * t + 12.0 * A4[e] * t2 + 20.0 * A5[e] * t3) + st * b2;
+        }
+        // the weights of d pos_k, d vel_k, d acc_k in the sample's cost: the consistent gradient's terms (gtop.h)
+        const double cdv = P.wc * (cd * dt), gw = P.wc * (gd * vn * dt);
+        double Sdyn = 0.0;
+        if (P.dyn) {
+#pragma unroll
+          for (int k = 0; k < 3; ++k)
+            Sdyn += P.alpha_v * exp((fabs(vel[k]) - P.v0) * P.inv_r_v) + P.alpha_a * exp((fabs(acc[k]) - P.a0) * P.inv_r_a);
+        }
+        double v18[18];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+          const double vk = vel[k] / vn;
+          double wp = gw * grad[k], wv = cdv * vk, wa = 0.0;
+          if (P.dyn) {
+            const double cv = P.alpha_v * exp((fabs(vel[k]) - P.v0) * P.inv_r_v);
+            const double ca = P.alpha_a * exp((fabs(acc[k]) - P.a0) * P.inv_r_a);
+            const double sv = (double)((vel[k] > 0.0) - (vel[k] < 0.0)), sa = (double)((acc[k] > 0.0) - (acc[k] < 0.0));
+            wv += cv * P.inv_r_v * sv * vn * dt + Sdyn * vk * dt;
+            wa = ca * P.inv_r_a * sa * vn * dt;
+          }
+          wp = live ? wp : 0.0;
+          wv = live ? wv : 0.0;
+          wa = live ? wa : 0.0;
+#pragma unroll
+          for (int e = 0; e < 6; ++e) v18[(e / 3) * 9 + k * 3 + e % 3] = wp * h[e] + wv * h1[e] + wa * h2[e];
+        }
+        gsum = time_half_spread18<true>(v18, i, 0.0);
+      }
       cs = live ? cs : 0.0;   // (past the loop bound, and the two idle lanes of a half: nothing reaches the sums)
       ds = live ? ds : 0.0;
       cs = time_half_sum(cs);
@@ -236,6 +364,32 @@ __device__ __forceinline__ double time_pass(const TimeParams &P, TimeMoving &M, 
           if constexpr (!MOV) o[5] = 0.0;
         }
       }
+    }
+    if constexpr (GX) {
+      // this lane's entry: the jerk term 2 ws (q3 dc3 + q4 dc4 + q5 dc5) first, the samples' sum second
+      const int sl = slot < 0 ? 0 : slot, part = sl / 9, k = (sl % 9) / 3, j = sl % 3, e = part * 3 + j;
+      double a3 = A3[0], a4 = A4[0], a5 = A5[0];
+#pragma unroll
+      for (int q = 1; q < 6; ++q) {
+        a3 = e == q ? A3[q] : a3;
+        a4 = e == q ? A4[q] : a4;
+        a5 = e == q ? A5[q] : a5;
+      }
+      const double j3 = k == 0 ? jq[0][0] : (k == 1 ? jq[1][0] : jq[2][0]);
+      const double j4 = k == 0 ? jq[0][1] : (k == 1 ? jq[1][1] : jq[2][1]);
+      const double j5 = k == 0 ? jq[0][2] : (k == 1 ? jq[1][2] : jq[2][2]);
+      const double mine = (j3 * a3 + j4 * a4 + j5 * a5) + gsum;
+      // part 0: the lower half's end part meets the upper half's start part (waypoint s0 + 1); part 1: the lower half's
+      // start part meets the end part carried from the pair before (waypoint s0)
+      const double other = __shfl_xor(mine, 32);
+      if (half == 0 && slot >= 0) {
+        if (part == 0) {
+          if (s0 + 1 < m) gx[k * ndp + 3 * s0 + j] = mine + other;
+        } else if (s0 > 0) {
+          gx[k * ndp + 3 * (s0 - 1) + j] = end_carry + mine;
+        }
+      }
+      end_carry = other;
     }
     // the cost: the segments' two parts in segment order, by every lane alike
     const double seg_cost = smooth + cs;

@@ -1,0 +1,396 @@
+"""include/gtop_joint.h on the GPU: the joint pass against gtop_time_gradient_device (bit for bit), against the
+evaluation's cost and consistent gradient and against the numpy twin (tests/joint_twin.py) on the library's own field,
+its bit-level laws, and the joint optimizer against its laws, the twin's run (oracle/mma_twin.minimize on z = [x | T])
+and the hand-derived case of tests/golden/JOINT_ANALYTIC.md.
+
+Criterion and tolerance of the comparisons: tests/test_gpu_time.py's — scenes.rel_err at 1e-5, the project's fp64
+parity bound, which covers a sample whose float rounding falls differently."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from grad_traj_optimization_amd import problem
+from tests import joint_cases as jc
+from tests import joint_twin as jt
+from tests import scenes
+from tests.test_gpu_time import DYN, _batch, _dev, _field, _special_rows
+
+pytestmark = pytest.mark.gpu
+TOL = 1e-5
+ERR_INVALID, ERR_STATE = 1, 4
+GUARD = -7.25
+
+
+@pytest.fixture(scope="module")
+def scene(gtop, oracle_mod):
+    mp = jc.scene_map()
+    ctx, sdf = _field(gtop, oracle_mod, mp)
+    yield mp, ctx, sdf
+    ctx.close()
+
+
+def _guarded(shapes):
+    import torch
+    bufs = [torch.full((int(np.prod(s)) + 16,), GUARD, dtype=torch.float64, device="cuda:0") for s in shapes]
+    views = [b[8:-8].view(*s) for b, s in zip(bufs, shapes)]
+    return bufs, views
+
+
+def _guards_hold(bufs):
+    import torch
+    return all(bool(torch.all(b[:8] == GUARD)) and bool(torch.all(b[-8:] == GUARD)) for b in bufs)
+
+
+def _joint(gtop, ctx, x, Df, Tt, parts=True):
+    """The joint pass into guarded buffers -> [cost, gx, gT, parts] (device tensors, cloned)."""
+    import torch
+    B, m = x.shape[0], x.shape[1] // 9 + 1
+    bufs, v = _guarded([(B,), (B, 9 * (m - 1)), (B, m), (B, m, 4)])
+    gtop.joint_gradient_device(ctx, x, Df, Tt, cost=v[0], gx=v[1], gT=v[2], parts=v[3] if parts else None)
+    torch.cuda.synchronize()
+    assert _guards_hold(bufs)
+    if not parts:
+        assert torch.all(bufs[3] == GUARD)
+    return [t.clone() for t in v]
+
+
+@pytest.mark.parametrize("B,m,shared_T,mode", [
+    (3, 2, False, "plain"), (65, 7, False, "plain"), (5, 13, False, "plain"), (2, 227, False, "plain"),
+    (130, 6, True, "plain"), (5, 13, False, "dyn"), (5, 13, False, "step1"), (5, 13, False, "signed"),
+    (5, 13, False, "ws0"), (65, 7, False, "dyn"), (65, 7, False, "step1"), (65, 7, False, "signed"), (65, 7, False, "ws0")])
+def test_gradient_against_the_time_pass_the_evaluation_and_the_twin(gtop, oracle_mod, scene, B, m, shared_T, mode):
+    import torch
+    mp, ctx, sdf = scene
+    if mode == "signed":
+        ctx, sdf = _field(gtop, oracle_mod, mp, signed=True)
+        assert ctx.field_sign()[0] and sdf.dist.min() < 0.0
+    extra = {"plain": {}, "signed": {}, "dyn": DYN, "step1": dict(DYN, step=1), "ws0": dict(ws=0.0)}[mode]
+    params = dict(gtop.OPTI_NODE_PARAMS, **extra)
+    b, T = _batch(B, m, mp, 3100 + 17 * m + B, shared_T)
+    if mode == "signed":   # waypoint 1 of every row sits deep inside an obstacle, where the signed field is negative
+        deep = np.argwhere(sdf.dist.reshape(mp.grid) < -0.15)
+        assert len(deep) >= B
+        x = b.x.reshape(B, 3, -1).copy()
+        x[:, :, 0] = (deep[:: len(deep) // B][:B] + 0.5) * mp.resolution + mp.origin
+        b = problem.Batch(b.waypoints, b.T, b.Df, x.reshape(B, -1), m)
+    xt, Dft, Tt = _dev(b.x, b.Df.reshape(-1, 18), T)
+    try:
+        ctx.set_params(**extra)
+        c, gx, gT, p = _joint(gtop, ctx, xt, Dft, Tt)
+        ct_, gt_, pt_ = gtop.time_gradient_device(ctx, xt, Dft, Tt, want_parts=True)
+        ctx.set_gradient_mode(True)
+        ce, ge = ctx.eval_device(xt, Dft, Tt)
+        torch.cuda.synchronize()
+    finally:
+        ctx.set_gradient_mode(False)
+        ctx.set_params()
+    assert torch.equal(c, ct_) and torch.equal(gT, gt_) and torch.equal(p, pt_)          # bit for bit
+    assert not torch.any(gx == GUARD) and torch.all(torch.isfinite(gx))
+    c, gx, ce, ge = (t.cpu().numpy() for t in (c, gx, ce, ge))
+    r_cost, r_eval = scenes.rel_err(c, gx, ce, ge - 1e-5)
+    rows = np.arange(B) if B <= 6 else np.r_[0:3, B - 3:B]
+    Tb = np.broadcast_to(T, (B, m))
+    c_ref, gx_ref, _, _ = jt.gradient_batch(Tb[rows], b.Df[rows], b.x[rows], sdf, params)
+    r_ctwin, r_twin = scenes.rel_err(c[rows], gx[rows], c_ref, gx_ref)
+    print(f"B={B} m={m} {mode}: cost against eval_device {r_cost:.2e}; gx against the consistent gradient - 1e-5 "
+          f"{r_eval:.2e}; against the twin cost {r_ctwin:.2e} gx {r_twin:.2e}")
+    assert r_cost <= TOL and r_eval <= TOL and r_ctwin <= TOL and r_twin <= TOL
+    if mode == "signed":
+        ctx.close()
+
+
+def test_out_of_map_and_replay_rows(gtop, scene):
+    mp, ctx, sdf = scene
+    b, T = _special_rows(mp)
+    xt, Dft, Tt = _dev(b.x, b.Df.reshape(-1, 18), T)
+    c, gx, gT, p = (t.cpu().numpy() for t in _joint(gtop, ctx, xt, Dft, Tt))
+    assert all(np.all(np.isfinite(a)) for a in (c, gx, gT, p))
+    c_ref, gx_ref, gT_ref, p_ref = jt.gradient_batch(T, b.Df, b.x, sdf, dict(gtop.OPTI_NODE_PARAMS))
+    rc, rg = scenes.rel_err(c, gx, c_ref, gx_ref)
+    _, rt = scenes.rel_err(c, gT, c_ref, gT_ref)
+    _, rp = scenes.rel_err(c, p, c_ref, p_ref)
+    print(f"out-of-map and replay rows against the twin: cost {rc:.2e} gx {rg:.2e} gT {rt:.2e} parts {rp:.2e}")
+    assert rc <= TOL and rg <= TOL and rt <= TOL and rp <= TOL
+
+
+def test_bit_level_laws(gtop, scene):
+    """One derivative under both gradient modes; a row's bits do not depend on the batch, its place or the time stride;
+    parts NULL changes nothing; a NaN row disturbs only itself; guard words stay and no output entry is left at the
+    guard; the host form gives the device form's bits."""
+    import torch
+    mp, ctx, sdf = scene
+    b, T = _special_rows(mp)
+    m = 5
+    x, Df, Tt = _dev(b.x, b.Df.reshape(-1, 18), T)
+    base = _joint(gtop, ctx, x, Df, Tt)
+    assert not any(bool(torch.any(t == GUARD)) for t in base)
+    try:
+        ctx.set_gradient_mode(True)
+        cons = _joint(gtop, ctx, x, Df, Tt)
+    finally:
+        ctx.set_gradient_mode(False)
+    assert all(torch.equal(a, c) for a, c in zip(base, cons))
+    nop = _joint(gtop, ctx, x, Df, Tt, parts=False)
+    assert all(torch.equal(nop[k], base[k]) for k in range(3))
+    r = 2
+    alone = _joint(gtop, ctx, x[r:r + 1].contiguous(), Df[r:r + 1].contiguous(), Tt[r:r + 1].contiguous())
+    shared = _joint(gtop, ctx, x[r:r + 1].contiguous(), Df[r:r + 1].contiguous(), Tt[r].contiguous())
+    big, _ = _batch(130, m, mp, 4300)
+    for place in (0, 129, 77):
+        xb, Dfb, Tb = _dev(big.x, big.Df.reshape(-1, 18), big.T)
+        xb[place], Dfb[place], Tb[place] = x[r], Df[r], Tt[r]
+        got = _joint(gtop, ctx, xb, Dfb, Tb)
+        for k in range(4):
+            assert torch.equal(got[k][place], base[k][r]), (place, k)
+    for k in range(4):
+        assert torch.equal(alone[k][0], base[k][r]) and torch.equal(shared[k][0], base[k][r])
+    xn = x.clone()
+    xn[3, 4] = float("nan")
+    bad = _joint(gtop, ctx, xn, Df, Tt)
+    for k in range(4):
+        assert torch.equal(bad[k][:3], base[k][:3])
+    ctx.set_problem(T, b.Df)
+    host = gtop.joint_gradient_batch(ctx, b.x)
+    for k in range(4):
+        assert np.array_equal(host[k], base[k].cpu().numpy()), k
+
+
+def _optimize(gtop, ctx, opts, b, T, lb, ub, T_lo=None, work=None):
+    """The joint optimizer into guarded buffers -> (x_out, T_out, info) as numpy arrays."""
+    import torch
+    B, m = b.x.shape[0], b.m
+    x, Df, Tt, lbt, ubt = _dev(b.x, b.Df.reshape(-1, 18), T, lb, ub)
+    bufs, (xv, T_out, info) = _guarded([(B, 9 * (m - 1)), (B, m), (B, 8)])
+    xv.copy_(x)
+    lo = None if T_lo is None else _dev(T_lo)[0]
+    gtop.optimize_joint_device(ctx, opts, xv, Df, Tt, lbt, ubt, T_lo=lo, T_out=T_out, info=info, work=work)
+    torch.cuda.synchronize()
+    assert _guards_hold(bufs) and not torch.any(T_out == GUARD) and not torch.any(info == GUARD)
+    return xv.cpu().numpy(), T_out.cpu().numpy(), info.cpu().numpy()
+
+
+@pytest.mark.parametrize("m", sorted(jc.SERIAL_SEEDS))
+def test_optimizer_follows_the_serial_restatement(gtop, scene, m):
+    """x_out, T_out and F against oracle/mma_twin.minimize on z with the twin's F and gradient, at 1e-6 relative (the
+    tolerance of test_gpu_swarm.py for the same kind of comparison); the rows have no decision within 1e-6 of a tie
+    (tests/test_joint_twin.py)."""
+    mp, ctx, sdf = scene
+    b, lb, ub, T_lo = jc.serial_case(m, mp)
+    o = jc.SERIAL_OPT
+    xs, Ts, info = _optimize(gtop, ctx, gtop.GtopJointOpt(**o), b, b.T, lb, ub, T_lo)
+    for i in range(jc.SERIAL_B):
+        x_ref, T_ref, i_ref, _ = jt.optimize(b.T[i], b.Df[i], b.x[i], sdf, dict(gtop.OPTI_NODE_PARAMS), lb[i], ub[i], o["rho"],
+                                             o["t_min"], o["t_max"], o["max_evals"], T_lo=T_lo[i])
+        dx = np.max(np.abs(xs[i] - x_ref)) / max(1.0, np.max(np.abs(x_ref)))
+        dT = np.max(np.abs(Ts[i] - T_ref)) / max(1.0, np.max(np.abs(T_ref)))
+        dF = abs(info[i, 3] - i_ref[3]) / abs(i_ref[3])
+        print(f"m={m} row {i}: x {dx:.2e}, T {dT:.2e}, F {dF:.2e} off the twin's run; F {info[i, 2]:.4f} -> {info[i, 3]:.4f}")
+        assert dx <= 1e-6 and dT <= 1e-6 and dF <= 1e-6
+        assert np.array_equal(info[i, :2], i_ref[:2]) and abs(info[i, 2] - i_ref[2]) <= 1e-6 * abs(i_ref[2])
+        assert Ts[i, 1] == T_lo[i, 1]
+
+
+@pytest.mark.parametrize("B,m", [(3, 2), (65, 7), (2, 227)])
+def test_optimizer_laws(gtop, scene, B, m):
+    """Bounds exact, pinned segments bit for bit, info[4] the gradient entry's cost at the output bit for bit, F never
+    above its start, codes and counts consistent, the host form's bits; with every T pinned and rho = 0 the run follows
+    optimize_device_ex (fusion 0, consistent mode) at 1e-6 over 12 evaluations."""
+    import torch
+    mp, ctx, sdf = scene
+    b, T = _batch(B, m, mp, 6100 + m + B)
+    lb, ub = gtop.GtopContext.default_bounds(b.waypoints)
+    evals = 12
+    o = dict(rho=2.0, t_min=0.0301 if m > 100 else 0.1, t_max=4.0, max_evals=evals)
+    T_lo = np.zeros((B, m))
+    T_lo[:, 0] = 0.01                    # below t_min
+    T_lo[:, 1] = o["t_max"] + 1.0        # pinned above t_max
+    if m > 2:
+        T_lo[:, 2] = 1.05 * T[:, 2]      # active: above the start point
+    for lo in (None, T_lo):
+        xs, Ts, info = _optimize(gtop, ctx, gtop.GtopJointOpt(**o), b, T, lb, ub, lo)
+        assert all(np.all(np.isfinite(a)) for a in (xs, Ts, info))
+        assert np.all(xs >= lb) and np.all(xs <= ub)
+        lob = np.full_like(Ts, o["t_min"]) if lo is None else np.maximum(o["t_min"], lo)
+        pinned = lob > o["t_max"]
+        assert np.array_equal(Ts[pinned], lob[pinned])
+        assert np.all(Ts[~pinned] >= lob[~pinned]) and np.all(Ts[~pinned] <= o["t_max"])
+        assert np.all(info[:, 3] <= info[:, 2]) and np.any(info[:, 3] < info[:, 2])
+        assert np.all(np.isin(info[:, 0], (3, 4, 5))) and np.all(info[:, 1] >= 1) and np.all(info[:, 1] <= evals)
+        assert np.all(info[info[:, 0] == 5, 1] == evals) and np.all(info[:, 6:] >= 0)
+        xo, Dft, To = _dev(xs, b.Df.reshape(-1, 18), Ts)
+        c, _, _, _ = gtop.joint_gradient_device(ctx, xo, Dft, To)
+        torch.cuda.synchronize()
+        assert np.array_equal(c.cpu().numpy(), info[:, 4])                             # bit for bit
+        assert np.max(np.abs(info[:, 3] - (info[:, 4] + o["rho"] * Ts.sum(1))) / np.abs(info[:, 3])) <= 1e-13
+        assert np.max(np.abs(info[:, 5] - Ts.sum(1)) / Ts.sum(1)) <= 1e-14
+    # the stop rules: loose tolerances stop rows before the cap
+    _, _, i_tol = _optimize(gtop, ctx, gtop.GtopJointOpt(**dict(o, ftol_rel=0.3, xtol_rel=1.5)), b, T, lb, ub, T_lo)
+    assert np.all(np.isin(i_tol[:, 0], (3, 4, 5))) and np.all(i_tol[i_tol[:, 0] != 5, 1] < evals)
+    assert np.all(i_tol[i_tol[:, 0] == 5, 1] == evals)
+    if B >= 65:
+        assert np.any(i_tol[:, 0] != 5)                          # (among 65 rows some stop early)
+    # the host form: the same bits
+    ctx.set_problem(T, b.Df)
+    Bh = min(B, 9)
+    xh, Th, ih = gtop.optimize_joint(ctx, gtop.GtopJointOpt(**o), b.x[:Bh], lb[:Bh], ub[:Bh], T_lo[:Bh])
+    assert np.array_equal(xh, xs[:Bh]) and np.array_equal(Th, Ts[:Bh]) and np.array_equal(ih, info[:Bh])
+    # every T pinned, rho = 0: the x half alone, as optimize_device_ex runs it
+    if m > 118:
+        return                                                   # (optimize_device_ex serves up to 118 segments)
+    pin = dict(o, rho=0.0, t_min=0.0301, t_max=0.0301)
+    xp, Tp, ip = _optimize(gtop, ctx, gtop.GtopJointOpt(**pin), b, T, lb, ub, T)
+    assert np.array_equal(Tp, T)
+    try:
+        ctx.set_gradient_mode(True)
+        ctx.set_optimizer_fusion(0)
+        xe, Dft, Tt, lbt, ubt = _dev(b.x, b.Df.reshape(-1, 18), T, lb, ub)
+        xe, ce, ne, code = ctx.optimize_device_ex(xe, Dft, Tt, lbt, ubt, evals)
+        torch.cuda.synchronize()
+    finally:
+        ctx.set_gradient_mode(False)
+        ctx.set_optimizer_fusion(2)                                   # (the default)
+    xe, ce = xe.cpu().numpy(), ce.cpu().numpy()
+    dx = np.max(np.abs(xp - xe), axis=1) / np.maximum(1.0, np.max(np.abs(xe), axis=1))
+    dF = np.abs(ip[:, 3] - ce) / np.abs(ce)
+    print(f"B={B} m={m}, every T pinned: x {dx.max():.2e}, F {dF.max():.2e} off optimize_device_ex")
+    assert np.all(dx <= 1e-6) and np.all(dF <= 1e-6)
+
+
+def test_optimizer_reaches_the_analytic_optimum(gtop, scene):
+    """tests/golden/JOINT_ANALYTIC.md: after its budget the device stands no further from F* than the margin the
+    document states over the twin's measured distance."""
+    mp, ctx, sdf = scene
+    Df, x0, lb, ub = jc.analytic_case()
+    ans = jc.analytic_answer()
+    b = problem.Batch(None, None, Df[None], x0[None], 2)
+    T = np.array([jc.ANALYTIC_START_T])
+    try:
+        ctx.set_params(ws=jc.ANALYTIC["ws"], wc=0.0)
+        xs, Ts, info = _optimize(gtop, ctx, gtop.GtopJointOpt(**jc.ANALYTIC_OPT), b, T, lb[None], ub[None])
+    finally:
+        ctx.set_params()
+    gap = (info[0, 3] - 1e-3 - ans["F"]) / ans["F"]
+    print(f"(F - F*) / F* = {gap:.3e} (the twin: {jc.ANALYTIC_TWIN_GAP:.3e}); T = {Ts[0]}, v = {xs[0, 1]:.6f} "
+          f"(v* = {ans['v']:.6f}), a = {xs[0, 2]:.2e}")
+    assert -1e-12 <= gap <= jc.ANALYTIC_MARGIN * jc.ANALYTIC_TWIN_GAP
+    assert xs[0, 0] == jc.ANALYTIC["L"] / 2 and np.all(xs[0, 3:] == 0.0)
+    assert np.max(np.abs(Ts[0] - ans["T"])) <= 0.02 * ans["tau"] and abs(xs[0, 1] - ans["v"]) <= 0.01 * ans["v"]
+
+
+def test_one_captured_graph_replays_the_eager_bits(gtop, scene):
+    """joint optimise -> coefficients -> validate_device, captured once, replayed twice."""
+    import torch
+    mp, ctx, sdf = scene
+    B, m = 40, 6
+    b, T = _batch(B, m, mp, 6500)
+    lb, ub = gtop.GtopContext.default_bounds(b.waypoints)
+    x0, Df, Tt, lbt, ubt = _dev(b.x, b.Df.reshape(-1, 18), T, lb, ub)
+    opts = gtop.GtopJointOpt(rho=2.0, t_min=0.1, t_max=4.0, max_evals=8)
+    work = torch.zeros(gtop.joint_workspace_bytes(B, m), dtype=torch.uint8, device="cuda:0")
+    T_out = torch.zeros((B, m), dtype=torch.float64, device="cuda:0")
+    info = torch.zeros((B, 8), dtype=torch.float64, device="cuda:0")
+    coeff = torch.zeros((B, m, 18), dtype=torch.float64, device="cuda:0")
+    report = torch.zeros((B, len(ctx.TRAJ_REPORT)), dtype=torch.float64, device="cuda:0")
+    lim = gtop.GtopLimits()
+
+    def cycle(xw):
+        gtop.optimize_joint_device(ctx, opts, xw, Df, Tt, lbt, ubt, T_out=T_out, info=info, work=work)
+        ctx.coefficients_device(xw, Df, T_out, coeff=coeff)
+        return ctx.validate_device(coeff, T_out, lim, report=report)
+
+    xe = x0.clone()
+    rep_e = cycle(xe)
+    torch.cuda.synchronize()
+    want = [t.clone() for t in (xe, T_out, info, coeff, rep_e)]
+    assert not torch.equal(want[1], Tt) and not torch.equal(xe, x0)
+    for t in (T_out, info, coeff, work, report):
+        t.zero_()
+    xg = x0.clone()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        rep_g = cycle(xg)
+    for _ in range(2):
+        xg.copy_(x0)
+        graph.replay()
+        torch.cuda.synchronize()
+        for k, (a, w) in enumerate(zip((xg, T_out, info, coeff, rep_g), want)):
+            assert torch.equal(a, w), k
+
+
+def test_refusals_launch_nothing(gtop, scene):
+    import torch
+    from grad_traj_optimization_amd import joint as gj
+    mp, ctx, sdf = scene
+    L = gj.joint_library()
+    B, m = 3, 4
+    b, T = _batch(B, m, mp, 5600)
+    lb, ub = gtop.GtopContext.default_bounds(b.waypoints)
+    x, Df, Tt, lbt, ubt = _dev(b.x, b.Df.reshape(-1, 18), T, lb, ub)
+    n = 9 * (m - 1)
+    nwork = gj.joint_workspace_bytes(B, m)
+    outs = [torch.full((k,), GUARD, dtype=torch.float64, device="cuda:0")
+            for k in (B, B * n, B * m, B * m * 4, B * m, B * 8, nwork // 8)]
+    pc, pgx, pg, pp, pT, pi, pw = (t.data_ptr() for t in outs)
+    xw = x.clone()
+    px, pD, pTt, plb, pub = xw.data_ptr(), Df.data_ptr(), Tt.data_ptr(), lbt.data_ptr(), ubt.data_ptr()
+    OPT = dict(rho=2.0, t_min=0.1, t_max=4.0, ftol_rel=1e-7, xtol_rel=1e-9, max_evals=5)
+    ok = gj.GtopJointOpt(**OPT)
+
+    def grad(B=B, m=m, px=px, pD=pD, pT_=pTt, stride=m, pc=pc, pgx=pgx, pg=pg):
+        return L.gtop_joint_gradient_device(ctx._h, B, m, px, pD, pT_, stride, pc, pgx, pg, pp, None)
+
+    def opt(o=ok, B=B, m=m, px=px, pD=pD, pT_=pTt, stride=m, plb=plb, pub=pub, plo=None, pout=pT, pinfo=pi, pw=pw,
+            nw=nwork):
+        return L.gtop_optimize_joint_device(ctx._h, None if o is None else C.byref(o), B, m, px, pD, pT_, stride, plb, pub,
+                                            plo, pout, pinfo, pw, nw, None)
+
+    for rc in (grad(m=1), grad(m=228), grad(B=-1), grad(stride=3), grad(stride=1), grad(px=None), grad(pD=None),
+               grad(pT_=None), grad(pc=None), grad(pgx=None), grad(pg=None),
+               opt(m=1), opt(m=228), opt(B=-1), opt(stride=2), opt(px=None), opt(pD=None), opt(pT_=None), opt(plb=None),
+               opt(pub=None), opt(pout=None), opt(pinfo=None), opt(pw=None), opt(o=None), opt(pout=pTt),
+               opt(nw=nwork - 1), opt(nw=0)):
+        assert rc == ERR_INVALID
+    for bad in (dict(reserved=1), dict(rho=-1.0), dict(rho=np.nan), dict(rho=np.inf), dict(t_min=0.03), dict(t_min=np.nan),
+                dict(t_min=5.0, t_max=4.0), dict(t_max=np.inf), dict(t_max=np.nan), dict(ftol_rel=-1e-3),
+                dict(ftol_rel=np.nan), dict(xtol_rel=-1.0), dict(xtol_rel=np.nan), dict(max_evals=0), dict(max_evals=-3)):
+        assert opt(o=gj.GtopJointOpt(**dict(OPT, **bad))) == ERR_INVALID, bad
+        with pytest.raises(gtop.GtopError) as e:
+            gtop.optimize_joint_device(ctx, gj.GtopJointOpt(**dict(OPT, **bad)), xw, Df, Tt, lbt, ubt)
+        assert e.value.code == ERR_INVALID
+    assert grad(B=0) == 0 and opt(B=0) == 0
+    # fp32 optimizer precision: the optimizer refuses, the gradient serves
+    try:
+        ctx.set_optimizer_precision("f32")
+        assert opt() == ERR_STATE
+    finally:
+        ctx.set_optimizer_precision("f64")
+    # the moving-obstacle cost switched on: GTOP_ERR_STATE from every entry, boxes or not
+    ctx.set_problem(T, b.Df)
+    try:
+        ctx.set_moving_cost(True)
+        assert grad() == ERR_STATE and opt() == ERR_STATE
+        for call in (lambda: gtop.joint_gradient_batch(ctx, b.x), lambda: gtop.optimize_joint(ctx, ok, b.x, lb, ub)):
+            with pytest.raises(gtop.GtopError) as e:
+                call()
+            assert e.value.code == ERR_STATE
+    finally:
+        ctx.set_moving_cost(False)
+    # no parameters, no field: a fresh context
+    fresh = gtop.GtopContext(device=0)
+    try:
+        def on(h):
+            return (L.gtop_joint_gradient_device(h, B, m, px, pD, pTt, m, pc, pgx, pg, pp, None),
+                    L.gtop_optimize_joint_device(h, C.byref(ok), B, m, px, pD, pTt, m, plb, pub, None, pT, pi, pw, nwork, None))
+        assert on(fresh._h) == (ERR_STATE, ERR_STATE)
+    finally:
+        fresh.close()
+    torch.cuda.synchronize()
+    assert all(bool(torch.all(t == GUARD)) for t in outs) and torch.equal(xw, x)
+    with pytest.raises(ValueError):
+        gtop.joint_gradient_device(ctx, x, Df, Tt, gx=outs[0])
+    with pytest.raises(ValueError):
+        gtop.optimize_joint_device(ctx, ok, xw, Df, Tt, lbt, ubt, T_lo=outs[0])
+    assert opt(o=gj.GtopJointOpt(**dict(OPT, t_min=0.0301, t_max=0.0301))) == 0     # the limits themselves are legal
+    assert grad() == 0 and opt() == 0                                                # and the context still serves
+    torch.cuda.synchronize()
