@@ -537,6 +537,16 @@ class GtopContext(_HostProblem):
         self._chk(self._L.gtop_edt_query_device(self._h, N, ppos, ptime, pdist, pgrad, _stream(stream, pos)))
         return dist, grad
 
+    def edt_coarse_query_device(self, pos, time, stream=None):
+        """torch fp64 CUDA tensors pos (N, 3), time (N,) -> dist (N,): edt_coarse_query on the device; asynchronous."""
+        if pos.dim() != 2 or pos.shape[1] != 3:
+            raise ValueError(f"pos: expected shape (N, 3), got {tuple(pos.shape)}")
+        N = pos.shape[0]
+        ppos, ptime = self._dev("pos", pos, N * 3), self._dev("time", time, N)
+        dist, pdist = self._out("dist", None, (N,), pos)
+        self._chk(self._L.gtop_edt_coarse_query_device(self._h, N, ppos, ptime, pdist, _stream(stream, pos)))
+        return dist
+
     # -- trajectory safety report and best-candidate selection (include/gtop.h) --
     TRAJ_REPORT = ("n_samples", "clearance", "clearance_t", "clearance_index", "n_below_margin", "first_below_t",
                    "n_out_of_map", "max_vel_norm", "max_acc_norm", "max_vel_axis", "max_acc_axis", "time_sum")

@@ -174,6 +174,8 @@ def _cases():
         Case("clock_stamp", lambda: dict(minmax=t("minmax", (2,), I64)), "gtop_device_clock_stamp", (h, p("minmax"))),
         Case("edt_query_device", lambda: dict(pos=t("pos", (4, 3)), time=t("time", (4,))),
              "gtop_edt_query_device", (h, 4, p("pos"), p("time"), p("new0"), p("new1"))),
+        Case("edt_coarse_query_device", lambda: dict(pos=t("pos", (4, 3)), time=t("time", (4,))),
+             "gtop_edt_coarse_query_device", (h, 4, p("pos"), p("time"), p("new0"))),
         Case("setup_paths_device", lambda: dict(waypoints=t("waypoints", (B, M + 1, 3)), mean_v=1.5, init_time=0.25,
                                                 T=t("T", (B, M)), Df=t("Df", (B, 18)), x0=t("x0", (B, N))),
              "gtop_setup_paths_device", (h, B, M, p("waypoints"), 1.5, 0.25, p("T"), p("Df"), p("x0")),
@@ -255,7 +257,7 @@ by_id = dict(ids=lambda c: c.id)
 def test_the_table_covers_every_method_that_takes_a_device_tensor():
     with_stream = {name for name, f in GtopContext.__dict__.items()
                    if isinstance(f, types.FunctionType) and "stream" in f.__code__.co_varnames[:f.__code__.co_argcount]}
-    assert len(with_stream) == 17
+    assert len(with_stream) == 18
     assert {c.method for c in CASES} == with_stream | {"set_sdf_device", "set_start_times_device"}
 
 
@@ -266,7 +268,8 @@ def test_call_record(case, allocations):
     want = case.expect + ((STREAM,) if case.has_stream else ())
     assert ctx._L.calls == [(case.entry, want)]
     assert all(fn == "empty" and device == torch.device("cuda", 0) for fn, _, _, device in allocations)
-    internal = {"edt_query_device": [((4,), F64), ((4, 3), F64)], "optimize_device_ex": [((B,), F64), ((B,), I32), ((B,), I32)],
+    internal = {"edt_query_device": [((4,), F64), ((4, 3), F64)], "edt_coarse_query_device": [((4,), F64)],
+                "optimize_device_ex": [((B,), F64), ((B,), I32), ((B,), I32)],
                 "select_best_device": [((B,), U8)] if case.args().get("want_pass", True) else []}
     assert [(shape, dtype) for _, shape, dtype, _ in allocations] == internal.get(case.method, [])
 
