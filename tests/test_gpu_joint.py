@@ -4,7 +4,11 @@ its bit-level laws, and the joint optimizer against its laws, the twin's run (or
 and the hand-derived case of tests/golden/JOINT_ANALYTIC.md.
 
 Criterion and tolerance of the comparisons: tests/test_gpu_time.py's — scenes.rel_err at 1e-5, the project's fp64
-parity bound, which covers a sample whose float rounding falls differently."""
+parity bound, which covers a sample whose float rounding falls differently.
+
+That criterion is normwise and, in a batch of more than six rows, looks at six of them (the twins are pure-Python loops).  Every row and every entry — the cost, each gT_s, each parts column and each gx entry — is held at rounding-error level by
+tests/test_gpu_time_entrywise.py against tests/time_entry_ref.py (whose magnitudes tests/test_time_entrywise_bound.py holds
+against 40-digit arithmetic)."""
 import ctypes as C
 
 import numpy as np
