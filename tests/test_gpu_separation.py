@@ -82,8 +82,8 @@ def start_times_of(kind, B, seed, nowhere=None):
 
 
 # (B, n_samples, m, shared T, start times, hold_ends, source, the row flown nowhere).  B: 1, 2, one below / at / one
-# above the tile edge, two tiles plus 2; n_samples: 1, one below / at / one above the chunk, three chunks plus 1;
-# m: 2, 3, 13 (6 from the scene)
+# above the tile edge, two tiles plus 2; n_samples: 1, one below / at / one above the chunk, three chunks plus 1, and
+# 16 400 and 5 480, past the sample kernel's grid; m: 2, 3, 13 (6 from the scene)
 CASES = [
     (1, 1, 2, False, "none", False, "random", None),
     (2, CHUNK - 1, 3, True, "one", True, "random", None),
@@ -95,6 +95,11 @@ CASES = [
     (2 * TILE + 2, 1, 2, False, "one", True, "random", None),
     (TILE + 1, 3 * CHUNK + 1, 6, False, "rows", False, "scene", None),
     (2 * TILE + 2, CHUNK, 6, False, "rows", True, "scene", 5),
+    # the sample kernel's stride loop (csrc/gtop_sep_sample.h: more than 4096 blocks of 4 samples over the tiles), on one
+    # tile of rows and on three with a padded last one: the edges of tests/swarm_limit_cases.py where pair_min and the
+    # row summaries read the positions
+    (3, 16400, 3, False, "rows", False, "random", None),
+    (2 * TILE + 2, 5480, 3, False, "rows", False, "random", 2 * TILE),
 ]
 
 

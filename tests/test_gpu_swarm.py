@@ -2,7 +2,11 @@
 (tests/swarm_twin.py): S, the gradient and the active count bit for bit at the tile, chunk and padding edges of the
 kernels, joint and frozen; the invariances a row's figures must have; every refusal; the swarm optimizer against
 gtop_optimize_device_ex (w = 0), against the serial restatement (oracle/mma_twin.py on the oracle's cost plus the twin's
-frozen term), on three robots whose plans cross, and captured into a graph."""
+frozen term), on three robots whose plans cross, and captured into a graph.
+
+The shapes here stop at m = 7 and n_samples = 257.  The branches only longer rows and longer grids reach — the later
+passes and stages of the rows kernel, the sample kernel's stride loop, m = 227, 65 536 samples — and the `add` form the
+optimizer's rounds use are held by tests/test_gpu_swarm_limits.py on the table of tests/swarm_limit_cases.py."""
 import numpy as np
 import pytest
 
@@ -70,8 +74,8 @@ def grid_for(T, t0, n):
     return 0.01, span / max(n - 1, 1) * 1.05
 
 
-# every B, m, n_samples, T form, start-time count and hold_ends of the issue; the three edges (a tile and a row more,
-# a chunk and a sample more, a padded last tile) meet in the cases with B = 65, n = 257
+# every T form, start-time count and hold_ends; the three edges (a tile and a row more, a chunk and a sample more, a
+# padded last tile) meet in the cases with B = 65, n = 257 (the limits of m and n_samples: tests/test_gpu_swarm_limits.py)
 CASES = [(1, 2, 1, False, 0, 0, False), (2, 3, 7, True, 1, 1, True), (3, 6, 8, False, "B", 0, False),
          (63, 7, 9, False, 0, 1, True), (64, 2, 64, True, "B", 0, False), (65, 3, 257, False, 1, 0, True),
          (65, 6, 257, True, "B", 1, False), (130, 6, 9, False, "B", 1, True), (130, 7, 64, True, 0, 0, False)]
@@ -323,16 +327,32 @@ def test_w_zero_is_the_batched_optimizer(gtop, scene):
         ctx.set_optimizer_fusion(2)
 
 
+def gathered_waypoints(mp, B, m, rng, inside=False):
+    """Waypoints (B, m + 1, 3) of B robots brought together: every path of make_trajectories shifted so that its middle
+    lies near the map's centre.  inside: then moved back as far as it left the margin the paths were drawn in (a long
+    random walk fills the map, and shifted by its mean a part of it would lie outside)."""
+    b = problem.make_trajectories(B, m, mp, seed=50 + m)
+    centre = np.array(mp.origin) + 0.5 * np.array(mp.map_size)
+    wp = b.waypoints - b.waypoints.mean(axis=1, keepdims=True) + centre + rng.uniform(-0.3, 0.3, (B, 1, 3))
+    if inside:
+        lo, hi = np.array(mp.origin) + 1.0, np.array(mp.origin) + np.array(mp.map_size) - 1.0
+        wp = wp + np.maximum(lo - wp.min(axis=1, keepdims=True), 0.0) + np.minimum(hi - wp.max(axis=1, keepdims=True), 0.0)
+    return wp
+
+
 @pytest.mark.parametrize("m", [3, 6])
 def test_optimizer_follows_the_serial_restatement(gtop, scene, oracle_mod, m):
+    follows_the_serial_restatement(gtop, scene, oracle_mod, m, B=4, sweeps=2, evals=12, n=48)
+
+
+def follows_the_serial_restatement(gtop, scene, oracle_mod, m, B, sweeps, evals, n, inside=False):
+    """(shared with tests/test_gpu_swarm_limits.py, which runs it at the segment counts of the rows kernel's later
+    passes)"""
     mp, ctx, sdf = scene
-    B, sweeps, evals, n = 4, 2, 12, 48
     w, radius = 40.0, 1.5
-    b = problem.make_trajectories(B, m, mp, seed=50 + m)
-    # the four robots brought together: every path shifted so that its middle lies near the map's centre
-    centre = np.array(mp.origin) + 0.5 * np.array(mp.map_size)
+    # the robots brought together: every path shifted so that its middle lies near the map's centre
     rng = np.random.default_rng(m)
-    wp = b.waypoints - b.waypoints.mean(axis=1, keepdims=True) + centre + rng.uniform(-0.3, 0.3, (B, 1, 3))
+    wp = gathered_waypoints(mp, B, m, rng, inside)
     T = problem.segment_times(wp)
     Df, Dp = problem.initial_derivatives(wp)
     x0 = Dp.reshape(B, -1) + rng.normal(0.0, 0.05, (B, 9 * (m - 1)))
@@ -369,6 +389,7 @@ def test_optimizer_follows_the_serial_restatement(gtop, scene, oracle_mod, m):
         assert np.max(np.abs(xs[i] - x[i])) <= 1e-6 * max(1.0, np.max(np.abs(x[i]))), i
         assert np.all(xs[i] >= lb[i] - 1e-12) and np.all(xs[i] <= ub[i] + 1e-12)
         assert costs[i] <= f_start[i] * (1 + 1e-6)                           # never worse than the last sweep's start
+    return costs, f_start
 
 
 def crossing_robots(mp):

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from tests import separation_twin as st
+from tests import swarm_limit_cases as lc
 from tests import swarm_twin as sw
 
 H = Fraction(1, 2 ** 30)
@@ -133,25 +134,50 @@ def test_the_D_table_is_the_coefficient_formula_differentiated():
                     assert all(v == 0 for a in other for v in d[0, s, 6 * a:6 * a + 6])
 
 
+def float_against_exact(x, Df, T, fz, t0, o):
+    """The float twin within KAPPA u of the exact one on every entry of S and the gradient, against the magnitudes;
+    returns (the worst ratio, the active terms)."""
+    worst = 0.0
+    ce = sw.coefficients(x, Df, T, sw.EXACT)
+    cf = np.asarray(ce, dtype=np.float64)   # the coefficients rounded once: both twins start from the same rows
+    ff = None if fz is None else np.asarray(fz, dtype=np.float64)
+    exact = sw.swarm_terms(cf, T, t0, frozen=ff, N=sw.EXACT, **o)
+    flt = sw.swarm_terms(cf, T, t0, frozen=ff, N=sw.FLOAT, **o)
+    mag = sw.swarm_terms(cf, T, t0, frozen=ff, N=sw.EXACT, mag=True, **o)
+    assert np.array_equal(exact[2], flt[2]) and exact[2].sum() > 0   # the same active terms
+    for e, f, mg in ((exact[0], flt[0], mag[0]), (exact[1].reshape(-1), flt[1].reshape(-1), mag[1].reshape(-1))):
+        for ev, fv, mv in zip(e, f, mg):
+            err = abs(Fraction(float(fv)) - ev)
+            assert err <= KAPPA * Fraction(U64) * mv, (o["n"], o["hold_ends"], float(err), float(mv))
+            if mv > 0:
+                worst = max(worst, float(err / (Fraction(U64) * mv)))
+    return worst, int(exact[2].sum())
+
+
 def test_float_twin_against_the_exact_one_entrywise():
     worst = 0.0
     for m, hold, frozen, t0_kind, seed in FD_CASES:
-        x, Df, T, fz, t0, o = fd_case(m, hold, frozen, t0_kind, seed)
-        ce = sw.coefficients(x, Df, T, sw.EXACT)
-        cf = np.asarray(ce, dtype=np.float64)   # the coefficients rounded once: both twins start from the same rows
-        ff = None if fz is None else np.asarray(fz, dtype=np.float64)
-        exact = sw.swarm_terms(cf, T, t0, frozen=ff, N=sw.EXACT, **o)
-        flt = sw.swarm_terms(cf, T, t0, frozen=ff, N=sw.FLOAT, **o)
-        mag = sw.swarm_terms(cf, T, t0, frozen=ff, N=sw.EXACT, mag=True, **o)
-        assert np.array_equal(exact[2], flt[2]) and exact[2].sum() > 0   # the same active terms
-        for e, f, mg in ((exact[0], flt[0], mag[0]), (exact[1].reshape(-1), flt[1].reshape(-1), mag[1].reshape(-1))):
-            for ev, fv, mv in zip(e, f, mg):
-                err = abs(Fraction(float(fv)) - ev)
-                assert err <= KAPPA * Fraction(U64) * mv, (m, hold, float(err), float(mv))
-                if mv > 0:
-                    worst = max(worst, float(err / (Fraction(U64) * mv)))
+        worst = max(worst, float_against_exact(*fd_case(m, hold, frozen, t0_kind, seed))[0])
     print(f"worst |float - exact| / (u * magnitude) = {worst:.3f}")
     assert worst > 0.0   # the float twin does round: the bound is not vacuous
+
+
+@pytest.mark.parametrize("B,m,n,hold,frozen,seed", lc.TWIN_CASES, ids=[f"m{c[1]}-n{c[2]}" for c in lc.TWIN_CASES])
+def test_float_twin_against_the_exact_one_at_long_rows(B, m, n, hold, frozen, seed):
+    """The same bound where the sums are long: the segment counts and sample counts of tests/swarm_limit_cases.py at
+    which the device is compared with the float twin bit for bit (a second pass of the variables at m = 9, of the
+    segment table at m = 65, more than one stage of samples at n = 300)."""
+    x, Df, T = sw.crossing_rows(B, m, seed, dyadic=True)
+    span = float(np.max(np.sum(T, axis=1)))
+    dt = np.ceil(span / (n - 1) * 256.0) / 256.0
+    fz = None
+    if frozen:
+        xf, _, _ = sw.crossing_rows(B, m, seed + 100, dyadic=True)
+        fz = sw.coefficients(xf, Df, T, sw.EXACT)
+    o = dict(t_lo=0.0, dt=dt, n=n, hold_ends=hold, w=1.5, radius=2.0)
+    worst, active = float_against_exact(x, Df, T, fz, None, o)
+    print(f"m = {m}, n = {n}: {active} active terms, worst |float - exact| / (u * magnitude) = {worst:.4f}")
+    assert worst > 0.0 and active >= 100
 
 
 def test_positions_are_the_separation_twins():
